@@ -10,15 +10,23 @@ Primary workload (`--workload search`, BASELINE.json config 3/4): cosine top-10 
 10,000,000 x 768 fp16 bank.  STRONG scaling: the bank is fixed -- the same rows whatever N is (every 2^20-row block
 has its own seed) -- and row-sharded over the N ranks (rank r generates rows [r*N/G, (r+1)*N/G) on its device); a
 step is one `EmbeddingBank.search` call -- local MFMA filter + exact re-score (+ exact redo of what the filter cannot
-prove, on the device), one RCCL all-gather of the Q x k partials, merge.  `value` = queries/s.  After the timed
-region every rank PROVES the merged answer on its shard (float64 on the device, "selfcheck" in the JSON line).
-
-Secondary (reported in the same JSON line under "encode", rank 0's GPU only): ResNet-50 -> 768-d float32
-`predict_step` on 512 random 224 x 224 uint8 images (BASELINE.json config 2), images/s; and under "encode_vit_b16"
-the same batch through the ViT-B/16 fp16 embedder (config 5).
+prove, on the device), one RCCL all-gather of the Q x k partials, merge.  `value` = queries/s.
 
 `--workload encode` makes the encode the primary metric instead (replicas: every rank encodes its own batch of
 512, weak scaling, no collective).
+
+A plain run sets up, warms up, times exactly `--steps` steps and reports them; nothing else.  `--full` adds, after the
+timed steps: the per-kernel roofline (a second, bracketed loop of the same steps), the self-check -- every rank PROVES
+the merged answer on its shard (float64 on the device, "selfcheck" in the JSON line) --, the query-count / shard-size
+sweeps and bank variants (N = 1), the CPU baselines, and, for `--workload search`, secondary lines on rank 0's GPU:
+under "encode" ResNet-50 -> 768-d float32 `predict_step` on 512 random 224 x 224 uint8 images (BASELINE.json config 2),
+images/s; under "encode_vit_b16" the same batch through the ViT-B/16 fp16 embedder (config 5); under
+"encode_efficientnet_v2_s" the reference's own EfficientNetV2-S embedder.  `--no-sweep`, `--no-secondary` and
+`--no-cpu-baseline` leave parts of that out.
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step (rank 0's copy) as DIR/<name>.npy:
+floating point as float32, integer indices as float64 (exact below 2^53).  The inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 
 Rank 0 prints ONE JSON line.
 """
@@ -95,10 +103,19 @@ def parse_args() -> argparse.Namespace:
     ap.add_argument("--batch", type=int, default=512, help="encode batch (images per step per rank)")
     ap.add_argument("--pipeline-rows", type=int, default=50_000_000, help="bank rows of --workload pipeline (all ranks)")
     ap.add_argument("--no-overlap", action="store_true", help="--workload pipeline: one stream instead of two")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the query-count / shard-size sweeps (N = 1 only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline, self-check, sweeps, bank "
+                         "variants, CPU baselines, secondary encode lines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary encode lines")
+    ap.add_argument("--no-sweep", action="store_true",
+                    help="--full without the query-count / shard-size sweeps and bank variants (N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def setup_dist(args: argparse.Namespace) -> tuple[int, int, torch.device]:
@@ -487,8 +504,26 @@ def bench_search(args: argparse.Namespace, rank: int, world: int, device: torch.
     # must not sit inside the number that is quoted).  scripts/trace_headline.sh reproduces `kernel_ms_per_step` from a
     # rocprofv3 kernel trace of this same command by launch index (profiles/*_headline_trace.json).
     seconds = timed_steps(step, args.steps, args.warmup, world, device)
-    while pending:
-        pending.pop(0).result()
+    scores, indices = pending.pop().result()  # the answer of the last timed step (the only handle still pending)
+    rows = hi - lo
+    out = {
+        "metric": "queries/s cosine top-10 over N x D bank",
+        "value": round(q * args.steps / seconds, 1),
+        "unit": "queries/s",
+        "ms_per_step": round(seconds / args.steps * 1e3, 4),
+        "scaling": "strong",
+        "dtype": "f16",
+        "config": {
+            "workload": f"cosine top-{k}: {q} fp16 queries x {n} x {d} fp16 bank (BASELINE config 4 bank; "
+                        f"row-sharded {world} way{'s' if world > 1 else ''})",
+            "bank_rows": n, "dim": d, "queries": q, "k": k, "rows_per_gpu": rows,
+            "parallelism": f"row-shard{world}" + ("+allgather" if world > 1 else ""),
+        },
+        "roofline": None,
+        "_outputs": {"scores": scores, "indices": indices},
+    }
+    if not args.full:
+        return out
     _lib.timing_enable(True)
     _lib.timing_read(_lib.ISC_KERNEL_DOTS_FILTER)
     seconds_bracketed = timed_steps(step, args.steps, 0, world, device)
@@ -504,7 +539,6 @@ def bench_search(args: argparse.Namespace, rank: int, world: int, device: torch.
     del shard
     torch.cuda.empty_cache()
 
-    rows = hi - lo
     roofline = search_roofline(rows, d, q, k, kernel_ms / args.steps, launches / args.steps)
     roofline["ms_per_step_with_brackets"] = round(seconds_bracketed / args.steps * 1e3, 4)
     roofline["search_calls_in_order"] = {"warmup": args.warmup, "timed": args.steps, "bracketed": args.steps, "selfcheck": 1}
@@ -543,18 +577,7 @@ def bench_search(args: argparse.Namespace, rank: int, world: int, device: torch.
         roofline["traffic_source"] = traffic_src
         roofline["traffic_over_algorithmic"] = round(step_bytes / roofline["algorithmic_bytes_per_step"], 3)
     return {
-        "metric": "queries/s cosine top-10 over N x D bank",
-        "value": round(q * args.steps / seconds, 1),
-        "unit": "queries/s",
-        "ms_per_step": round(seconds / args.steps * 1e3, 4),
-        "scaling": "strong",
-        "dtype": "f16",
-        "config": {
-            "workload": f"cosine top-{k}: {q} fp16 queries x {n} x {d} fp16 bank (BASELINE config 4 bank; "
-                        f"row-sharded {world} way{'s' if world > 1 else ''})",
-            "bank_rows": n, "dim": d, "queries": q, "k": k, "rows_per_gpu": rows,
-            "parallelism": f"row-shard{world}" + ("+allgather" if world > 1 else ""),
-        },
+        **out,
         "roofline": roofline,
         "selfcheck": check,
         "overflowed_candidate_buffers": status[0],
@@ -599,23 +622,20 @@ def cpu_baseline_search(args: argparse.Namespace) -> dict:
 
 # ------------------------------------------------------------------------------------------------ encode
 def bench_encode(args: argparse.Namespace, rank: int, world: int, device: torch.device, steps: int, warmup: int,
-                 collective_timing: bool) -> dict:
+                 collective_timing: bool, full: bool) -> dict:
     b = args.batch
     model = ResNet50Embedder(seed=0).to(device)
     images = torch.randint(0, 256, (b, 3, 224, 224), dtype=torch.uint8,
                            generator=torch.Generator().manual_seed(SEED + rank)).to(device)
     batch = ImageBatch(indices=torch.arange(b, device=device), images=images)
+    last: list = [None]
 
     def step() -> None:
-        model.predict_step(batch)
+        last[0] = model.predict_step(batch)
 
     seconds = timed_steps(step, steps, warmup, world if collective_timing else 1, device)  # brackets off
-    kernel_ms, launches = bracketed_kernel_ms(step, steps, _lib.ISC_KERNEL_CONV)
-    flops = float(resnet50.conv_flops(b, 224, 224))
-    tflops = flops * steps / (kernel_ms / 1e3) / 1e12
     ranks = world if collective_timing else 1
-    enc_traffic, enc_traffic_src, enc_ratio = measured_encoder_traffic("resnet50", b)
-    return {
+    out = {
         "metric": "images/s encode",
         "value": round(b * ranks * steps / seconds, 1),
         "unit": "images/s",
@@ -624,6 +644,18 @@ def bench_encode(args: argparse.Namespace, rank: int, world: int, device: torch.
         "dtype": "f32",
         "config": {"workload": f"ResNet-50 (random weights) batch-{b} 224x224 uint8 -> 768-d predict_step, fp32 "
                                f"(BASELINE config 2)", "batch_per_gpu": b, "parallelism": f"replicas{ranks}"},
+        "roofline": None,
+        "_outputs": {"indices": last[0].indices, "embeddings": last[0].embeddings},
+        "_model": model, "_images": images,
+    }
+    if not full:
+        return out
+    kernel_ms, launches = bracketed_kernel_ms(step, steps, _lib.ISC_KERNEL_CONV)
+    flops = float(resnet50.conv_flops(b, 224, 224))
+    tflops = flops * steps / (kernel_ms / 1e3) / 1e12
+    enc_traffic, enc_traffic_src, enc_ratio = measured_encoder_traffic("resnet50", b)
+    return {
+        **out,
         "roofline": {
             "kernel": "k_conv_f32",
             "bound": "mfma",
@@ -640,7 +672,6 @@ def bench_encode(args: argparse.Namespace, rank: int, world: int, device: torch.
             "algorithmic_flops_per_step": flops,
             "algorithmic_bytes_per_step": float(resnet50.conv_bytes(b, 224, 224)),
         },
-        "_model": model, "_images": images,
     }
 
 
@@ -766,6 +797,8 @@ def bench_pipeline(args: argparse.Namespace, rank: int, world: int, device: torc
                    "bank_rows": n, "dim": d, "batch_per_gpu": b, "k": k, "rows_per_gpu": hi - lo,
                    "parallelism": f"encode replicas{world} + row-shard{world}" + ("+allgather" if world > 1 else "")},
         "roofline": None,
+        "_outputs": {"indices": results[-1].indices, "scores": results[-1].scores,
+                     "neighbours": results[-1].neighbours},
     }
 
 
@@ -798,17 +831,40 @@ def strip(d: dict) -> dict:
     return {k: v for k, v in d.items() if not k.startswith("_")}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, outputs: dict[str, torch.Tensor]) -> None:
+    """`--dump-outputs`: one DIR/<name>.npy per array the timed path returned in its last step, floating point as float32
+    and integers as float64.  Above DUMP_LIMIT_BYTES in all, every array keeps a fixed, seeded sample of its rows, and
+    DIR/<name>_rows.npy says which."""
+    import numpy as np
+
+    arrays = {name: (t.float() if t.is_floating_point() else t.double()).cpu().numpy() for name, t in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = DUMP_LIMIT_BYTES / total / 2  # half the budget: room for the row lists
+        for name in list(arrays):
+            n = len(arrays[name])
+            rows = np.sort(np.random.default_rng(SEED).choice(n, max(1, int(n * frac)), replace=False))
+            arrays[name] = arrays[name][rows]
+            arrays[f"{name}_rows"] = rows.astype(np.float64)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def main() -> None:
     args = parse_args()
     rank, world, device = setup_dist(args)
     torch.manual_seed(SEED)
     if args.workload == "search":
         primary = bench_search(args, rank, world, device)
-        primary.pop("_bank"), primary.pop("_queries")
+        primary.pop("_bank", None), primary.pop("_queries", None)
         torch.cuda.empty_cache()
         secondary = secondary_vit = secondary_eff = None
-        if not args.no_secondary and rank == 0:
-            secondary = bench_encode(args, rank, world, device, steps=6, warmup=2, collective_timing=False)
+        if args.full and not args.no_secondary and rank == 0:
+            secondary = bench_encode(args, rank, world, device, steps=6, warmup=2, collective_timing=False, full=True)
             secondary.pop("_model"), secondary.pop("_images")
             torch.cuda.empty_cache()
             secondary_vit = bench_encode_vit(args, device, steps=6, warmup=2)
@@ -818,8 +874,12 @@ def main() -> None:
         primary = bench_pipeline(args, rank, world, device)
         secondary = secondary_vit = secondary_eff = None
     else:
-        primary = bench_encode(args, rank, world, device, args.steps, args.warmup, collective_timing=True)
+        primary = bench_encode(args, rank, world, device, args.steps, args.warmup, collective_timing=True,
+                               full=args.full)
         secondary = secondary_vit = secondary_eff = None
+    outputs = primary.pop("_outputs")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), outputs)
     if world > 1:
         dist.barrier()
     if rank == 0:
@@ -848,7 +908,7 @@ def main() -> None:
             line["scaling_projection"] = primary["scaling_projection"]
         if primary.get("bank_variants"):
             line["bank_variants"] = primary["bank_variants"]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.workload != "pipeline":
                 line["cpu_baseline"] = (cpu_baseline_search(args) if args.workload == "search"
                                         else cpu_baseline_encode(args))

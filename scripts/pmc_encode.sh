@@ -3,7 +3,7 @@
 set -o pipefail
 TAG=${1:-r01}
 OUT=gpurun_out/pmc_encode_${TAG}
-ARGS="--workload encode --steps 3 --warmup 1 --no-cpu-baseline"
+ARGS="--full --workload encode --steps 3 --warmup 1 --no-cpu-baseline"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p "$OUT"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -- python3 bench.py $ARGS > "$OUT/bench_fetch.json" 2> "$OUT/fetch.err" &&

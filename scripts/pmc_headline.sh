@@ -5,7 +5,7 @@
 set -o pipefail
 TAG=${1:-r01}
 OUT=gpurun_out/pmc_headline_${TAG}
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-sweep"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-sweep"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p "$OUT"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -- python3 bench.py $ARGS > "$OUT/bench_fetch.json" 2> "$OUT/fetch.err" &&

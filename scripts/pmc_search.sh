@@ -7,7 +7,7 @@ COUNTERS=${@:-SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_AN
 OUT=gpurun_out/pmc_${TAG}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p "$OUT"
-rocprofv3 --kernel-trace --pmc $COUNTERS --output-format csv -d "$OUT" -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > "$OUT/bench.json" 2> "$OUT/err.log"
+rocprofv3 --kernel-trace --pmc $COUNTERS --output-format csv -d "$OUT" -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-secondary > "$OUT/bench.json" 2> "$OUT/err.log"
 echo "exit $?"; tail -2 "$OUT/err.log"
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/<tag>_headline_trace.json from a rocprofv3 kernel trace of `python bench.py --no-sweep --no-secondary
+"""profiles/<tag>_headline_trace.json from a rocprofv3 kernel trace of `python bench.py --full --no-sweep --no-secondary
 --no-cpu-baseline` (scripts/trace_headline.sh).
 
 The bench issues its searches in a known order -- W warm-up, K timed (event brackets off: `value`), K bracketed
@@ -56,7 +56,7 @@ peak = line["roofline"]["peak"] if line["roofline"]["unit"] == "TFLOP/s" else 25
 frac_trace = flops / (mean / 1e3) / 1e12 / peak
 out = {
     "tag": tag,
-    "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-sweep --no-secondary --no-cpu-baseline",
+    "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-sweep --no-secondary --no-cpu-baseline",
     "searches_in_trace": len(searches), "searches_expected": expect,
     "timed_steps": per_step,
     "k_dots_filter_ms_per_timed_step_mean": round(mean, 4),

@@ -25,8 +25,8 @@ for (_, kind), c in per.items():
     if c.get("SQ_WAVE_CYCLES", 0) < 1e6:  # an empty (early-exit) redo launch
         continue
     groups[kind].append(c)
-out = {"tag": tag, "method": "scripts/pmc_stalls.sh: rocprofv3 --kernel-trace --pmc SQ_* (one pass) over bench.py --steps 3 "
-                             "(10M x 768 fp16, Q = 1024); shares of SQ_WAVE_CYCLES", "kernels": {}}
+out = {"tag": tag, "method": "scripts/pmc_stalls.sh: rocprofv3 --kernel-trace --pmc SQ_* (one pass) over bench.py --full "
+                             "--steps 3 (10M x 768 fp16, Q = 1024); shares of SQ_WAVE_CYCLES", "kernels": {}}
 for kind, rows in groups.items():
     tot = lambda k: sum(r.get(k, 0.0) for r in rows)
     wc = tot("SQ_WAVE_CYCLES")

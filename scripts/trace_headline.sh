@@ -8,5 +8,5 @@ TAG=${1:-r04}
 OUT=gpurun_out/trace_headline_${TAG}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 rm -rf "$OUT" && mkdir -p "$OUT"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --no-sweep --no-secondary --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" &&
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --full --no-sweep --no-secondary --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" &&
 python3 scripts/summarize_headline_trace.py "$TAG" "$OUT"
