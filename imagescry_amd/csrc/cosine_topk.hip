@@ -1384,50 +1384,6 @@ __global__ __launch_bounds__(SEL_THREADS, 4) void k_select(int32_t* __restrict__
     }
 }
 
-// 16 bytes of a packed row as float64 values
-template <typename T>
-struct Chunk16;
-template <>
-struct Chunk16<_Float16> {
-    static constexpr int N = 8;
-    static __device__ __forceinline__ void load(const unsigned char* p, double (&v)[8]) {
-        const uint4 raw = *reinterpret_cast<const uint4*>(p);
-        const _Float16* h = reinterpret_cast<const _Float16*>(&raw);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (double)(float)h[j];
-    }
-};
-template <>
-struct Chunk16<float> {
-    static constexpr int N = 4;
-    static __device__ __forceinline__ void load(const unsigned char* p, double (&v)[8]) {
-        const float4 raw = *reinterpret_cast<const float4*>(p);
-        v[0] = (double)raw.x;
-        v[1] = (double)raw.y;
-        v[2] = (double)raw.z;
-        v[3] = (double)raw.w;
-    }
-};
-
-// float64 norm of the packed query row at `qrow_base` (K step s at + s * tnq * 128 B); called by ONE wave, result in
-// every lane
-template <typename T>
-__device__ double wave_query_norm(const unsigned char* qrow_base, int ks, int tnq) {
-    const int lane = threadIdx.x & 63;
-    const int sub = lane >> 3, ch = lane & 7;
-    double acc = 0.0;
-    for (int s0 = 0; s0 < ks; s0 += 8) {
-        const int s = s0 + sub;
-        if (s < ks) {
-            double v[8];
-            Chunk16<T>::load(qrow_base + (size_t)s * tnq * ISC_KSTEP_BYTES + ch * 16, v);
-#pragma unroll
-            for (int j = 0; j < Chunk16<T>::N; ++j) acc = fma(v[j], v[j], acc);
-        }
-    }
-    return isc_wave_sum(acc);
-}
-
 // Exact float64 dots of `nc` candidates with one query: one wave per candidate, a lane covers the 16-byte chunk `ch` of
 // K steps sub, sub + 8, ...; four candidates of a wave are in flight together (their loads are independent).
 // row_of(c) -> packed row or -1; store(c, dot) is called by lane 0 of the wave that owns candidate c (dot = 0 for row -1).

@@ -1,10 +1,11 @@
-// Pieces shared by the search kernels (cosine_topk.hip) and the exact float64 search (search_exact.hip).
+// Pieces shared by the search kernels (cosine_topk.hip, search_range.hip) and the exact float64 search (search_exact.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "bank_layout.h"
+#include "isc_common.h"
 
 // ---- (score, row) as one 64-bit key whose unsigned order is the search order ------------------------------------
 // larger key = better candidate: higher score first, then LOWER row.  Keys of distinct rows are distinct.  A NaN
@@ -66,6 +67,51 @@ __device__ __forceinline__ unsigned long long isc_wave_max_key(unsigned long lon
         }
     }
     return ((unsigned long long)hi << 32) | lo;
+}
+
+// ---- float64 arithmetic shared by the exact re-scores of cosine_topk.hip and search_range.hip ---------------------
+// 16 bytes of a packed row as float64 values
+template <typename T>
+struct Chunk16;
+template <>
+struct Chunk16<_Float16> {
+    static constexpr int N = 8;
+    static __device__ __forceinline__ void load(const unsigned char* p, double (&v)[8]) {
+        const uint4 raw = *reinterpret_cast<const uint4*>(p);
+        const _Float16* h = reinterpret_cast<const _Float16*>(&raw);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (double)(float)h[j];
+    }
+};
+template <>
+struct Chunk16<float> {
+    static constexpr int N = 4;
+    static __device__ __forceinline__ void load(const unsigned char* p, double (&v)[8]) {
+        const float4 raw = *reinterpret_cast<const float4*>(p);
+        v[0] = (double)raw.x;
+        v[1] = (double)raw.y;
+        v[2] = (double)raw.z;
+        v[3] = (double)raw.w;
+    }
+};
+
+// float64 norm of the packed query row at `qrow_base` (K step s at + s * tnq * 128 B); called by ONE wave, result in
+// every lane
+template <typename T>
+__device__ double wave_query_norm(const unsigned char* qrow_base, int ks, int tnq) {
+    const int lane = threadIdx.x & 63;
+    const int sub = lane >> 3, ch = lane & 7;
+    double acc = 0.0;
+    for (int s0 = 0; s0 < ks; s0 += 8) {
+        const int s = s0 + sub;
+        if (s < ks) {
+            double v[8];
+            Chunk16<T>::load(qrow_base + (size_t)s * tnq * ISC_KSTEP_BYTES + ch * 16, v);
+#pragma unroll
+            for (int j = 0; j < Chunk16<T>::N; ++j) acc = fma(v[j], v[j], acc);
+        }
+    }
+    return isc_wave_sum(acc);
 }
 
 // ---- exact float64 search of a LIST of queries (search_exact.hip) -------------------------------------------------

@@ -29,6 +29,7 @@ search i + 1.
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from os import PathLike
 from typing import Sequence
 
@@ -39,7 +40,7 @@ from torch import Tensor
 from imagescry_amd import _lib
 from imagescry_amd.data import EmbeddingBatch
 
-__all__ = ["EmbeddingBank", "SearchHandle", "shard_bounds"]
+__all__ = ["EmbeddingBank", "RangeResult", "SearchHandle", "shard_bounds"]
 
 _PAD_INDEX = torch.iinfo(torch.int64).max
 
@@ -93,6 +94,32 @@ class SearchHandle:
                 if t is not None:
                     t.record_stream(cur)
         return self._scores, self._indices
+
+
+@dataclass
+class RangeResult:
+    """Result of `EmbeddingBank.search_range`: query q's rows are `scores[offsets[q]:offsets[q + 1]]` /
+    `indices[...]`, ordered by (score descending, row index ascending).  All three tensors live on the bank's device."""
+
+    offsets: Tensor  # int64 [Q + 1]
+    scores: Tensor  # float32 [M]
+    indices: Tensor  # int64 [M]
+
+    def __len__(self) -> int:
+        return self.offsets.shape[0] - 1
+
+    @property
+    def counts(self) -> Tensor:
+        """int64 [Q]: rows per query."""
+        return self.offsets[1:] - self.offsets[:-1]
+
+    def __getitem__(self, q: int) -> tuple[Tensor, Tensor]:
+        n = len(self)
+        if not -n <= q < n:
+            raise IndexError(f"query {q} out of range for {n} queries")
+        q %= n
+        lo, hi = (int(v) for v in self.offsets[q : q + 2].tolist())
+        return self.scores[lo:hi], self.indices[lo:hi]
 
 
 class _ExchangeSlot:
@@ -160,6 +187,8 @@ class EmbeddingBank:
         self._slot_next = 0
         self._xstream: "torch.cuda.Stream | None" = None
         self.last_status: Tensor | None = None
+        self.last_range_status: Tensor | None = None
+        self._range_ws: Tensor | None = None  # the range search's workspace, grown on demand
         self.last_gathered_status: Tensor | None = None
         self.row_origin: Tensor | None = None  # set by from_database: (image_id, h, w) of every row
 
@@ -529,3 +558,136 @@ class EmbeddingBank:
         gathered = torch.empty(self.world_size * src.numel(), dtype=torch.uint8, device=src.device)
         dist.all_gather_into_tensor(gathered, src, group=self.process_group)
         return gathered.to(xbuf.device).view(self.world_size, src.numel())
+
+    # ------------------------------------------------------------------ range search
+    # Entries the first attempt of a range search reserves per query; a larger result costs one more call with the exact
+    # capacity the first one reported.
+    _RANGE_GUESS_PER_QUERY = 2048
+
+    def _range_thresholds(self, min_score: "float | Tensor", nq: int) -> Tensor:
+        if isinstance(min_score, Tensor):
+            if min_score.shape != (nq,):
+                raise ValueError(f"min_score must be a float or a [Q] = [{nq}] tensor, got shape {tuple(min_score.shape)}")
+            if min_score.dtype != torch.float32:
+                raise TypeError(f"min_score tensor must be float32, got {min_score.dtype}")
+            if bool(torch.isnan(min_score).any()):
+                raise ValueError("min_score contains NaN")
+            return min_score.to(self.device).contiguous()
+        if isinstance(min_score, bool) or not isinstance(min_score, (int, float)):
+            raise TypeError(f"min_score must be a float or a float32 tensor, got {type(min_score).__name__}")
+        if math.isnan(min_score):
+            raise ValueError("min_score is NaN")
+        return torch.full((nq,), float(min_score), dtype=torch.float32, device=self.device)
+
+    def _range_call(self, q: Tensor, thr: Tensor, capacity: int) -> tuple[int, RangeResult, Tensor]:
+        """One `isc_cosine_range` call: (needed, result -- valid only when needed <= capacity --, status int32[4])."""
+        lib = _lib.load()
+        nq = q.shape[0]
+        code = _lib.dtype_code(self.dtype)
+        need = _lib.c_size_t()
+        _lib.check(lib.isc_cosine_range_workspace_bytes(code, self.num_local_rows, self.dim, nq, capacity, need),
+                   "isc_cosine_range_workspace_bytes")
+        if self._range_ws is None or self._range_ws.numel() < need.value:
+            self._range_ws = None
+            self._range_ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        ws = self._range_ws
+        offsets = torch.empty(nq + 1, dtype=torch.int64, device=self.device)
+        scores = torch.empty(capacity, dtype=torch.float32, device=self.device)
+        indices = torch.empty(capacity, dtype=torch.int64, device=self.device)
+        needed = torch.empty(1, dtype=torch.int64, device=self.device)
+        status = torch.empty(4, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = lib.isc_cosine_range(
+                self._bank.data_ptr(), code, self.num_local_rows, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
+                q.stride(0), thr.data_ptr(), self.index_base, self._norm_bound.data_ptr(), capacity,
+                offsets.data_ptr(), scores.data_ptr(), indices.data_ptr(), needed.data_ptr(), status.data_ptr(),
+                ws.data_ptr(), ws.numel(), _lib.stream_handle(self.device),
+            )
+        _lib.check(st, "isc_cosine_range")
+        return int(needed.item()), RangeResult(offsets, scores, indices), status
+
+    def _local_range(self, queries: Tensor, min_score: Tensor, max_results: int) -> tuple[int, RangeResult | None]:
+        """Range search of this rank's rows with GLOBAL row indices: `(total, result)`; `result` is None when `total`
+        exceeds `max_results` (then `total` is the exact row count, or, when even counting would need more than twice
+        `max_results` entries, the filter's candidate count, an upper bound of it)."""
+        nq = queries.shape[0]
+        if self.num_local_rows == 0 or nq == 0:
+            empty = RangeResult(torch.zeros(nq + 1, dtype=torch.int64, device=self.device),
+                                torch.empty(0, dtype=torch.float32, device=self.device),
+                                torch.empty(0, dtype=torch.int64, device=self.device))
+            return 0, empty
+        limit = min(max(max_results, 1), 0x7FFFFFFF)
+        cap = min(max(1 << 16, self._RANGE_GUESS_PER_QUERY * nq), limit)
+        needed, res, status = self._range_call(queries, min_score, cap)
+        if needed > cap:
+            if needed > 2 * limit or needed > 0x7FFFFFFF:
+                self.last_range_status = status
+                return needed, None
+            needed, res, status = self._range_call(queries, min_score, needed)
+        self.last_range_status = status
+        total = int(res.offsets[-1].item())
+        if total > max_results:
+            return total, None
+        return total, RangeResult(res.offsets, res.scores[:total], res.indices[:total])
+
+    def search_range(self, queries: Tensor, min_score: "float | Tensor", *, max_results: int = 1 << 26) -> RangeResult:
+        """Every row whose cosine score against a query is >= `min_score` (a float, or a float32 `[Q]` tensor of
+        per-query thresholds): a `RangeResult` whose query q holds its rows ordered by (score descending, row index
+        ascending), indices global.  Exact: the scores and the membership are those of the top-k (`search`), so with
+        t = the k-th score of `search(q, k)` the first k rows of `search_range(q, t)` are `search(q, k)`.  NaN scores
+        are never in a result.
+
+        The call synchronises the host to size the output (like `torch.nonzero`); a result larger than the first
+        internal guess costs a second device call of the exact size.  More than `max_results` rows in all raise
+        ValueError with the count.  `last_range_status` (int32[4], device) holds diagnostics: [0] filter candidates,
+        [1] queries answered by the float64 sweep, [2] float bits of the largest filter error in units of its bound.
+        A sharded bank searches its shard on every rank, all-gathers the per-rank totals and then the rows, and every
+        rank merges them into the answer of the unsharded bank."""
+        q = self._prepare_queries(queries)
+        nq = q.shape[0]
+        thr = self._range_thresholds(min_score, nq)
+        if isinstance(max_results, bool) or not isinstance(max_results, int) or max_results < 0:
+            raise ValueError(f"max_results must be a non-negative int, got {max_results!r}")
+        total, res = self._local_range(q, thr, max_results)
+        if self.process_group is None:
+            if res is None:
+                raise ValueError(f"search_range found {total} rows, more than max_results={max_results}")
+            return res
+        return self._exchange_range(nq, total, res, max_results)
+
+    def _exchange_range(self, nq: int, total: int, res: RangeResult | None, max_results: int) -> RangeResult:
+        """Two all-gathers (per-rank totals, then the padded rows) and the merge into (query, score desc, index asc)
+        order.  Every rank issues the same collectives whatever its shard holds."""
+        g = self.world_size
+        dev = self.device
+        tot = torch.tensor([total, 0 if res is not None else 1], dtype=torch.int64, device=dev)
+        all_tot = self._all_gather_bytes(tot.view(torch.uint8)).view(torch.int64).view(g, 2).cpu()
+        merged = int(all_tot[:, 0].sum())
+        if merged > max_results or bool(all_tot[:, 1].any()):
+            raise ValueError(f"search_range found {merged}{'' if not all_tot[:, 1].any() else ' or more'} rows, more "
+                             f"than max_results={max_results}")
+        if merged == 0:
+            return RangeResult(torch.zeros(nq + 1, dtype=torch.int64, device=dev),
+                               torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int64, device=dev))
+        width = int(all_tot[:, 0].max())
+        # payload of this rank: [query int64 | index int64 | score float32 (as 8 bytes)] x width, padding rows unused
+        pay = torch.zeros((3, width), dtype=torch.int64, device=dev)
+        if total:
+            assert res is not None
+            pay[0, :total] = torch.repeat_interleave(torch.arange(nq, device=dev), res.counts)
+            pay[1, :total] = res.indices
+            pay[2, :total] = res.scores.to(torch.float64).view(torch.int64)
+        gathered = self._all_gather_bytes(pay.view(-1).view(torch.uint8)).view(torch.int64).view(g, 3, width)
+        keep = torch.arange(width, device=dev)[None, :] < all_tot[:, 0].to(dev)[:, None]  # [G, width]
+        qs = gathered[:, 0][keep]
+        idx = gathered[:, 1][keep]
+        sc = gathered[:, 2][keep].view(torch.float64).to(torch.float32)
+        # ranks are gathered in row order and each rank's rows of a query come index-ascending within a score, so two
+        # stable sorts -- score descending, then query -- give (query, score desc, index asc)
+        order = torch.sort(sc, descending=True, stable=True).indices
+        qs, idx, sc = qs[order], idx[order], sc[order]
+        order = torch.sort(qs, stable=True).indices
+        qs, idx, sc = qs[order], idx[order], sc[order]
+        offsets = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+        offsets[1:] = torch.cumsum(torch.bincount(qs, minlength=nq), 0)
+        return RangeResult(offsets, sc, idx)

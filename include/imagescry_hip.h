@@ -348,6 +348,32 @@ int isc_cosine_topk_exhaustive(const void* bank, int dtype, int64_t N, int D, co
                                int64_t ldq, int k, int64_t index_base, float* out_scores, int64_t* out_indices,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Exact cosine range search: for every query, EVERY row with score(q, b) >= min_score[q], with the score of
+ * isc_cosine_topk (the query rounded to the bank dtype first; float32(dot_f64(q, b) / max(||q||_2, 1e-12))).  NaN scores
+ * are never in a result.  Each query's rows are ordered by (score descending, row index ascending) -- the top-k's order, so
+ * with t = the k-th score of isc_cosine_topk the first k rows of a query are its top-k, bit for bit.  Same pipeline idea
+ * as isc_cosine_topk's redo pass: an fp32 matrix-core filter against a per-query threshold just below t less the rounding
+ * bound, every survivor re-scored in float64, a float64 sweep for queries outside the range where the bound holds (a bank
+ * with a NaN / inf row: every query).  No host round trip.
+ *   bank, dtype, N, D, queries, q_dtype, Q, ldq, index_base, norm_bound   as isc_cosine_topk (1 <= N <= 2^31 - 2)
+ *   min_score    device float [Q]: the threshold t of each query (NaN: empty result)
+ *   capacity     entries of `scores` / `indices` and of the workspace's candidate buffer, 1 .. 2^31 - 1
+ *   offsets      int64_t [Q + 1]: query q's rows are [offsets[q], offsets[q + 1]) of scores / indices
+ *   scores       float   [capacity]
+ *   indices      int64_t [capacity]  row index + index_base
+ *   needed       device int64_t [1]: the capacity this call needs (filter candidates + rows of zero queries with t <= 0,
+ *                an upper bound of offsets[Q]).  When it exceeds `capacity` NOTHING is usable -- offsets are all 0 -- and
+ *                the caller re-issues the call with capacity >= needed (the count is exact, so one retry suffices)
+ *   status       int32_t [4] device words, diagnostics only: [0] = filter candidates (saturating), [1] = queries that
+ *                took the float64 sweep, [2] = float bits of max |filter score - exact dot| / rounding bound over the
+ *                re-scored candidates (must stay < 1), [3] = reserved (0)
+ * The workspace depends on (dtype, D, min(Q, 1024), Q, capacity); calls with Q > 1024 run as passes of 1024 queries. */
+int isc_cosine_range_workspace_bytes(int dtype, int64_t N, int D, int Q, int64_t capacity, size_t* bytes);
+int isc_cosine_range(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q, int64_t ldq,
+                     const float* min_score, int64_t index_base, const float* norm_bound, int64_t capacity,
+                     int64_t* offsets, float* scores, int64_t* indices, int64_t* needed, int32_t* status,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* Merge G partial results (e.g. one per bank shard after the all-gather) into the final top-k by
  * (score descending, index ascending): scores float [G,Q,kin], indices int64 [G,Q,kin] -> [Q,kout], kout <= G*kin <= 4096.
  * `stride_g_*` = distance in ELEMENTS between the [Q,kin] blocks of consecutive shards (0 = dense); this lets the merge
