@@ -8,7 +8,8 @@ Public surface (same names as the reference where the reference has them):
   `ResNet50Embedder`, `ViTB16Embedder`           -- reference src/imagescry/models/embedding.py:27-183
 * `PCA`, `EmbeddingPCAPipeline`                  -- reference src/imagescry/models/decomposition.py, pipelines.py
 * `EmbedSearchPipeline`                          -- encode -> search on two HIP streams (BASELINE config 5; new)
-* `EmbeddingBank`, `RangeResult`                 -- cosine top-k and range search (new; see search.py)
+* `EmbeddingBank`, `RangeResult`, `RowFilter`    -- cosine top-k and range search, optionally over a row filter (new;
+  see search.py)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/imagescry_hip.h;
 PyTorch is used for device memory, streams and `torch.distributed` only.
@@ -25,7 +26,7 @@ from imagescry_amd.embedding import (
     l2_normalize_channels,
 )
 from imagescry_amd.pipelines import EmbeddingPCAPipeline, EmbedSearchPipeline, SearchResult
-from imagescry_amd.search import EmbeddingBank, RangeResult, SearchHandle, shard_bounds
+from imagescry_amd.search import EmbeddingBank, RangeResult, RowFilter, SearchHandle, shard_bounds
 from imagescry_amd.transforms import normalize_per_channel, resize, to_4d
 
 __all__ = [
@@ -39,6 +40,7 @@ __all__ = [
     "SearchResult",
     "PCA",
     "RangeResult",
+    "RowFilter",
     "ResNet50Embedder",
     "ViTB16Embedder",
     "l2_normalize_channels",

@@ -152,6 +152,23 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
         [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int64,
          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "isc_row_mask_words": (c_int, [c_int64, POINTER(c_size_t)]),
+    "isc_row_mask_pack": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "isc_cosine_topk_masked": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p, c_void_p],
+    ),
+    "isc_cosine_topk_exhaustive_masked": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p,
+         c_void_p, c_size_t, c_void_p, c_void_p],
+    ),
+    "isc_cosine_range_masked": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p],
+    ),
     "isc_topk_merge": (
         c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p]
     ),

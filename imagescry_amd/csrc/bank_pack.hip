@@ -1,5 +1,6 @@
 // Packing of embedding rows into the tile-contiguous, row-permuted bank layout (include/imagescry_hip.h:
-// isc_bank_pack, isc_bank_unpack, isc_bank_packed_bytes, isc_bank_permutation).
+// isc_bank_pack, isc_bank_unpack, isc_bank_packed_bytes, isc_bank_permutation), and of a row filter into the same row
+// order (isc_row_mask_words, isc_row_mask_pack).
 #include "bank_layout.h"
 #include "isc_common.h"
 
@@ -84,6 +85,21 @@ __global__ __launch_bounds__(256) void k_bank_unpack(const unsigned char* __rest
     const int lane = threadIdx.x & 63;
     const int64_t row = isc_perm_pos(pm, first_row + r);
     for (int e = lane; e < d; e += 64) y[r * ldy + e] = isc_packed_load<T>(packed, row, e, ks);
+}
+
+// Row filter of a masked search: one thread per PACKED position p of the padded bank, allowed iff p < n and
+// allow[orig(p)] != 0; a wave's ballot is two bitmap words, written by lanes 0 and 32.  The allowed rows of the wave are
+// added to `allowed_count` with one atomic.
+__global__ __launch_bounds__(256) void k_row_mask_pack(const uint8_t* __restrict__ allow, IscPerm pm,
+                                                       uint32_t* __restrict__ packed_mask,
+                                                       unsigned long long* __restrict__ allowed_count) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool ok = p < pm.n && allow[isc_perm_orig(pm, p)] != 0;
+    const unsigned long long bits = __ballot(ok);
+    if (lane == 0) packed_mask[p >> 5] = (uint32_t)bits;
+    if (lane == 32) packed_mask[p >> 5] = (uint32_t)(bits >> 32);
+    if (allowed_count && lane == 0 && bits != 0ull) atomicAdd(allowed_count, (unsigned long long)__popcll(bits));
 }
 
 int check_dtype(int dtype) { return dtype == ISC_F16 || dtype == ISC_F32; }
@@ -184,5 +200,21 @@ extern "C" int isc_bank_unpack(const void* packed, int dtype, int D, int64_t n_t
     else
         hipLaunchKernelGGL(k_bank_unpack<float>, dim3((unsigned)blocks), dim3(256), 0, isc_stream(stream), in, D,
                            isc_ksteps(D, 4), pm, first_row, n_rows, static_cast<float*>(rows), ldy);
+    return isc_launch_status();
+}
+
+extern "C" int isc_row_mask_words(int64_t N, size_t* words) {
+    ISC_REQUIRE(words && N > 0 && N <= 0x7ffffffe);
+    *words = (size_t)isc_ceil_div<int64_t>(N, ISC_TILE_ROWS) * (ISC_TILE_ROWS / 32);
+    return ISC_OK;
+}
+
+extern "C" int isc_row_mask_pack(const uint8_t* allow, int64_t N, uint32_t* packed_mask, int64_t* allowed_count,
+                                 void* stream) {
+    ISC_REQUIRE(allow && packed_mask && N > 0 && N <= 0x7ffffffe);
+    if (!isc_aligned(packed_mask, 4) || !isc_aligned(allowed_count, 8)) return ISC_ERR_ALIGNMENT;
+    const int64_t tiles = isc_ceil_div<int64_t>(N, ISC_TILE_ROWS);
+    hipLaunchKernelGGL(k_row_mask_pack, dim3((unsigned)tiles), dim3(256), 0, isc_stream(stream), allow, isc_make_perm(N),
+                       packed_mask, reinterpret_cast<unsigned long long*>(allowed_count));
     return isc_launch_status();
 }

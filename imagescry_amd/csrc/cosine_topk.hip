@@ -418,7 +418,10 @@ constexpr int A_TILE_BYTES = TM * 128;  // 32 KiB: one K step of one bank tile
 // 2 = no staging after the prologue, 3 = staging but no MFMAs, 41 / 43 = the query operand ablations, 7 = like 2 without LDS fragment reads, 11 = no
 // half-row-block stagger of the wm = 1 waves, 15 = DMA issued but never waited for, 17 = DMA and MFMAs but no LDS
 // fragment reads.
-template <typename T, int TNQ, int DBG, bool SAMPLE>
+//
+// RowMask: empty, or the row filter of a masked search (isc_row_mask_pack; search_common.h): the rows it disallows become
+// -inf where the rows past the end do, so they are never a candidate and never count towards a bound.
+template <typename T, int TNQ, int DBG, bool SAMPLE, typename... RowMask>
 __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* __restrict__ bank, int64_t r0,
                                                           int64_t r1, int tiles_per_chunk, int ntiles,
                                                           const unsigned char* __restrict__ qpacked, int ksteps,
@@ -426,7 +429,8 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
                                                           Cand* __restrict__ seg_ent, int32_t* __restrict__ qcount,
                                                           Cand* __restrict__ qlist, int kp, int nslots,
                                                           int32_t* __restrict__ qflag, int32_t* __restrict__ status,
-                                                          const int32_t* __restrict__ active) {
+                                                          const int32_t* __restrict__ active, RowMask... row_mask) {
+    constexpr bool MASK = sizeof...(RowMask) > 0;
     // DBG 20 / 32 / 33 are the REDO instantiations of 0 / 12 / 13 (k_final2's feeder: the whole bank against the fixed
     // thresholds of the listed queries).  They are kernels of their own so that a profile lists them apart from the
     // search's streaming launches; `active` counts the listed query slots -- normally zero, and the launch ends here.
@@ -598,6 +602,41 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
 #pragma unroll
         for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+    // ---- row filter (MASK).  A wave's rows of a tile are MBE blocks of 16 from wave_row0; block m is bits
+    // (SUB + 16 m) % 32 .. + 15 of word (SUB + 16 m) / 32 of the wave's words, which start at word wave_row0 / 32 of the
+    // tile's eight.  SUB (wave_row0 % 32) is 16 only for the wm = 1 waves of an odd asymmetric split, and known at compile
+    // time wherever the words are used.  The address is wave-uniform: scalar loads, issued at the tile's first K step and
+    // consumed at its end.
+    constexpr int MASK_WORDS = (16 + MBMAX * 16 + 31) / 32;
+    auto load_mask = [&](auto mbe_c, auto sub_c, int64_t gtile, uint32_t (&w)[MASK_WORDS]) {
+        constexpr int MBE = decltype(mbe_c)::value, SUB = decltype(sub_c)::value, NW = (SUB + MBE * 16 + 31) / 32;
+        // (the constant address space: the bitmap does not change during the kernel, which lets the wave-uniform address
+        // go to the scalar unit)
+        typedef const __attribute__((address_space(4))) uint32_t ConstWord;
+        ConstWord* src = (ConstWord*)(isc_row_mask_ptr(row_mask...) + gtile * (TM / 32) + (wave_row0 >> 5));
+#pragma unroll
+        for (int i = 0; i < NW; ++i) w[i] = src[i];
+    };
+    // disallowed rows -> -inf; a block whose sixteen rows are all allowed skips the select (wave-uniform test)
+    auto apply_mask = [&](auto mbe_c, auto sub_c, const uint32_t (&w)[MASK_WORDS]) {
+        constexpr int MBE = decltype(mbe_c)::value, SUB = decltype(sub_c)::value;
+#pragma unroll
+        for (int m = 0; m < MBE; ++m) {
+            const uint32_t bits = w[(SUB + 16 * m) >> 5] >> ((SUB + 16 * m) & 31);
+            if ((bits & 0xffffu) == 0xffffu) continue;
+            const uint32_t nib = bits >> (fg * 4);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (!((nib >> r) & 1u)) {
+#pragma unroll
+                    for (int n = 0; n < 4; ++n) acc[m][n][r] = -INFINITY;
+                }
+        }
+    };
+    [[maybe_unused]] uint32_t sample_mask[MASK_WORDS];
+    if constexpr (MASK && SAMPLE)  // the one tile of a sample workgroup: its words are in flight during the whole loop
+        load_mask(std::integral_constant<int, MB>{}, std::integral_constant<int, 0>{}, (r0 >> 8) + tile_begin, sample_mask);
+
     const int seg = (chunk * WM + wm) * 4 + fg;
     Cand* my_ent = seg_ent + ((size_t)seg * qpad + q0 + wn * 64 + frow) * CAP;  // + n * 16 * CAP
 
@@ -633,9 +672,16 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
     // so neither version pays for the other's registers.
     auto main_loop = [&](auto stagger_tag) {
     constexpr bool STAGGER = decltype(stagger_tag)::value;
+    // this copy's row blocks, and the row filter's offset of its first one inside a word (see load_mask)
+    using MBE_C = std::integral_constant<int, STAGGER ? MBHI : MBLO>;
+    using SUB_C = std::integral_constant<int, (TNQ == 256 && STAGGER) ? ((ASYM ? MBLO : MB) * 16) & 31 : 0>;
     int kt = 0, tile = 0;
+    [[maybe_unused]] uint32_t tile_mask[MASK_WORDS];
     if constexpr (MODE == 22) st_prev = stamp();
     for (int step = 0; step < total_steps; ++step) {
+        if constexpr (MASK && !SAMPLE) {
+            if (kt == 0) load_mask(MBE_C{}, SUB_C{}, (r0 >> 8) + tile_begin + tile, tile_mask);
+        }
         if constexpr (HM) {
             // ---- 256-query shape, half-major.  A K step is 2 MBW units: unit u = (row block u % MBW, half u / MBW), four
             // MFMAs (fp16) each.  LDS read stream of a wave and step (the LDS returns in order; every counted wait below is
@@ -975,6 +1021,7 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
             kt = 0;
             constexpr int MBE = STAGGER ? MBHI : MBLO;  // this wave's row blocks (MB when the split is symmetric)
             const int64_t trow0 = r0 + (int64_t)(tile_begin + tile) * TM + wave_row0 + fg * 4;
+            if constexpr (MASK) apply_mask(MBE_C{}, SUB_C{}, tile_mask);
             // rows past the end of the level exist only in its last tile: they become -inf there, once, instead of
             // being tested per element
             if (r0 + (int64_t)(tile_begin + tile + 1) * TM > r1) {
@@ -1067,6 +1114,7 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
         // the whole bank.  With nslots ~ 2 kp about 1.35 kp scores per query pass.  nslots = 0 (kp > 64): every score
         // is kept.  Rows past the end of the bank count as -inf.
         const int64_t trow0 = r0 + (int64_t)tile_begin * TM + wm * (TM / WM) + fg * 4;
+        if constexpr (MASK) apply_mask(std::integral_constant<int, MB>{}, std::integral_constant<int, 0>{}, sample_mask);
 #pragma unroll
         for (int m = 0; m < MB; ++m)
 #pragma unroll
@@ -1440,7 +1488,9 @@ struct RedoLists {
 
 // One workgroup per query: last selection, exact float64 re-score of the carried candidates, final order, output,
 // and the guard that proves the float32 filter lost nothing (see the file header).
-template <typename T, int SPEC>
+// MASK: the search ran with a row filter.  A query may then have fewer allowed rows than k: its last positions get the ABI's
+// padding (score NaN, index INT64_MAX), and a query that carries fewer than kp candidates is final (see below).
+template <typename T, int SPEC, bool MASK>
 __global__ __launch_bounds__(SEL_THREADS, 4) void k_final(
     const unsigned char* __restrict__ bank, int ks, const unsigned char* __restrict__ qpacked, int tnq, int kp, int k,
     IscPerm pm, int64_t index_base, const float* __restrict__ norm_bound, const int32_t* __restrict__ qcount,
@@ -1477,7 +1527,13 @@ __global__ __launch_bounds__(SEL_THREADS, 4) void k_final(
     // 0 against every row, a query with a non-finite norm NaN (any dot is +-inf or NaN, divided by inf or NaN): the order is
     // by row index alone, i.e. the first k rows.  Only when the bank itself is finite (its norm bound is).
     if ((qnorm == 0.0 || !(qnorm <= 1.7e308)) && bmax <= 1.7e308) {
-        if (tid < k) {
+        if constexpr (MASK) {
+            // the first k ALLOWED rows: k_exact's sweep finds them (every score is 0, or NaN, so the row index decides)
+            if (tid == 0) {
+                rl.x_list[atomicAdd(rl.x_count, 1)] = q;
+                atomicAdd(&status[3], 1);
+            }
+        } else if (tid < k) {
             out_s[(size_t)q * k + tid] = qnorm == 0.0 ? 0.f : __uint_as_float(0x7fc00000u);
             out_i[(size_t)q * k + tid] = (int64_t)tid + index_base;
         }
@@ -1517,13 +1573,25 @@ __global__ __launch_bounds__(SEL_THREADS, 4) void k_final(
             if (ratio == ratio) atomicMax(reinterpret_cast<unsigned*>(&status[2]), __float_as_uint(ratio));
         }
     }
+    if (MASK && tid >= nc && tid < k) {  // fewer allowed rows than k (a redo below rewrites the whole row)
+        out_s[(size_t)q * k + tid] = __uint_as_float(0x7fc00000u);
+        out_i[(size_t)q * k + tid] = INT64_MAX;
+    }
     redo = __syncthreads_or(redo ? 1 : 0) != 0;
     if (tid == 0) {
         slot_sh = -1;
         if (!filter_trusted) redo = true;
         if (!redo && (int64_t)nc < pm.n) {  // with every row of the bank carried the answer is exact as it stands
             if (nc < kp) {
-                redo = true;  // fewer candidates than asked for although the bank has more rows (NaN scores)
+                // fewer candidates than asked for although the bank has more rows (NaN scores)
+                if constexpr (!MASK) redo = true;
+                // MASK: the carried list is every allowed row.  Nothing overflowed (no flag) and the filter is trusted,
+                // so every filter score is finite: the carried list never held kp entries, hence every k_select left
+                // tau = -inf (it sets tau only from the kp-th entry), and every filter level kept each allowed row,
+                // because "A > -inf" holds for every finite A.  The sample level kept each one too: a workgroup whose
+                // bound L is finite emits at least kp rows >= L (L is the kp-th of its slot maxima, and disallowed rows
+                // are -inf, so they are not among them), which would have filled the list; with L = -inf it emits every
+                // allowed row.  The nc rows written above are the whole answer, and the padding fills the rest.
             } else {
                 const float t = isc_key_score(sh.topk[kp - 1]);  // every dropped row's filter score is <= t
                 const float bound = (float)(((double)t + eps) / denom);
@@ -1676,13 +1744,13 @@ struct FilterIO {
     const int32_t* active;  // nullptr, or the device-side number of listed slots (redo): tiles past it exit at once
 };
 
-template <typename T, int TNQ>
+template <typename T, int TNQ, typename... RowMask>
 void launch_filter(const Level& l, const Plan& p, const Workspace& w, const FilterIO& io, const unsigned char* bank,
-                   int ksteps, int32_t* status, hipStream_t stream) {
-#define ISC_LAUNCH_FILTER(DBG_, SAMPLE_)                                                                             \
-    hipLaunchKernelGGL((k_dots_filter<T, TNQ, DBG_, SAMPLE_>), dim3(l.nchunks, p.qtiles), dim3(NTHREADS), 0, stream, \
-                       bank, l.r0, l.r1, l.tiles_per_chunk, l.ntiles, io.qpacked, ksteps, io.tau, p.qpad, w.seg_ent,  \
-                       io.qcount, w.qlist, p.kp, nslots_arg, io.qflag, status, io.active)
+                   int ksteps, int32_t* status, hipStream_t stream, RowMask... rm) {
+#define ISC_LAUNCH_FILTER(DBG_, SAMPLE_)                                                                              \
+    hipLaunchKernelGGL((k_dots_filter<T, TNQ, DBG_, SAMPLE_, RowMask...>), dim3(l.nchunks, p.qtiles), dim3(NTHREADS), \
+                       0, stream, bank, l.r0, l.r1, l.tiles_per_chunk, l.ntiles, io.qpacked, ksteps, io.tau, p.qpad,   \
+                       w.seg_ent, io.qcount, w.qlist, p.kp, nslots_arg, io.qflag, status, io.active, rm...)
     int nslots_arg = p.nslots;
     if constexpr (TNQ == 128) {
         // 64 < Q <= 128: always ONE query tile, so the bank stream is non-temporal (13) in the sample level, the filter
@@ -1699,9 +1767,9 @@ void launch_filter(const Level& l, const Plan& p, const Workspace& w, const Filt
         }();
         Plan pa = p;
         pa.nslots |= abl << 16;
-        hipLaunchKernelGGL((k_dots_filter<T, TNQ, 12, true>), dim3(l.nchunks, p.qtiles), dim3(NTHREADS), 0, stream, bank,
-                           l.r0, l.r1, l.tiles_per_chunk, l.ntiles, io.qpacked, ksteps, io.tau, p.qpad, w.seg_ent, io.qcount,
-                           w.qlist, p.kp, pa.nslots, io.qflag, status, io.active);
+        hipLaunchKernelGGL((k_dots_filter<T, TNQ, 12, true, RowMask...>), dim3(l.nchunks, p.qtiles), dim3(NTHREADS), 0,
+                           stream, bank, l.r0, l.r1, l.tiles_per_chunk, l.ntiles, io.qpacked, ksteps, io.tau, p.qpad,
+                           w.seg_ent, io.qcount, w.qlist, p.kp, pa.nslots, io.qflag, status, io.active, rm...);
 #else
         if constexpr (TNQ == 64) {
             if (p.qtiles == 1) ISC_LAUNCH_FILTER(13, true);  // one query tile: non-temporal bank stream
@@ -1783,9 +1851,12 @@ void for_each_segment(const Level& l, const Plan& p, F&& launch) {
     }
 }
 
-template <typename T, typename TQ>
+// RowMask: empty, or the row filter of isc_cosine_topk_masked (const uint32_t*), handed to every filter launch and k_exact
+template <typename T, typename TQ, typename... RowMask>
 int run(const void* bank, int64_t n, int d, const void* queries, int q_total, int64_t ldq, int k, int64_t index_base,
-        const float* norm_bound, float* out_s, int64_t* out_i, int32_t* status, void* ws_base, hipStream_t stream) {
+        const float* norm_bound, float* out_s, int64_t* out_i, int32_t* status, void* ws_base, hipStream_t stream,
+        RowMask... rm) {
+    constexpr bool MASK = sizeof...(RowMask) > 0;
     const Plan p = make_plan(n, q_total, k);
 #ifdef ISC_ABLATION
     static const bool thr_inf_set = [] {
@@ -1818,9 +1889,9 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q_total, in
             // 1.3 x with 127 / 483).
             for_each_segment(l, p, [&](const Level& ls) {
                 isc_timing_begin(ISC_KERNEL_DOTS_FILTER, stream);
-                if (p.tnq == 256) launch_filter<T, 256>(ls, p, w, io, bank_bytes, ksteps, status, stream);
-                else if (p.tnq == 128) launch_filter<T, 128>(ls, p, w, io, bank_bytes, ksteps, status, stream);
-                else launch_filter<T, 64>(ls, p, w, io, bank_bytes, ksteps, status, stream);
+                if (p.tnq == 256) launch_filter<T, 256>(ls, p, w, io, bank_bytes, ksteps, status, stream, rm...);
+                else if (p.tnq == 128) launch_filter<T, 128>(ls, p, w, io, bank_bytes, ksteps, status, stream, rm...);
+                else launch_filter<T, 64>(ls, p, w, io, bank_bytes, ksteps, status, stream, rm...);
                 isc_timing_end(ISC_KERNEL_DOTS_FILTER, stream);
             });
             if (li + 1 < p.nlevels) {
@@ -1834,11 +1905,11 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q_total, in
         }
         const RedoLists rl{w.r_count, w.r_list, w.tau2, w.qpacked2, w.exact.redo_count, w.exact.redo_list};
         if (spec_all)
-            hipLaunchKernelGGL((k_final<T, SEL_PER>), dim3(q), dim3(SEL_THREADS), 0, stream, bank_bytes, ksteps, w.qpacked,
+            hipLaunchKernelGGL((k_final<T, SEL_PER, MASK>), dim3(q), dim3(SEL_THREADS), 0, stream, bank_bytes, ksteps, w.qpacked,
                                p.tnq, p.kp, k, pm, index_base, norm_bound, w.qcount, w.qlist, w.carry_s, w.carry_r,
                                w.carry_n, w.qflag, os, oi, rl, status);
         else
-            hipLaunchKernelGGL((k_final<T, SEL_SPEC_MANY>), dim3(q), dim3(SEL_THREADS), 0, stream, bank_bytes, ksteps,
+            hipLaunchKernelGGL((k_final<T, SEL_SPEC_MANY, MASK>), dim3(q), dim3(SEL_THREADS), 0, stream, bank_bytes, ksteps,
                                w.qpacked, p.tnq, p.kp, k, pm, index_base, norm_bound, w.qcount, w.qlist, w.carry_s,
                                w.carry_r, w.carry_n, w.qflag, os, oi, rl, status);
         // ---- matrix-core redo of the listed queries (normally none: every launch below exits at once, ~1.5 us each):
@@ -1856,9 +1927,9 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q_total, in
             all.tiles_per_chunk = isc_ceil_div(all.ntiles, want);
             all.nchunks = isc_ceil_div(all.ntiles, all.tiles_per_chunk);
             for_each_segment(all, p, [&](const Level& ls) {
-                if (p.tnq == 256) launch_filter<T, 256>(ls, p, w, rio, bank_bytes, ksteps, status, stream);
-                else if (p.tnq == 128) launch_filter<T, 128>(ls, p, w, rio, bank_bytes, ksteps, status, stream);
-                else launch_filter<T, 64>(ls, p, w, rio, bank_bytes, ksteps, status, stream);
+                if (p.tnq == 256) launch_filter<T, 256>(ls, p, w, rio, bank_bytes, ksteps, status, stream, rm...);
+                else if (p.tnq == 128) launch_filter<T, 128>(ls, p, w, rio, bank_bytes, ksteps, status, stream, rm...);
+                else launch_filter<T, 64>(ls, p, w, rio, bank_bytes, ksteps, status, stream, rm...);
             });
             hipLaunchKernelGGL(k_final2<T>, dim3(q), dim3(SEL_THREADS), 0, stream, bank_bytes, ksteps, w.qpacked2, p.tnq, k,
                                pm, index_base, w.r_count, w.r_list, w.qcount2, w.qflag2, w.qlist, os, oi,
@@ -1866,7 +1937,7 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q_total, in
         }
         const int st = isc_exact_launch(sizeof(T) == 2 ? ISC_F16 : ISC_F32, bank, n, d, qptr,
                                         sizeof(TQ) == 2 ? ISC_F16 : ISC_F32, ldq, k, index_base, w.exact, os, oi, status,
-                                        stream);
+                                        isc_row_mask_ptr(rm...), stream);
         if (st != ISC_OK) return st;
     }
     return isc_launch_status();
@@ -1892,10 +1963,11 @@ extern "C" int isc_cosine_topk_workspace_bytes(int dtype, int64_t N, int D, int 
     return ISC_OK;
 }
 
-extern "C" int isc_cosine_topk(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
-                               int64_t ldq, int k, int64_t index_base, const float* norm_bound, float* out_scores,
-                               int64_t* out_indices, int32_t* status, void* workspace, size_t workspace_bytes,
-                               void* stream) {
+namespace {
+
+int topk(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q, int64_t ldq, int k,
+         int64_t index_base, const float* norm_bound, float* out_scores, int64_t* out_indices, int32_t* status,
+         void* workspace, size_t workspace_bytes, const uint32_t* row_mask, void* stream) {
     ISC_REQUIRE(bank && queries && out_scores && out_indices && status);
     ISC_REQUIRE(q_dtype == ISC_F16 || q_dtype == ISC_F32);
     const int st = check_args(dtype, N, D, Q, k);
@@ -1905,9 +1977,11 @@ extern "C" int isc_cosine_topk(const void* bank, int dtype, int64_t N, int D, co
     size_t need = 0;
     isc_cosine_topk_workspace_bytes(dtype, N, D, Q, k, &need);
     if (!workspace || workspace_bytes < need) return ISC_ERR_WORKSPACE;
-#define ISC_RUN(T_, TQ_)                                                                                          \
-    return run<T_, TQ_>(bank, N, D, queries, Q, ldq, k, index_base, norm_bound, out_scores, out_indices, status, \
-                        workspace, isc_stream(stream))
+#define ISC_RUN(T_, TQ_)                                                                                             \
+    return row_mask ? run<T_, TQ_>(bank, N, D, queries, Q, ldq, k, index_base, norm_bound, out_scores, out_indices,    \
+                                   status, workspace, isc_stream(stream), row_mask)                                    \
+                    : run<T_, TQ_>(bank, N, D, queries, Q, ldq, k, index_base, norm_bound, out_scores, out_indices,    \
+                                   status, workspace, isc_stream(stream))
     if (dtype == ISC_F16) {
         if (q_dtype == ISC_F16) ISC_RUN(_Float16, _Float16);
         ISC_RUN(_Float16, float);
@@ -1915,4 +1989,23 @@ extern "C" int isc_cosine_topk(const void* bank, int dtype, int64_t N, int D, co
     if (q_dtype == ISC_F16) ISC_RUN(float, _Float16);
     ISC_RUN(float, float);
 #undef ISC_RUN
+}
+
+}  // namespace
+
+extern "C" int isc_cosine_topk(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
+                               int64_t ldq, int k, int64_t index_base, const float* norm_bound, float* out_scores,
+                               int64_t* out_indices, int32_t* status, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    return topk(bank, dtype, N, D, queries, q_dtype, Q, ldq, k, index_base, norm_bound, out_scores, out_indices, status,
+                workspace, workspace_bytes, nullptr, stream);
+}
+
+extern "C" int isc_cosine_topk_masked(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,
+                                      int Q, int64_t ldq, int k, int64_t index_base, const float* norm_bound,
+                                      float* out_scores, int64_t* out_indices, int32_t* status, void* workspace,
+                                      size_t workspace_bytes, const uint32_t* row_mask, void* stream) {
+    ISC_REQUIRE(row_mask);
+    return topk(bank, dtype, N, D, queries, q_dtype, Q, ldq, k, index_base, norm_bound, out_scores, out_indices, status,
+                workspace, workspace_bytes, row_mask, stream);
 }

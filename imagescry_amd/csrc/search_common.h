@@ -69,6 +69,25 @@ __device__ __forceinline__ unsigned long long isc_wave_max_key(unsigned long lon
     return ((unsigned long long)hi << 32) | lo;
 }
 
+// ---- row filter of a masked search (isc_row_mask_pack) ------------------------------------------------------------
+// Bit p of word p / 32 allows packed position p; a tile's 256 bits are the 8 words from 8 * tile, padding bits 0.  The masked
+// kernels take the bitmap as a trailing parameter PACK, empty in their unmasked instantiations: those keep their argument
+// list, and with it their code (kernels that read the grid size load it from just past the explicit arguments).
+template <typename... RowMask>
+__host__ __device__ __forceinline__ const uint32_t* isc_row_mask_ptr(RowMask... row_mask) {
+    if constexpr (sizeof...(RowMask) == 0) return nullptr;
+    else return (row_mask, ...);
+}
+template <typename... RowMask>
+__device__ __forceinline__ bool isc_row_allowed(int64_t p, RowMask... row_mask) {
+    if constexpr (sizeof...(RowMask) == 0) {
+        return true;
+    } else {
+        const uint32_t* m = isc_row_mask_ptr(row_mask...);
+        return (m[p >> 5] >> (p & 31)) & 1u;
+    }
+}
+
 // ---- float64 arithmetic shared by the exact re-scores of cosine_topk.hip and search_range.hip ---------------------
 // 16 bytes of a packed row as float64 values
 template <typename T>
@@ -131,6 +150,8 @@ IscExactWs isc_exact_ws_carve(void* base, int64_t n, int q, int k);
 // enqueue k_exact: searches queries redo_list[0 .. *redo_count) and writes rows redo_list[i] of out_s / out_i
 // (leading dimension k).  Queries of `q_dtype` at `queries` with leading dimension ldq (elements of q_dtype); every
 // element is rounded to the bank's `dtype` first, as isc_cosine_topk does when it packs them.
+// row_mask: NULL, or a packed row filter -- disallowed rows are skipped, and a query with fewer than k allowed rows gets
+// the ABI's padding (score NaN, index INT64_MAX) in its last positions
 int isc_exact_launch(int dtype, const void* bank, int64_t n, int d, const void* queries, int q_dtype, int64_t ldq, int k,
                      int64_t index_base, const IscExactWs& ws, float* out_s, int64_t* out_i, int32_t* status,
-                     hipStream_t stream);
+                     const uint32_t* row_mask, hipStream_t stream);

@@ -63,7 +63,9 @@ __device__ __forceinline__ double group8_sum(double v) {  // over the 8 lanes th
 // sorted list of its best k keys (exact float32 score, ORIGINAL row) per query; per chunk they are merged into one sorted
 // list per query and published; the workgroup that publishes last merges the chunks' lists (k-way merge of sorted
 // lists by one wave per query) and writes the result rows.
-template <typename T, int GQ>
+// RowMask: empty, or the row filter of a masked search (isc_row_allowed): disallowed rows are never candidates, and a query
+// with fewer than k allowed rows ends in the ABI's padding (score NaN, index INT64_MAX) instead of empty keys.
+template <typename T, int GQ, typename... RowMask>
 __global__ __launch_bounds__(EX_THREADS) void k_exact(const unsigned char* __restrict__ bank, int ks, IscPerm pm,
                                                       int ntiles, int tiles_per_chunk, const void* __restrict__ queries,
                                                       int q_f32, int64_t ldq, int d, int k, int64_t index_base,
@@ -71,7 +73,8 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact(const unsigned char* __res
                                                       const int32_t* __restrict__ redo_list,
                                                       unsigned long long* __restrict__ part, int32_t* __restrict__ done,
                                                       float* __restrict__ out_s, int64_t* __restrict__ out_i,
-                                                      int32_t* __restrict__ status) {
+                                                      int32_t* __restrict__ status, RowMask... row_mask) {
+    constexpr bool MASK = sizeof...(RowMask) > 0;
     const int nf = *redo_count;
     if (nf <= 0) return;  // the normal case
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
@@ -139,7 +142,8 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact(const unsigned char* __res
                     const float sc = (float)(group8_sum(acc[g]) / denom[g]);
                     unsigned long long* wl = lists + ((size_t)g * EX_WAVES + wave) * k;
                     const unsigned long long worst = wl[k - 1];  // 0 while the list is not full
-                    const bool cand = ch == 0 && p < pm.n && isc_score_bits(sc) >= (unsigned)(worst >> 32);
+                    bool cand = ch == 0 && p < pm.n && isc_score_bits(sc) >= (unsigned)(worst >> 32);
+                    if constexpr (MASK) cand = cand && isc_row_allowed(p, row_mask...);
                     unsigned long long mask = __ballot(cand);
                     if (mask == 0ull) continue;
                     const unsigned long long key = cand ? isc_make_key(sc, (int)isc_perm_orig(pm, p)) : 0ull;
@@ -217,8 +221,13 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact(const unsigned char* __res
             for (int j = 1; j < 4; ++j) best = cur[j] > best ? cur[j] : best;
             const unsigned long long win = isc_wave_max_key(best);
             if (lane == 0) {
-                out_s[(size_t)qi * k + r] = isc_key_score(win);
-                out_i[(size_t)qi * k + r] = (int64_t)isc_key_row(win) + index_base;
+                if (MASK && win == 0ull) {  // fewer than k allowed rows
+                    out_s[(size_t)qi * k + r] = __uint_as_float(0x7fc00000u);
+                    out_i[(size_t)qi * k + r] = INT64_MAX;
+                } else {
+                    out_s[(size_t)qi * k + r] = isc_key_score(win);
+                    out_i[(size_t)qi * k + r] = (int64_t)isc_key_row(win) + index_base;
+                }
             }
             if (win != 0ull) {  // keys of distinct rows are distinct: exactly one head matches
 #pragma unroll
@@ -297,9 +306,10 @@ int ex_check(int dtype, int64_t n, int d, int q, int k) {
     return ISC_OK;
 }
 
-template <typename T, int GQ>
+template <typename T, int GQ, typename... RowMask>
 int launch_exact(const void* bank, int64_t n, int d, const void* queries, int q_f32, int64_t ldq, int k, int64_t index_base,
-                  const IscExactWs& ws, float* out_s, int64_t* out_i, int32_t* status, hipStream_t stream) {
+                  const IscExactWs& ws, float* out_s, int64_t* out_i, int32_t* status, hipStream_t stream,
+                  RowMask... row_mask) {
     const int ks = isc_ksteps(d, (int)sizeof(T));
     const int dp = ks * (ISC_KSTEP_BYTES / (int)sizeof(T));
     const size_t lds = (size_t)GQ * dp * 8 + (size_t)GQ * EX_WAVES * k * 8;
@@ -311,27 +321,43 @@ int launch_exact(const void* bank, int64_t n, int d, const void* queries, int q_
     if (hipGetDevice(&dev) != hipSuccess) return ISC_ERR_NO_DEVICE;
     const bool tracked = dev >= 0 && dev < 64;
     if (!tracked || !((__atomic_load_n(&attr_done, __ATOMIC_RELAXED) >> dev) & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_exact<T, GQ>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_exact<T, GQ, RowMask...>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
             (void)hipGetLastError();
             return ISC_ERR_UNSUPPORTED;
         }
         if (tracked) __atomic_fetch_or(&attr_done, 1ull << dev, __ATOMIC_RELAXED);
     }
-    hipLaunchKernelGGL((k_exact<T, GQ>), dim3(ws.chunks), dim3(EX_THREADS), lds, stream,
+    hipLaunchKernelGGL((k_exact<T, GQ, RowMask...>), dim3(ws.chunks), dim3(EX_THREADS), lds, stream,
                        static_cast<const unsigned char*>(bank), ks, isc_make_perm(n), ntiles, ws.tiles_per_chunk,
                        queries, q_f32, ldq, d, k, index_base, ws.redo_count, ws.redo_list, ws.part,
-                       ws.done, out_s, out_i, status);
+                       ws.done, out_s, out_i, status, row_mask...);
     return ISC_OK;
 }
 
-template <typename T>
+template <typename T, typename... RowMask>
 int launch_exact_t(const void* bank, int64_t n, int d, const void* queries, int q_f32, int64_t ldq, int k, int64_t index_base,
-                    const IscExactWs& ws, float* out_s, int64_t* out_i, int32_t* status, hipStream_t stream) {
+                    const IscExactWs& ws, float* out_s, int64_t* out_i, int32_t* status, hipStream_t stream,
+                    RowMask... rm) {
     const int dp = isc_ksteps(d, (int)sizeof(T)) * (ISC_KSTEP_BYTES / (int)sizeof(T));
-    if (dp <= 3072) return launch_exact<T, 4>(bank, n, d, queries, q_f32, ldq, k, index_base, ws, out_s, out_i, status, stream);
-    if (dp <= 6144) return launch_exact<T, 2>(bank, n, d, queries, q_f32, ldq, k, index_base, ws, out_s, out_i, status, stream);
-    return launch_exact<T, 1>(bank, n, d, queries, q_f32, ldq, k, index_base, ws, out_s, out_i, status, stream);
+    if (dp <= 3072)
+        return launch_exact<T, 4>(bank, n, d, queries, q_f32, ldq, k, index_base, ws, out_s, out_i, status, stream, rm...);
+    if (dp <= 6144)
+        return launch_exact<T, 2>(bank, n, d, queries, q_f32, ldq, k, index_base, ws, out_s, out_i, status, stream, rm...);
+    return launch_exact<T, 1>(bank, n, d, queries, q_f32, ldq, k, index_base, ws, out_s, out_i, status, stream, rm...);
+}
+
+template <typename... RowMask>
+int exact_launch(int dtype, const void* bank, int64_t n, int d, const void* queries, int q_dtype, int64_t ldq, int k,
+                 int64_t index_base, const IscExactWs& ws, float* out_s, int64_t* out_i, int32_t* status,
+                 hipStream_t stream, RowMask... rm) {
+    const int qf = q_dtype == ISC_F32 ? 1 : 0;
+    const int st = dtype == ISC_F16
+                       ? launch_exact_t<_Float16>(bank, n, d, queries, qf, ldq, k, index_base, ws, out_s, out_i, status,
+                                                  stream, rm...)
+                       : launch_exact_t<float>(bank, n, d, queries, qf, ldq, k, index_base, ws, out_s, out_i, status,
+                                               stream, rm...);
+    return st != ISC_OK ? st : isc_launch_status();
 }
 
 }  // namespace
@@ -356,12 +382,11 @@ IscExactWs isc_exact_ws_carve(void* base, int64_t n, int q, int k) {
 
 int isc_exact_launch(int dtype, const void* bank, int64_t n, int d, const void* queries, int q_dtype, int64_t ldq, int k,
                      int64_t index_base, const IscExactWs& ws, float* out_s, int64_t* out_i, int32_t* status,
-                     hipStream_t stream) {
-    const int qf = q_dtype == ISC_F32 ? 1 : 0;
-    const int st = dtype == ISC_F16
-                       ? launch_exact_t<_Float16>(bank, n, d, queries, qf, ldq, k, index_base, ws, out_s, out_i, status, stream)
-                       : launch_exact_t<float>(bank, n, d, queries, qf, ldq, k, index_base, ws, out_s, out_i, status, stream);
-    return st != ISC_OK ? st : isc_launch_status();
+                     const uint32_t* row_mask, hipStream_t stream) {
+    if (row_mask)
+        return exact_launch(dtype, bank, n, d, queries, q_dtype, ldq, k, index_base, ws, out_s, out_i, status, stream,
+                            row_mask);
+    return exact_launch(dtype, bank, n, d, queries, q_dtype, ldq, k, index_base, ws, out_s, out_i, status, stream);
 }
 
 extern "C" int isc_topk_merge(const float* scores, const int64_t* indices, int G, int Q, int kin, int kout,
@@ -388,9 +413,11 @@ extern "C" int isc_cosine_topk_exhaustive_workspace_bytes(int dtype, int64_t N, 
     return ISC_OK;
 }
 
-extern "C" int isc_cosine_topk_exhaustive(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,
-                                          int Q, int64_t ldq, int k, int64_t index_base, float* out_scores,
-                                          int64_t* out_indices, void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+
+int exhaustive(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q, int64_t ldq, int k,
+               int64_t index_base, float* out_scores, int64_t* out_indices, void* workspace, size_t workspace_bytes,
+               const uint32_t* row_mask, void* stream) {
     ISC_REQUIRE(bank && queries && out_scores && out_indices);
     ISC_REQUIRE(q_dtype == ISC_F16 || q_dtype == ISC_F32);
     const int st = ex_check(dtype, N, D, Q, k);
@@ -408,8 +435,26 @@ extern "C" int isc_cosine_topk_exhaustive(const void* bank, int dtype, int64_t N
                            q);
         const int st2 = isc_exact_launch(dtype, bank, N, D, static_cast<const char*>(queries) + (size_t)q0 * ldq * esz,
                                          q_dtype, ldq, k, index_base, ws, out_scores + (size_t)q0 * k,
-                                         out_indices + (size_t)q0 * k, nullptr, s);
+                                         out_indices + (size_t)q0 * k, nullptr, row_mask, s);
         if (st2 != ISC_OK) return st2;
     }
     return isc_launch_status();
+}
+
+}  // namespace
+
+extern "C" int isc_cosine_topk_exhaustive(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,
+                                          int Q, int64_t ldq, int k, int64_t index_base, float* out_scores,
+                                          int64_t* out_indices, void* workspace, size_t workspace_bytes, void* stream) {
+    return exhaustive(bank, dtype, N, D, queries, q_dtype, Q, ldq, k, index_base, out_scores, out_indices, workspace,
+                      workspace_bytes, nullptr, stream);
+}
+
+extern "C" int isc_cosine_topk_exhaustive_masked(const void* bank, int dtype, int64_t N, int D, const void* queries,
+                                                 int q_dtype, int Q, int64_t ldq, int k, int64_t index_base,
+                                                 float* out_scores, int64_t* out_indices, void* workspace,
+                                                 size_t workspace_bytes, const uint32_t* row_mask, void* stream) {
+    ISC_REQUIRE(row_mask);
+    return exhaustive(bank, dtype, N, D, queries, q_dtype, Q, ldq, k, index_base, out_scores, out_indices, workspace,
+                      workspace_bytes, row_mask, stream);
 }

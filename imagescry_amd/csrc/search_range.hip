@@ -27,6 +27,10 @@
 // infinite bound) take the float64 scan instead.  A zero query scores 0 against every row of a finite bank and a query
 // with a NaN / inf element NaN: neither needs a scan.
 //
+// A masked call (isc_cosine_range_masked) hands the row filter to the filter and the scan, which skip the rows it disallows.
+// Its zero queries with t <= 0 take the scan as well: it collects every ALLOWED row (all score 0), and the sort puts them
+// in row order, so their segments need no row-order fill.
+//
 // If the candidates outgrow `capacity` the counter keeps counting, every later stage sees empty segments, and the caller
 // learns the exact size to re-issue with from `needed`.
 #include <math.h>
@@ -210,8 +214,9 @@ __global__ __launch_bounds__(256) void k_range_pack(const TQ* __restrict__ queri
     *reinterpret_cast<uint4*>(packed + (size_t)i * 16) = *reinterpret_cast<const uint4*>(v);
 }
 
-// One wave per query slot of the pass: norm, mode, threshold (see the file header).
-template <typename T>
+// One wave per query slot of the pass: norm, mode, threshold (see the file header).  MASK: a masked call, whose all-row
+// queries are scanned (see the file header).
+template <typename T, bool MASK>
 __global__ __launch_bounds__(256) void k_range_qinfo(const unsigned char* __restrict__ qpacked, int ks, int qb, int qpad,
                                                      int q0, int64_t n, const float* __restrict__ min_score,
                                                      const float* __restrict__ norm_bound, float* __restrict__ tau,
@@ -240,7 +245,8 @@ __global__ __launch_bounds__(256) void k_range_qinfo(const unsigned char* __rest
     if (t != t) {
         m = MODE_NONE;  // no score is >= NaN
     } else if ((qnorm == 0.0 || !(qnorm <= 1.7e308)) && bmax <= 1.7e308) {
-        m = qnorm == 0.0 && 0.f >= t ? MODE_ALL : MODE_NONE;  // every score is 0 (zero query) or NaN (non-finite query)
+        // every score is 0 (zero query) or NaN (non-finite query)
+        m = qnorm == 0.0 && 0.f >= t ? (MASK ? MODE_SCAN : MODE_ALL) : MODE_NONE;
     } else if (!(qnorm >= 1e-30 && qnorm * bmax <= 1e37)) {
         m = MODE_SCAN;  // outside the range where eps bounds the filter (a NaN / inf bound included)
     } else {
@@ -273,14 +279,15 @@ __global__ __launch_bounds__(256) void k_range_qinfo(const unsigned char* __rest
 // One workgroup = one 256-row bank tile x one 64-query tile; wave w owns rows 64 w .. 64 w + 63 of the tile (4 x 4 blocks of
 // 16 x 16 scores).  Fragments come straight from global memory (the bank tile's K step is 32 KiB of contiguous HBM, a
 // wave's share 8 KiB), one K step ahead of the matrix cores; consecutive workgroups are the query tiles of one bank tile,
-// so a bank tile read by several of them is served from L2.  Scores above tau are appended (wave_reserve).
-template <typename T>
+// so a bank tile read by several of them is served from L2.  Scores above tau are appended (wave_reserve); with a row filter
+// (RowMask, search_common.h) only those of allowed rows.
+template <typename T, typename... RowMask>
 __global__ __launch_bounds__(256) void k_range_filter(const unsigned char* __restrict__ bank, int64_t n, int ks, int nqt,
                                                       const unsigned char* __restrict__ qpacked,
                                                       const float* __restrict__ tau, int q0,
                                                       unsigned long long* __restrict__ count, int64_t capacity,
                                                       int32_t* __restrict__ cand_q, int32_t* __restrict__ cand_r,
-                                                      float* __restrict__ cand_a) {
+                                                      float* __restrict__ cand_a, RowMask... row_mask) {
     const int64_t tile = blockIdx.x / nqt;
     const int qt = blockIdx.x % nqt;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -325,6 +332,21 @@ __global__ __launch_bounds__(256) void k_range_filter(const unsigned char* __res
 
     // acc[m][nb][j] = score of bank row 16 m + 4 grp + j (of this wave's 64) with query 16 nb + r16 of the tile
     const int64_t row0 = tile * ISC_TILE_ROWS + wave * 64 + grp * 4;
+    // row filter: disallowed rows score -inf, which no tau lets through ("A > tau" is false even for tau = -inf).  This
+    // wave's 64 rows are two words; row 16 m + 4 grp + j is bit 16 (m & 1) + 4 grp + j of word m / 2.
+    if constexpr (sizeof...(RowMask) > 0) {
+        const uint32_t* mw = isc_row_mask_ptr(row_mask...) + tile * (ISC_TILE_ROWS / 32) + wave * 2;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const uint32_t nib = mw[m >> 1] >> ((m & 1) * 16 + grp * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (!((nib >> j) & 1u)) {
+#pragma unroll
+                    for (int nb = 0; nb < 4; ++nb) acc[m][nb][j] = -INFINITY;
+                }
+        }
+    }
     float tq[4];
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) tq[nb] = tau[qt * RQT + nb * 16 + r16];
@@ -358,7 +380,8 @@ __global__ __launch_bounds__(256) void k_range_filter(const unsigned char* __res
 
 // The float64 scan of the queries the filter cannot serve: one thread per bank row, the whole bank per listed query.  A row
 // is appended when its score is >= prevfloat(t) (one float32 step of margin for the summation order): the re-score decides.
-template <typename T>
+// Rows a row filter disallows (RowMask) are skipped.
+template <typename T, typename... RowMask>
 __global__ __launch_bounds__(256) void k_range_scan(const unsigned char* __restrict__ bank, int64_t n, int ks,
                                                     const unsigned char* __restrict__ qpacked,
                                                     const int32_t* __restrict__ fb_count,
@@ -366,7 +389,7 @@ __global__ __launch_bounds__(256) void k_range_scan(const unsigned char* __restr
                                                     const float* __restrict__ min_score, int q0,
                                                     unsigned long long* __restrict__ count, int64_t capacity,
                                                     int32_t* __restrict__ cand_q, int32_t* __restrict__ cand_r,
-                                                    float* __restrict__ cand_a) {
+                                                    float* __restrict__ cand_a, RowMask... row_mask) {
     const int nfb = *fb_count;
     for (int li = 0; li < nfb; ++li) {
         const int w = fb_list[li];
@@ -377,7 +400,7 @@ __global__ __launch_bounds__(256) void k_range_scan(const unsigned char* __restr
             const int64_t row = base + threadIdx.x;
             double e = 0.0;
             bool keep = false;
-            if (row < n) {
+            if (row < n && isc_row_allowed(row, row_mask...)) {
                 for (int s = 0; s < ks; ++s) {
 #pragma unroll
                     for (int ch = 0; ch < 8; ++ch) {
@@ -539,10 +562,10 @@ int grid_for(int64_t items, int per_block, int cap) {
     return (int)(b < 1 ? 1 : b > cap ? cap : b);
 }
 
-template <typename T, typename TQ>
+template <typename T, typename TQ, typename... RowMask>
 int run(const void* bank, int64_t n, int d, const void* queries, int q, int64_t ldq, const float* min_score,
         int64_t index_base, const float* norm_bound, int64_t capacity, int64_t* offsets, float* scores,
-        int64_t* indices, int64_t* needed, int32_t* status, void* workspace, hipStream_t stream) {
+        int64_t* indices, int64_t* needed, int32_t* status, void* workspace, hipStream_t stream, RowMask... rm) {
     const int ks = isc_ksteps(d, (int)sizeof(T));
     const RangeWs w = carve(ks, q, capacity, workspace);
     const IscPerm pm = isc_make_perm(n);
@@ -559,14 +582,14 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q, int64_t 
         k_range_pack<T, TQ><<<isc_ceil_div(qpad * ks * 8, 256), 256, 0, stream>>>(
             static_cast<const TQ*>(queries) + (int64_t)p0 * ldq, ldq, qb, d, ks, qpad, w.qpacked, w.fb_count,
             w.pass_begin + pass, w.count);
-        k_range_qinfo<T><<<qpad / 4, 256, 0, stream>>>(w.qpacked, ks, qb, qpad, p0, n, min_score, norm_bound, w.tau,
+        k_range_qinfo<T, (sizeof...(RowMask) > 0)><<<qpad / 4, 256, 0, stream>>>(w.qpacked, ks, qb, qpad, p0, n, min_score, norm_bound, w.tau,
                                                        w.denom, w.eps, w.mode, w.qcount, w.fb_count, w.fb_list,
                                                        w.all_count, w.all_list, w.all_rows, status);
-        k_range_filter<T><<<(unsigned)(ntiles * nqt), 256, 0, stream>>>(bk, n, ks, nqt, w.qpacked, w.tau, p0, w.count,
-                                                                         capacity, w.cand_q, w.cand_r, w.cand_a);
-        k_range_scan<T><<<grid_for(n, 256, 4 * cus), 256, 0, stream>>>(bk, n, ks, w.qpacked, w.fb_count, w.fb_list,
-                                                                       w.denom, min_score, p0, w.count, capacity,
-                                                                       w.cand_q, w.cand_r, w.cand_a);
+        k_range_filter<T, RowMask...><<<(unsigned)(ntiles * nqt), 256, 0, stream>>>(
+            bk, n, ks, nqt, w.qpacked, w.tau, p0, w.count, capacity, w.cand_q, w.cand_r, w.cand_a, rm...);
+        k_range_scan<T, RowMask...><<<grid_for(n, 256, 4 * cus), 256, 0, stream>>>(
+            bk, n, ks, w.qpacked, w.fb_count, w.fb_list, w.denom, min_score, p0, w.count, capacity, w.cand_q, w.cand_r,
+            w.cand_a, rm...);
         k_range_rescore<T><<<grid_for(capacity, 4, 8 * cus), 256, 0, stream>>>(
             bk, ks, w.qpacked, p0, w.pass_begin + pass, w.count, capacity, w.cand_q, w.cand_r, w.cand_a, w.denom, w.eps,
             w.mode, min_score, w.qcount, status);
@@ -606,10 +629,12 @@ extern "C" int isc_cosine_range_workspace_bytes(int dtype, int64_t N, int D, int
     return ISC_OK;
 }
 
-extern "C" int isc_cosine_range(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
-                                int64_t ldq, const float* min_score, int64_t index_base, const float* norm_bound,
-                                int64_t capacity, int64_t* offsets, float* scores, int64_t* indices, int64_t* needed,
-                                int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+
+int range(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q, int64_t ldq,
+          const float* min_score, int64_t index_base, const float* norm_bound, int64_t capacity, int64_t* offsets,
+          float* scores, int64_t* indices, int64_t* needed, int32_t* status, void* workspace, size_t workspace_bytes,
+          const uint32_t* row_mask, void* stream) {
     ISC_REQUIRE(bank && queries && min_score && offsets && scores && indices && needed && status);
     ISC_REQUIRE(q_dtype == ISC_F16 || q_dtype == ISC_F32);
     const int st = check_args(dtype, N, D, Q, capacity);
@@ -619,9 +644,11 @@ extern "C" int isc_cosine_range(const void* bank, int dtype, int64_t N, int D, c
     size_t need = 0;
     isc_cosine_range_workspace_bytes(dtype, N, D, Q, capacity, &need);
     if (!workspace || workspace_bytes < need) return ISC_ERR_WORKSPACE;
-#define ISC_RUN(T_, TQ_)                                                                                          \
-    return run<T_, TQ_>(bank, N, D, queries, Q, ldq, min_score, index_base, norm_bound, capacity, offsets, scores, \
-                        indices, needed, status, workspace, isc_stream(stream))
+#define ISC_RUN(T_, TQ_)                                                                                              \
+    return row_mask ? run<T_, TQ_>(bank, N, D, queries, Q, ldq, min_score, index_base, norm_bound, capacity, offsets,   \
+                                   scores, indices, needed, status, workspace, isc_stream(stream), row_mask)            \
+                    : run<T_, TQ_>(bank, N, D, queries, Q, ldq, min_score, index_base, norm_bound, capacity, offsets,   \
+                                   scores, indices, needed, status, workspace, isc_stream(stream))
     if (dtype == ISC_F16) {
         if (q_dtype == ISC_F16) ISC_RUN(_Float16, _Float16);
         ISC_RUN(_Float16, float);
@@ -629,4 +656,24 @@ extern "C" int isc_cosine_range(const void* bank, int dtype, int64_t N, int D, c
     if (q_dtype == ISC_F16) ISC_RUN(float, _Float16);
     ISC_RUN(float, float);
 #undef ISC_RUN
+}
+
+}  // namespace
+
+extern "C" int isc_cosine_range(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
+                                int64_t ldq, const float* min_score, int64_t index_base, const float* norm_bound,
+                                int64_t capacity, int64_t* offsets, float* scores, int64_t* indices, int64_t* needed,
+                                int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    return range(bank, dtype, N, D, queries, q_dtype, Q, ldq, min_score, index_base, norm_bound, capacity, offsets, scores,
+                 indices, needed, status, workspace, workspace_bytes, nullptr, stream);
+}
+
+extern "C" int isc_cosine_range_masked(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,
+                                       int Q, int64_t ldq, const float* min_score, int64_t index_base,
+                                       const float* norm_bound, int64_t capacity, int64_t* offsets, float* scores,
+                                       int64_t* indices, int64_t* needed, int32_t* status, void* workspace,
+                                       size_t workspace_bytes, const uint32_t* row_mask, void* stream) {
+    ISC_REQUIRE(row_mask);
+    return range(bank, dtype, N, D, queries, q_dtype, Q, ldq, min_score, index_base, norm_bound, capacity, offsets, scores,
+                 indices, needed, status, workspace, workspace_bytes, row_mask, stream);
 }

@@ -29,6 +29,7 @@ search i + 1.
 from __future__ import annotations
 
 import math
+import weakref
 from dataclasses import dataclass
 from os import PathLike
 from typing import Sequence
@@ -40,7 +41,7 @@ from torch import Tensor
 from imagescry_amd import _lib
 from imagescry_amd.data import EmbeddingBatch
 
-__all__ = ["EmbeddingBank", "RangeResult", "SearchHandle", "shard_bounds"]
+__all__ = ["EmbeddingBank", "RangeResult", "RowFilter", "SearchHandle", "shard_bounds"]
 
 _PAD_INDEX = torch.iinfo(torch.int64).max
 
@@ -122,6 +123,28 @@ class RangeResult:
         return self.scores[lo:hi], self.indices[lo:hi]
 
 
+def _unpad(scores: Tensor, indices: Tensor) -> tuple[Tensor, Tensor]:
+    """The public form of a masked top-k: the C ABI's padding (score NaN, index INT64_MAX) becomes (-inf, -1)."""
+    pad = indices == _PAD_INDEX
+    return scores.masked_fill(pad, -math.inf), indices.masked_fill(pad, -1)
+
+
+class RowFilter:
+    """A set of allowed rows of ONE bank, made by `EmbeddingBank.row_filter`: the bitmap of this rank's rows in the bank's
+    packed row order (`isc_row_mask_pack`) and the number of rows it allows (int64 [1], device).  Searches given it as
+    `mask=` answer as if the bank held the allowed rows only, with their indices in the whole bank."""
+
+    __slots__ = ("packed", "allowed_count", "_bank")
+
+    def __init__(self, bank: "EmbeddingBank", packed: Tensor, allowed_count: Tensor) -> None:
+        self.packed = packed  # int32 [isc_row_mask_words(N_local)] (uint32 bit patterns); empty for a shard with no row
+        self.allowed_count = allowed_count
+        self._bank = weakref.ref(bank)
+
+    def belongs_to(self, bank: "EmbeddingBank") -> bool:
+        return self._bank() is bank
+
+
 class _ExchangeSlot:
     """One of the two exchange buffers of a sharded bank and the event behind the last exchange that read it."""
 
@@ -173,6 +196,7 @@ class EmbeddingBank:
         elif process_group is None and index_base != 0 and not presharded:
             raise ValueError("index_base is only meaningful for a presharded bank")
         self.index_base = int(index_base)
+        self.presharded = bool(presharded)
         self.dtype = dtype
         self.dim = int(embeddings.shape[1])
         self.num_local_rows = int(embeddings.shape[0])
@@ -281,6 +305,88 @@ class EmbeddingBank:
     def __len__(self) -> int:
         return self.num_local_rows
 
+    # ------------------------------------------------------------------ row filters
+    def _global_rows(self) -> int | None:
+        """Rows of the whole (possibly sharded) bank; on a sharded bank the first call is a collective of every rank.
+        None for a presharded bank without a process group: its shard ends at row index_base + len(self) of a bank whose
+        size only the caller knows."""
+        if self.process_group is None:
+            return None if self.presharded else self.num_local_rows
+        if not hasattr(self, "_n_total"):
+            self._n_total = self._total_rows()
+        return self._n_total
+
+    def row_filter(self, allow: Tensor | None = None, *, rows: "Tensor | Sequence[int] | None" = None,
+                   image_ids: "Tensor | Sequence[int] | None" = None, exclude: bool = False) -> RowFilter:
+        """A `RowFilter` of this bank for the `mask=` of its searches, from exactly one of
+        - `allow`: bool `[N]` over the GLOBAL rows of the bank (True = the row may be returned),
+        - `rows`: global row indices,
+        - `image_ids`: the images whose cells may be returned (needs `row_origin`, i.e. a bank from `from_database`);
+        `exclude=True` allows the complement instead.  A sharded bank keeps the bits of its own rows
+        `[index_base, index_base + len(self))`; there every rank makes the filter (the first call learns the global row
+        count with a collective).  A presharded bank without a process group takes an `allow` of any length that covers
+        its rows.  The filter is packed on the device in one launch and belongs to this bank."""
+        if sum(x is not None for x in (allow, rows, image_ids)) != 1:
+            raise ValueError("give exactly one of allow, rows or image_ids")
+        n_total = self._global_rows()
+        hi = self.index_base + self.num_local_rows
+        dev = self.device
+        if allow is not None:
+            ok = isinstance(allow, Tensor) and allow.dtype == torch.bool and allow.ndim == 1
+            if not ok or (allow.shape[0] != n_total if n_total is not None else allow.shape[0] < hi):
+                raise ValueError(f"allow must be a bool tensor of shape [{n_total if n_total is not None else 'N >= ' + str(hi)}]"
+                                 " (the bank's global rows)")
+            keep = allow.to(dev)
+        elif rows is not None:
+            r = rows if isinstance(rows, Tensor) else torch.as_tensor(list(rows), dtype=torch.int64)
+            if r.dtype.is_floating_point or r.dtype == torch.bool or r.ndim != 1:
+                raise ValueError("rows must be a 1-D sequence of integer row indices")
+            r = r.to(torch.int64)
+            if r.numel() and (int(r.min()) < 0 or (n_total is not None and int(r.max()) >= n_total)):
+                raise ValueError(f"rows must lie in [0, {n_total if n_total is not None else 'N'})")
+            size = n_total if n_total is not None else max(hi, int(r.max()) + 1 if r.numel() else 0)
+            keep = torch.zeros(size, dtype=torch.bool, device=dev)
+            keep[r.to(dev)] = True
+        else:
+            if self.row_origin is None:
+                raise ValueError("image_ids needs row_origin: build the bank with EmbeddingBank.from_database")
+            if self.row_origin.shape[0] != (n_total if n_total is not None else self.row_origin.shape[0]):
+                raise ValueError("row_origin does not describe the bank's rows")
+            ids = image_ids if isinstance(image_ids, Tensor) else torch.as_tensor(list(image_ids), dtype=torch.int64)
+            origin = self.row_origin[:, 0]
+            keep = torch.isin(origin, ids.to(device=origin.device, dtype=origin.dtype)).to(dev)
+        if exclude:
+            keep = ~keep
+        return self._pack_filter(keep[self.index_base : self.index_base + self.num_local_rows])
+
+    def _pack_filter(self, local: Tensor) -> RowFilter:
+        """`isc_row_mask_pack` of this rank's bool `[N_local]` rows."""
+        count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        n = self.num_local_rows
+        if n == 0:
+            return RowFilter(self, torch.empty(0, dtype=torch.int32, device=self.device), count)
+        lib = _lib.load()
+        words = _lib.c_size_t()
+        _lib.check(lib.isc_row_mask_words(n, words), "isc_row_mask_words")
+        packed = torch.empty(words.value, dtype=torch.int32, device=self.device)
+        allow = local.to(torch.uint8).contiguous()
+        with torch.cuda.device(self.device):
+            st = lib.isc_row_mask_pack(allow.data_ptr(), n, packed.data_ptr(), count.data_ptr(),
+                                       _lib.stream_handle(self.device))
+        _lib.check(st, "isc_row_mask_pack")
+        return RowFilter(self, packed, count)
+
+    def _as_filter(self, mask: "RowFilter | Tensor | None") -> RowFilter | None:
+        if mask is None:
+            return None
+        if isinstance(mask, RowFilter):
+            if not mask.belongs_to(self):
+                raise ValueError("this RowFilter belongs to another EmbeddingBank")
+            return mask
+        if isinstance(mask, Tensor):
+            return self.row_filter(mask)
+        raise TypeError(f"mask must be a RowFilter or a bool tensor, got {type(mask).__name__}")
+
     # ------------------------------------------------------------------ search
     def _prepare_queries(self, queries: Tensor) -> Tensor:
         if not isinstance(queries, Tensor) or not queries.dtype.is_floating_point:
@@ -321,12 +427,14 @@ class EmbeddingBank:
 
     def _local_topk(
         self, queries: Tensor, k: int, out: tuple[Tensor, Tensor, Tensor] | None = None, lane: int = -1,
-        stream: "torch.cuda.Stream | None" = None,
+        stream: "torch.cuda.Stream | None" = None, mask: RowFilter | None = None,
     ) -> tuple[Tensor, Tensor]:
         """Top-k of this rank's rows: `(float32 [Q, k], int64 [Q, k])` with GLOBAL row indices, final when the stream
         has run the call.  `out` optionally supplies the (scores, indices, status int32[4]) tensors to write into (the
         exchange buffer of a sharded search); `lane` / `stream`: the workspace set and the stream of an asynchronous search
-        (default: the caller's current stream).  Tensors are allocated on the caller's stream whichever stream computes."""
+        (default: the caller's current stream).  Tensors are allocated on the caller's stream whichever stream computes.
+        `mask`: search the rows of a row filter only (`isc_cosine_topk_masked`); a query with fewer than k allowed rows ends
+        in the C ABI's padding (score NaN, index INT64_MAX), which the public calls map to (-inf, -1) at the very end."""
         nq = queries.shape[0]
         if out is None:
             scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
@@ -341,22 +449,32 @@ class EmbeddingBank:
             # is given to somebody else before the lane's kernels have run
             for t in (scores, indices, status, ws, self._bank, self._norm_bound):
                 t.record_stream(stream)
+            if mask is not None:
+                mask.packed.record_stream(stream)
         lib = _lib.load()
         with torch.cuda.device(self.device):
-            st = lib.isc_cosine_topk(
+            args = (
                 self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.num_local_rows, self.dim, queries.data_ptr(),
                 _lib.dtype_code(queries.dtype), nq, queries.stride(0), k, self.index_base, self._norm_bound.data_ptr(),
                 scores.data_ptr(),
                 indices.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
-                stream.cuda_stream if stream is not None else _lib.stream_handle(self.device),
             )
-            _lib.check(st, "isc_cosine_topk")
+            sh = stream.cuda_stream if stream is not None else _lib.stream_handle(self.device)
+            if mask is None:
+                st = lib.isc_cosine_topk(*args, sh)
+                _lib.check(st, "isc_cosine_topk")
+            else:
+                st = lib.isc_cosine_topk_masked(*args, mask.packed.data_ptr(), sh)
+                _lib.check(st, "isc_cosine_topk_masked")
         self.last_status = status
         return scores, indices
 
-    def search_exhaustive(self, queries: Tensor, k: int = 10) -> tuple[Tensor, Tensor]:
+    def search_exhaustive(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None
+                          ) -> tuple[Tensor, Tensor]:
         """The same answer from the data-independent float64 kernel (`isc_cosine_topk_exhaustive`): every score of
-        every query evaluated exactly.  Slow; the on-device reference the fast path is tested against."""
+        every query evaluated exactly.  Slow; the on-device reference the fast path is tested against.  `mask`: as in
+        `search`."""
+        rf = self._as_filter(mask)
         q = self._prepare_queries(queries)
         nq = q.shape[0]
         if self.process_group is not None:
@@ -374,13 +492,16 @@ class EmbeddingBank:
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         indices = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
-            st = lib.isc_cosine_topk_exhaustive(
+            args = (
                 self._bank.data_ptr(), code, self.num_local_rows, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
                 q.stride(0), k, self.index_base, scores.data_ptr(), indices.data_ptr(), ews.data_ptr(), ews.numel(),
-                _lib.stream_handle(self.device),
             )
-        _lib.check(st, "isc_cosine_topk_exhaustive")
-        return scores, indices
+            if rf is None:
+                st = lib.isc_cosine_topk_exhaustive(*args, _lib.stream_handle(self.device))
+            else:
+                st = lib.isc_cosine_topk_exhaustive_masked(*args, rf.packed.data_ptr(), _lib.stream_handle(self.device))
+        _lib.check(st, "isc_cosine_topk_exhaustive" + ("" if rf is None else "_masked"))
+        return (scores, indices) if rf is None else _unpad(scores, indices)
 
     def _merge_topk(self, scores: Tensor, indices: Tensor, k: int) -> tuple[Tensor, Tensor]:
         """Merge `[G, Q, kin]` partial results into `[Q, k]` by (score desc, index asc) (`isc_topk_merge`).  The two
@@ -406,7 +527,8 @@ class EmbeddingBank:
         dist.all_gather_object(counts, self.num_local_rows, group=self.process_group)
         return int(sum(counts))
 
-    def search(self, queries: Tensor, k: int = 10, *, check: bool = True) -> tuple[Tensor, Tensor]:
+    def search(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None,
+               check: bool = True) -> tuple[Tensor, Tensor]:
         """Cosine top-k of every query against the whole (possibly sharded) bank.
 
         Returns `(scores float32 [Q, k], indices int64 [Q, k])`, best first, ties by lower row index.  The call
@@ -417,11 +539,17 @@ class EmbeddingBank:
         four such queries: a bank with thousands of exact copies of a row pays this for queries that hit them).  `check` is accepted for compatibility with the
         first version of this API and ignored.  Everything runs on the caller's current stream (a sharded bank's
         exchange on the bank's exchange stream, ordered behind it).
+
+        `mask` restricts the search to a set of rows: a `RowFilter` of this bank (`row_filter`), or a bool tensor of the
+        bank's GLOBAL row count (True = allowed), packed for this call.  The answer is the search of the bank of the
+        allowed rows alone, with indices in the whole bank, bit for bit; `k` is still bounded by the bank size, and a
+        query with fewer than k allowed rows ends in score -inf, index -1 entries.  The whole bank is streamed whatever
+        the filter's density (the masked filter).
         """
         del check
-        return self._search(queries, k, lanes=False).result()
+        return self._search(queries, k, lanes=False, mask=mask).result()
 
-    def search_async(self, queries: Tensor, k: int = 10) -> SearchHandle:
+    def search_async(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None) -> SearchHandle:
         """`search` that returns as soon as everything is ENQUEUED; `handle.result()` orders the caller's current stream
         behind the answer.  The local kernels of a search of up to 128 queries run on one of TWO library-owned streams
         of the device, alternately -- the bank keeps a workspace for each -- ordered behind the caller's stream as it
@@ -435,8 +563,9 @@ class EmbeddingBank:
         Ownership until `handle.result()`: the search reads `queries` on a library-owned stream (float16 / float32
         queries with unit inner stride are NOT copied), and writes `last_status` / `last_gathered_status` there -- so the
         caller must not overwrite the query tensor in place, nor read those status tensors, on its own stream before it
-        has resolved the handle.  `search()` has no such window: everything it does is ordered on the caller's stream."""
-        return self._search(queries, k, lanes=True)
+        has resolved the handle.  `search()` has no such window: everything it does is ordered on the caller's stream.
+        `mask`: as in `search` (a `RowFilter` is read on the library's stream too: keep it until the handle is resolved)."""
+        return self._search(queries, k, lanes=True, mask=mask)
 
     def _lane(self, cur: "torch.cuda.Stream", q: Tensor) -> tuple[int, "torch.cuda.Stream"]:
         """The next of the two search streams, ordered behind everything the caller's stream holds so far."""
@@ -454,7 +583,8 @@ class EmbeddingBank:
     # shard), and two of them sharing the GPU would stretch each other's launches.
     _LANE_MAX_QUERIES = 128
 
-    def _search(self, queries: Tensor, k: int, lanes: bool) -> SearchHandle:
+    def _search(self, queries: Tensor, k: int, lanes: bool, mask: "RowFilter | Tensor | None" = None) -> SearchHandle:
+        rf = self._as_filter(mask)
         if not isinstance(k, int) or isinstance(k, bool):
             raise TypeError(f"k must be an int, got {type(k).__name__}")
         if k < 1:
@@ -470,6 +600,16 @@ class EmbeddingBank:
             if nq == 0:
                 return SearchHandle(torch.empty((0, k), dtype=torch.float32, device=self.device),
                                     torch.empty((0, k), dtype=torch.int64, device=self.device))
+            if rf is not None:  # the padding of a masked search becomes (-inf, -1) on the stream that computed it
+                if not (lanes and self.device.type == "cuda"):
+                    return SearchHandle(*_unpad(*self._local_topk(q, k, mask=rf)))
+                lane, ls = self._lane(torch.cuda.current_stream(self.device), q)
+                out_s, out_i = self._local_topk(q, k, lane=lane, stream=ls, mask=rf)
+                with torch.cuda.stream(ls):
+                    out_s, out_i = _unpad(out_s, out_i)
+                done = torch.cuda.Event()
+                done.record(ls)
+                return SearchHandle(out_s, out_i, done)
             if not (lanes and self.device.type == "cuda"):
                 return SearchHandle(*self._local_topk(q, k))
             lane, ls = self._lane(torch.cuda.current_stream(self.device), q)
@@ -515,21 +655,26 @@ class EmbeddingBank:
         part_i = xbuf[off_i:off_s].view(torch.int64).view(nq, k)
         status = xbuf[off_s:].view(torch.int32)
         if kl < k:  # a shard with fewer rows than k: pad with entries that rank after every real candidate
-            part_s.fill_(-math.inf)
+            # (a masked search pads with the C ABI's (NaN, INT64_MAX), which ranks after NaN-scored rows of other shards too)
+            part_s.fill_(-math.inf if rf is None else math.nan)
             part_i.fill_(_PAD_INDEX)
             status.zero_()
             if kl > 0:
-                s, i = self._local_topk(q, kl)
+                s, i = self._local_topk(q, kl) if rf is None else self._local_topk(q, kl, mask=rf)
                 part_s[:, :kl] = s
                 part_i[:, :kl] = i
-        else:
+        elif rf is None:
             self._local_topk(q, k, out=(part_s, part_i, status), lane=lane, stream=ls)
+        else:
+            self._local_topk(q, k, out=(part_s, part_i, status), lane=lane, stream=ls, mask=rf)
 
         def exchange() -> tuple[Tensor, Tensor, Tensor, Tensor]:
             gathered = self._all_gather_bytes(xbuf)
             all_s = gathered[:, : 4 * nq * k].view(torch.float32).view(self.world_size, nq, k)
             all_i = gathered[:, off_i:off_s].view(torch.int64).view(self.world_size, nq, k)
             out_s, out_i = self._merge_topk(all_s, all_i, k)
+            if rf is not None:
+                out_s, out_i = _unpad(out_s, out_i)
             return out_s, out_i, gathered, gathered[:, off_s:].view(torch.int32)  # [G, 4]: every shard's diagnostics
 
         if not on_gpu:  # CPU tensors (the gloo rehearsal of the host logic): nothing to overlap
@@ -579,7 +724,8 @@ class EmbeddingBank:
             raise ValueError("min_score is NaN")
         return torch.full((nq,), float(min_score), dtype=torch.float32, device=self.device)
 
-    def _range_call(self, q: Tensor, thr: Tensor, capacity: int) -> tuple[int, RangeResult, Tensor]:
+    def _range_call(self, q: Tensor, thr: Tensor, capacity: int, mask: RowFilter | None = None
+                    ) -> tuple[int, RangeResult, Tensor]:
         """One `isc_cosine_range` call: (needed, result -- valid only when needed <= capacity --, status int32[4])."""
         lib = _lib.load()
         nq = q.shape[0]
@@ -597,16 +743,21 @@ class EmbeddingBank:
         needed = torch.empty(1, dtype=torch.int64, device=self.device)
         status = torch.empty(4, dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            st = lib.isc_cosine_range(
+            args = (
                 self._bank.data_ptr(), code, self.num_local_rows, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
                 q.stride(0), thr.data_ptr(), self.index_base, self._norm_bound.data_ptr(), capacity,
                 offsets.data_ptr(), scores.data_ptr(), indices.data_ptr(), needed.data_ptr(), status.data_ptr(),
-                ws.data_ptr(), ws.numel(), _lib.stream_handle(self.device),
+                ws.data_ptr(), ws.numel(),
             )
-        _lib.check(st, "isc_cosine_range")
+            if mask is None:
+                st = lib.isc_cosine_range(*args, _lib.stream_handle(self.device))
+            else:
+                st = lib.isc_cosine_range_masked(*args, mask.packed.data_ptr(), _lib.stream_handle(self.device))
+        _lib.check(st, "isc_cosine_range" + ("" if mask is None else "_masked"))
         return int(needed.item()), RangeResult(offsets, scores, indices), status
 
-    def _local_range(self, queries: Tensor, min_score: Tensor, max_results: int) -> tuple[int, RangeResult | None]:
+    def _local_range(self, queries: Tensor, min_score: Tensor, max_results: int, mask: RowFilter | None = None
+                     ) -> tuple[int, RangeResult | None]:
         """Range search of this rank's rows with GLOBAL row indices: `(total, result)`; `result` is None when `total`
         exceeds `max_results` (then `total` is the exact row count, or, when even counting would need more than twice
         `max_results` entries, the filter's candidate count, an upper bound of it)."""
@@ -618,19 +769,20 @@ class EmbeddingBank:
             return 0, empty
         limit = min(max(max_results, 1), 0x7FFFFFFF)
         cap = min(max(1 << 16, self._RANGE_GUESS_PER_QUERY * nq), limit)
-        needed, res, status = self._range_call(queries, min_score, cap)
+        needed, res, status = self._range_call(queries, min_score, cap, mask)
         if needed > cap:
             if needed > 2 * limit or needed > 0x7FFFFFFF:
                 self.last_range_status = status
                 return needed, None
-            needed, res, status = self._range_call(queries, min_score, needed)
+            needed, res, status = self._range_call(queries, min_score, needed, mask)
         self.last_range_status = status
         total = int(res.offsets[-1].item())
         if total > max_results:
             return total, None
         return total, RangeResult(res.offsets, res.scores[:total], res.indices[:total])
 
-    def search_range(self, queries: Tensor, min_score: "float | Tensor", *, max_results: int = 1 << 26) -> RangeResult:
+    def search_range(self, queries: Tensor, min_score: "float | Tensor", *, max_results: int = 1 << 26,
+                     mask: "RowFilter | Tensor | None" = None) -> RangeResult:
         """Every row whose cosine score against a query is >= `min_score` (a float, or a float32 `[Q]` tensor of
         per-query thresholds): a `RangeResult` whose query q holds its rows ordered by (score descending, row index
         ascending), indices global.  Exact: the scores and the membership are those of the top-k (`search`), so with
@@ -642,13 +794,15 @@ class EmbeddingBank:
         ValueError with the count.  `last_range_status` (int32[4], device) holds diagnostics: [0] filter candidates,
         [1] queries answered by the float64 sweep, [2] float bits of the largest filter error in units of its bound.
         A sharded bank searches its shard on every rank, all-gathers the per-rank totals and then the rows, and every
-        rank merges them into the answer of the unsharded bank."""
+        rank merges them into the answer of the unsharded bank.  `mask`: as in `search` -- the result without the rows the
+        filter disallows, bit for bit."""
+        rf = self._as_filter(mask)
         q = self._prepare_queries(queries)
         nq = q.shape[0]
         thr = self._range_thresholds(min_score, nq)
         if isinstance(max_results, bool) or not isinstance(max_results, int) or max_results < 0:
             raise ValueError(f"max_results must be a non-negative int, got {max_results!r}")
-        total, res = self._local_range(q, thr, max_results)
+        total, res = self._local_range(q, thr, max_results) if rf is None else self._local_range(q, thr, max_results, rf)
         if self.process_group is None:
             if res is None:
                 raise ValueError(f"search_range found {total} rows, more than max_results={max_results}")

@@ -144,6 +144,20 @@ int isc_bank_pack(const void* rows, int in_dtype, int64_t n_rows, int D, int64_t
 int isc_bank_unpack(const void* packed, int dtype, int D, int64_t n_total, int64_t first_row, int64_t n_rows,
                     void* rows, int64_t ldy, void* stream);
 
+/* Row filter of the masked searches (isc_cosine_topk_masked, isc_cosine_topk_exhaustive_masked, isc_cosine_range_masked):
+ * a bitmap in the PACKED row order of an N-row bank.  Bit p of word p / 32 allows packed position p, i.e. ORIGINAL row
+ * (mul * p) mod N (isc_bank_permutation); the bank's padding to 256-row tiles is included and its bits are 0, so one
+ * tile's bits are 8 aligned words.
+ *   words          host: the bitmap's size in uint32 words, ceil(N / 256) * 8;  0 < N < 2^31 - 1 */
+int isc_row_mask_words(int64_t N, size_t* words);
+
+/* Pack a row filter given in ORIGINAL row order, in one launch (no host synchronisation).
+ *   allow          uint8 [N]: 1 = the row may be returned, 0 = it may not (any non-zero byte counts as 1)
+ *   packed_mask    uint32 [isc_row_mask_words(N)], 4-byte aligned: written entirely
+ *   allowed_count  optional device int64: the number of allowed rows is ADDED to it (zero it first, like isc_bank_pack's
+ *                  norm_bound); NULL = not counted */
+int isc_row_mask_pack(const uint8_t* allow, int64_t N, uint32_t* packed_mask, int64_t* allowed_count, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Encoder blocks (float32, NHWC activations, KRSC weights)
  * ------------------------------------------------------------------------------------------- */
@@ -340,6 +354,20 @@ int isc_cosine_topk(const void* bank, int dtype, int64_t N, int D, const void* q
                     int k, int64_t index_base, const float* norm_bound, float* out_scores, int64_t* out_indices,
                     int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* isc_cosine_topk over the rows a row filter allows: the answer of isc_cosine_topk on the bank of the allowed rows alone,
+ * with their indices in the whole bank, bit for bit.  Same arguments, limits and workspace (isc_cosine_topk_workspace_bytes)
+ * plus
+ *   row_mask     the packed row filter of this bank (isc_row_mask_pack); NULL is ISC_ERR_INVALID_ARG, not "no filter"
+ * k is still bounded by N only.  A query with m < k allowed rows gets them in positions 0 .. m-1 and PADDING after them:
+ * score NaN, index INT64_MAX.  The padding ranks after every real row in isc_topk_merge's order (a NaN-scored row
+ * included), so masked shards merge as they are.  The filter pass skips nothing: the whole bank is streamed whatever the
+ * filter's density; disallowed rows score -inf in it, and a query that carries fewer candidates than it asks for has seen
+ * every allowed row (cosine_topk.hip, k_final). */
+int isc_cosine_topk_masked(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
+                           int64_t ldq, int k, int64_t index_base, const float* norm_bound, float* out_scores,
+                           int64_t* out_indices, int32_t* status, void* workspace, size_t workspace_bytes,
+                           const uint32_t* row_mask, void* stream);
+
 /* Same contract and the same limits, data-independent cost: every score of every query is evaluated in float64
  * (vector FMA, no matrix cores, about one bank stream per four queries).  The kernel isc_cosine_topk falls back to
  * per query; exported as the reference implementation of the search on the device. */
@@ -347,6 +375,13 @@ int isc_cosine_topk_exhaustive_workspace_bytes(int dtype, int64_t N, int D, int 
 int isc_cosine_topk_exhaustive(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
                                int64_t ldq, int k, int64_t index_base, float* out_scores, int64_t* out_indices,
                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* isc_cosine_topk_exhaustive over the rows `row_mask` allows (NULL: ISC_ERR_INVALID_ARG), with isc_cosine_topk_masked's
+ * contract and padding; the workspace of isc_cosine_topk_exhaustive_workspace_bytes. */
+int isc_cosine_topk_exhaustive_masked(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,
+                                      int Q, int64_t ldq, int k, int64_t index_base, float* out_scores,
+                                      int64_t* out_indices, void* workspace, size_t workspace_bytes,
+                                      const uint32_t* row_mask, void* stream);
 
 /* Exact cosine range search: for every query, EVERY row with score(q, b) >= min_score[q], with the score of
  * isc_cosine_topk (the query rounded to the bank dtype first; float32(dot_f64(q, b) / max(||q||_2, 1e-12))).  NaN scores
@@ -373,6 +408,15 @@ int isc_cosine_range(const void* bank, int dtype, int64_t N, int D, const void* 
                      const float* min_score, int64_t index_base, const float* norm_bound, int64_t capacity,
                      int64_t* offsets, float* scores, int64_t* indices, int64_t* needed, int32_t* status,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* isc_cosine_range restricted to the rows `row_mask` allows (isc_row_mask_pack; NULL: ISC_ERR_INVALID_ARG): the unmasked
+ * result without the disallowed rows, bit for bit -- the rows of a zero query with t <= 0 are the allowed rows in row
+ * order.  Same arguments, limits and workspace (isc_cosine_range_workspace_bytes); `needed` counts allowed rows only. */
+int isc_cosine_range_masked(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
+                            int64_t ldq, const float* min_score, int64_t index_base, const float* norm_bound,
+                            int64_t capacity, int64_t* offsets, float* scores, int64_t* indices, int64_t* needed,
+                            int32_t* status, void* workspace, size_t workspace_bytes, const uint32_t* row_mask,
+                            void* stream);
 
 /* Merge G partial results (e.g. one per bank shard after the all-gather) into the final top-k by
  * (score descending, index ascending): scores float [G,Q,kin], indices int64 [G,Q,kin] -> [Q,kout], kout <= G*kin <= 4096.
