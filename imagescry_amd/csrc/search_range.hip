@@ -15,7 +15,7 @@
 //                      float32(E / denom) >= t
 //   k_range_offsets    per-query counts -> exclusive scan -> offsets[Q + 1]; needed = candidates + rows of all-row queries
 //   k_range_scatter    kept candidates -> (score, original row) keys in their query's segment
-//   segmented radix sort of the keys, descending (rocPRIM through hipCUB)
+//   segmented radix sort of the keys, descending (rocPRIM)
 //   k_range_fill_all   segments of zero queries with t <= 0 (every row ties at 0: already in order)
 //   k_range_emit       keys -> scores, indices + index_base
 //
@@ -35,7 +35,7 @@
 // learns the exact size to re-issue with from `needed`.
 #include <math.h>
 
-#include <hipcub/hipcub.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include "bank_layout.h"
 #include "isc_common.h"
@@ -99,12 +99,22 @@ struct RangeWs {
     size_t bytes;
 };
 
+// rocPRIM's default segmented sort for this architecture (it has no tuned gfx950 entry: 6 radix bits, 128 x 17 items,
+// warp sorts of 32 x 4 and 32 x 4) with the partitioning of segments by size switched off.  With partitioning the sort
+// reads the segment counts back to the host (hipMemcpyWithStream) once a call has 3000 segments or more, i.e. a range
+// search of >= 3000 queries would synchronise the host and could not be captured into a hipGraph.
+using SortConfig = rocprim::segmented_radix_sort_config<6, rocprim::kernel_config<128, 17>,
+                                                        rocprim::WarpSortConfig<32, 4, 256, 0xffffffffu, 32, 4, 256>, true>;
+
+hipError_t sort_keys_desc(void* tmp, size_t& bytes, const unsigned long long* in, unsigned long long* out, int64_t cap,
+                          int q, const int64_t* begin, const int64_t* end, hipStream_t stream) {
+    return rocprim::segmented_radix_sort_keys_desc<SortConfig>(tmp, bytes, in, out, (unsigned)cap, (unsigned)q, begin, end,
+                                                               0, 64, stream);
+}
+
 size_t sort_temp_bytes(int q, int64_t cap) {
     size_t bytes = 0;
-    if (hipcub::DeviceSegmentedRadixSort::SortKeysDescending(
-            nullptr, bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)cap, q,
-            (const int64_t*)nullptr, (const int64_t*)nullptr, 0, 64, (hipStream_t)0) != hipSuccess)
-        return 0;
+    if (sort_keys_desc(nullptr, bytes, nullptr, nullptr, cap, q, nullptr, nullptr, (hipStream_t)0) != hipSuccess) return 0;
     return bytes;
 }
 
@@ -600,9 +610,8 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q, int64_t 
                                                                           capacity, needed, offsets, w.fill, pm,
                                                                           w.keys_in);
     size_t sort_bytes = w.sort_bytes;
-    if (hipcub::DeviceSegmentedRadixSort::SortKeysDescending(w.sort_tmp, sort_bytes, w.keys_in, w.keys_out,
-                                                             (int)capacity, q, (const int64_t*)offsets,
-                                                             (const int64_t*)w.seg_end, 0, 64, stream) != hipSuccess)
+    if (sort_keys_desc(w.sort_tmp, sort_bytes, w.keys_in, w.keys_out, capacity, q, offsets, w.seg_end, stream) !=
+        hipSuccess)
         return ISC_ERR_LAUNCH;
     k_range_fill_all<<<grid_for(n, 256, 4 * cus), 256, 0, stream>>>(n, w.all_count, w.all_list, needed, capacity,
                                                                     offsets, w.keys_out);

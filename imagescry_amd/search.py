@@ -206,6 +206,9 @@ class EmbeddingBank:
         # search workspaces per LANE: -1 = the caller's stream (`search`), 0 / 1 = the two streams `search_async` alternates
         # between -- two searches in flight must not share a workspace
         self._workspaces: dict[int, dict[tuple[int, int], Tensor]] = {}
+        # workspaces a stream capture has seen (`_workspace`): a captured graph replays into them, so they live as long as
+        # the bank whatever the bucket cache drops
+        self._captured_workspaces: list[Tensor] = []
         self._lane_next = 0
         self._slots = (_ExchangeSlot(), _ExchangeSlot())
         self._slot_next = 0
@@ -407,7 +410,11 @@ class EmbeddingBank:
         """The search workspace.  The C side runs a call as passes of at most `ISC_SEARCH_PASS_QUERIES` queries over
         one workspace and cuts the queries into ONE tile of 64 (Q <= 64) or 128 (Q <= 128), or tiles of 256, so the size depends on
         (padded queries of a pass, k) only: alternating batch sizes inside one bucket -- a pipeline's short last
-        batch -- reuse one allocation instead of reallocating 150-300 MB per call.  One buffer per bucket and lane is kept."""
+        batch -- reuse one allocation instead of reallocating 150-300 MB per call.  One buffer per bucket and lane is kept.
+
+        A workspace handed out while the current stream is being captured is also kept in `_captured_workspaces`, which
+        the bucket cache never evicts: the graph holds its raw pointer, and a replay after the bucket had been dropped would
+        write into whatever tensor the allocator had given that memory to."""
         nq = min(n_queries, _lib.ISC_SEARCH_PASS_QUERIES)
         key = (-(-nq // 64) * 64 if nq <= 128 else -(-nq // 256) * 256, k)
         cache = self._workspaces.setdefault(lane, {})
@@ -423,6 +430,9 @@ class EmbeddingBank:
             if len(cache) >= 4:  # bound what a bank pins: drop the oldest bucket
                 cache.pop(next(iter(cache)))
             cache[key] = ws
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            if all(t.data_ptr() != ws.data_ptr() for t in self._captured_workspaces):
+                self._captured_workspaces.append(ws)
         return ws
 
     def _local_topk(
@@ -545,6 +555,11 @@ class EmbeddingBank:
         allowed rows alone, with indices in the whole bank, bit for bit; `k` is still bounded by the bank size, and a
         query with fewer than k allowed rows ends in score -inf, index -1 entries.  The whole bank is streamed whatever
         the filter's density (the masked filter).
+
+        A world-1 `search` may be captured into a CUDA / HIP graph (`torch.cuda.graph`) and replayed.  The workspace a
+        capture used stays allocated for the bank's lifetime so that replays stay valid: each distinct (query bucket, k)
+        captured pins one `isc_cosine_topk_workspace_bytes` buffer -- up to a few hundred MB on a large bank -- until the
+        bank is dropped.
         """
         del check
         return self._search(queries, k, lanes=False, mask=mask).result()
@@ -789,7 +804,8 @@ class EmbeddingBank:
         t = the k-th score of `search(q, k)` the first k rows of `search_range(q, t)` are `search(q, k)`.  NaN scores
         are never in a result.
 
-        The call synchronises the host to size the output (like `torch.nonzero`); a result larger than the first
+        The call synchronises the host to size the output (like `torch.nonzero`), so it cannot be captured into a graph
+        (capture `isc_cosine_range` itself with a fixed capacity instead); a result larger than the first
         internal guess costs a second device call of the exact size.  More than `max_results` rows in all raise
         ValueError with the count.  `last_range_status` (int32[4], device) holds diagnostics: [0] filter candidates,
         [1] queries answered by the float64 sweep, [2] float bits of the largest filter error in units of its bound.

@@ -14,7 +14,15 @@
  *   - `stream` is a `hipStream_t` passed as `void*` (NULL = the default stream); all
  *     work is enqueued on it and the call returns without synchronising, so the
  *     functions may be captured into a hipGraph;
- *   - scratch memory is a caller-provided workspace whose size is queried first;
+ *   - scratch memory is a caller-provided workspace whose size is queried first.  Its contents on entry do not matter
+ *     (every word a call reads it first writes or resets on the device, in the same call), and one workspace may serve
+ *     calls of different shapes in turn, as long as it is large enough for each;
+ *   - every output a function documents is written in full, whatever it held (outputs documented as accumulated into,
+ *     such as isc_bank_pack's norm_bound, excepted; a range search that overflows its capacity writes its offsets,
+ *     `needed` and status, and leaves the row buffers alone);
+ *   - a captured graph replays into the buffers it was captured with: keep the workspace and outputs alive while the
+ *     graph exists.  Timing (isc_timing_enable) records events around launches that isc_timing_read synchronises: keep
+ *     it off while a stream is being captured;
  *   - return value: 0 = ISC_OK, negative = error (see `isc_strerror`); never throws;
  *   - layouts are row-major / NCHW or NHWC as stated per function, dense unless a
  *     leading dimension is given (in ELEMENTS).

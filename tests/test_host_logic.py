@@ -141,3 +141,23 @@ def test_efficientnet_v2_parameter_counts_match_torchvision() -> None:
     assert sd["features.4.0.block.1.0.weight"].shape == (256, 1, 3, 3)  # depthwise
     assert sd["features.4.0.block.2.fc1.weight"].shape == (16, 256, 1, 1)  # squeeze = in_channels // 4
     assert sd["features.7.0.weight"].shape == (1280, 256, 1, 1)
+
+
+def test_workspaces_seen_by_a_capture_outlive_the_bucket_cache(monkeypatch) -> None:
+    """`EmbeddingBank._workspace` pins every workspace it hands out while the current stream is being captured (a graph
+    keeps its raw pointer): six (bucket, k) keys later the bucket cache has dropped it, the pin list has not, and asking
+    again does not pin it twice.  Host logic only: the bank is a bare object on the CPU."""
+    bank = EmbeddingBank.__new__(EmbeddingBank)
+    bank._bank = torch.empty(0)
+    bank.dtype, bank.num_local_rows, bank.dim = torch.float16, 5000, 64
+    bank._workspaces, bank._captured_workspaces = {}, []
+    capturing = {"on": True}
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: capturing["on"])
+    captured = bank._workspace(64, 10)
+    assert bank._workspace(64, 10) is captured and len(bank._captured_workspaces) == 1
+    capturing["on"] = False
+    for nq, k in ((1, 3), (100, 5), (300, 7), (1500, 9), (200, 11)):
+        bank._workspace(nq, k)
+    assert all(w is not captured for w in bank._workspaces[-1].values())  # evicted from the cache ...
+    assert [w.data_ptr() for w in bank._captured_workspaces] == [captured.data_ptr()]  # ... but still referenced
