@@ -8,8 +8,8 @@ Public surface (same names as the reference where the reference has them):
   `ResNet50Embedder`, `ViTB16Embedder`           -- reference src/imagescry/models/embedding.py:27-183
 * `PCA`, `EmbeddingPCAPipeline`                  -- reference src/imagescry/models/decomposition.py, pipelines.py
 * `EmbedSearchPipeline`                          -- encode -> search on two HIP streams (BASELINE config 5; new)
-* `EmbeddingBank`, `RangeResult`, `RowFilter`    -- cosine top-k and range search, optionally over a row filter (new;
-  see search.py)
+* `EmbeddingBank`, `RangeResult`, `RowFilter`    -- cosine top-k and range search, optionally over a row filter and
+  with per-query group exclusion (`row_groups=`, `exclude_group=`) (new; see search.py)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/imagescry_hip.h;
 PyTorch is used for device memory, streams and `torch.distributed` only.

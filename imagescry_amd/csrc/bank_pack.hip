@@ -1,6 +1,6 @@
 // Packing of embedding rows into the tile-contiguous, row-permuted bank layout (include/imagescry_hip.h:
 // isc_bank_pack, isc_bank_unpack, isc_bank_packed_bytes, isc_bank_permutation), and of a row filter into the same row
-// order (isc_row_mask_words, isc_row_mask_pack).
+// order (isc_row_mask_words, isc_row_mask_pack), and of row group codes (isc_row_groups_pack).
 #include "bank_layout.h"
 #include "isc_common.h"
 
@@ -100,6 +100,15 @@ __global__ __launch_bounds__(256) void k_row_mask_pack(const uint8_t* __restrict
     if (lane == 0) packed_mask[p >> 5] = (uint32_t)bits;
     if (lane == 32) packed_mask[p >> 5] = (uint32_t)(bits >> 32);
     if (allowed_count && lane == 0 && bits != 0ull) atomicAdd(allowed_count, (unsigned long long)__popcll(bits));
+}
+
+// Row group codes of a grouped search: one thread per PACKED position p of the padded bank; code[orig(p)] for p < n, -2
+// for the padding and for a negative code (a query code < 0 is read as -1: it matches neither).
+__global__ __launch_bounds__(256) void k_row_groups_pack(const int32_t* __restrict__ codes, IscPerm pm,
+                                                         int32_t* __restrict__ packed_codes) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int32_t c = p < pm.n ? codes[isc_perm_orig(pm, p)] : -2;
+    packed_codes[p] = c < 0 ? -2 : c;
 }
 
 int check_dtype(int dtype) { return dtype == ISC_F16 || dtype == ISC_F32; }
@@ -216,5 +225,14 @@ extern "C" int isc_row_mask_pack(const uint8_t* allow, int64_t N, uint32_t* pack
     const int64_t tiles = isc_ceil_div<int64_t>(N, ISC_TILE_ROWS);
     hipLaunchKernelGGL(k_row_mask_pack, dim3((unsigned)tiles), dim3(256), 0, isc_stream(stream), allow, isc_make_perm(N),
                        packed_mask, reinterpret_cast<unsigned long long*>(allowed_count));
+    return isc_launch_status();
+}
+
+extern "C" int isc_row_groups_pack(const int32_t* codes, int64_t N, int32_t* packed_codes, void* stream) {
+    ISC_REQUIRE(codes && packed_codes && N > 0 && N <= 0x7ffffffe);
+    if (!isc_aligned(codes, 4) || !isc_aligned(packed_codes, 16)) return ISC_ERR_ALIGNMENT;
+    const int64_t tiles = isc_ceil_div<int64_t>(N, ISC_TILE_ROWS);
+    hipLaunchKernelGGL(k_row_groups_pack, dim3((unsigned)tiles), dim3(256), 0, isc_stream(stream), codes,
+                       isc_make_perm(N), packed_codes);
     return isc_launch_status();
 }

@@ -61,6 +61,7 @@ namespace {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TM = 256;        // bank rows per tile
 constexpr int NTHREADS = 512;  // 8 waves
@@ -420,7 +421,9 @@ constexpr int A_TILE_BYTES = TM * 128;  // 32 KiB: one K step of one bank tile
 // fragment reads.
 //
 // RowMask: empty, or the row filter of a masked search (isc_row_mask_pack; search_common.h): the rows it disallows become
-// -inf where the rows past the end do, so they are never a candidate and never count towards a bound.
+// -inf where the rows past the end do, so they are never a candidate and never count towards a bound.  Or the IscGroups
+// of a grouped search: its optional row filter as above, and every score of a row whose group code equals its query's
+// becomes -inf as well (per query column), at the same place.
 template <typename T, int TNQ, int DBG, bool SAMPLE, typename... RowMask>
 __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* __restrict__ bank, int64_t r0,
                                                           int64_t r1, int tiles_per_chunk, int ntiles,
@@ -431,6 +434,7 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
                                                           int32_t* __restrict__ qflag, int32_t* __restrict__ status,
                                                           const int32_t* __restrict__ active, RowMask... row_mask) {
     constexpr bool MASK = sizeof...(RowMask) > 0;
+    constexpr bool GROUP = isc_grouped<RowMask...>();  // (MASK as well; its bitmap may then be NULL)
     // DBG 20 / 32 / 33 are the REDO instantiations of 0 / 12 / 13 (k_final2's feeder: the whole bank against the fixed
     // thresholds of the listed queries).  They are kernels of their own so that a profile lists them apart from the
     // search's streaming launches; `active` counts the listed query slots -- normally zero, and the launch ends here.
@@ -633,9 +637,60 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
                 }
         }
     };
+    // a grouped search without a row filter skips the bitmap (kernel argument: uniform)
+    [[maybe_unused]] const bool use_mask = !GROUP || isc_row_mask_ptr(row_mask...) != nullptr;
     [[maybe_unused]] uint32_t sample_mask[MASK_WORDS];
-    if constexpr (MASK && SAMPLE)  // the one tile of a sample workgroup: its words are in flight during the whole loop
-        load_mask(std::integral_constant<int, MB>{}, std::integral_constant<int, 0>{}, (r0 >> 8) + tile_begin, sample_mask);
+    if constexpr (MASK && SAMPLE) {  // the one tile of a sample workgroup: its words are in flight during the whole loop
+        if (use_mask)
+            load_mask(std::integral_constant<int, MB>{}, std::integral_constant<int, 0>{}, (r0 >> 8) + tile_begin,
+                      sample_mask);
+    }
+
+    // ---- group exclusion (GROUP).  The lane's four query columns' codes, once per workgroup (a redo launch maps its slots
+    // to queries through slot_query; unused slots and columns past the pass carry no group).  A wave's rows of a tile are
+    // MBE blocks of 16 from wave_row0, and the lane holds rows 4 fg .. 4 fg + 3 of each: one 16-byte vector load per block,
+    // issued at the tile's first K step (before that step's LDS-DMA, so the counted waits retire it with the DMA older than
+    // what they leave in flight) and consumed at its end, where the scores of the query's own group become -inf.
+    // The 256-query shape has no registers for a tile's codes (MBE x 4 VGPRs beside 160 accumulators: the streaming
+    // instantiations spilled 12 - 34 VGPRs), so there (DEFER) a streaming launch tests a survivor's code where the tail
+    // moves it from the lane's segment into the query's list: a survivor is rare, and the segments are read after the last
+    // DMA.  An own-group survivor still takes a segment slot, so a group of thousands of rows can overflow a segment: the
+    // query is then redone (qflag), exactly.  Its sample launch loads the codes in the epilogue, after the loop.
+    constexpr bool DEFER = GROUP && TNQ == 256 && !SAMPLE;
+    constexpr bool LATE = GROUP && TNQ == 256 && SAMPLE;
+    [[maybe_unused]] int qcode[4];
+    if constexpr (GROUP) {
+        const IscGroups& gr = (row_mask, ...);
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const int col = q0 + wn * 64 + n * 16 + frow;
+            if constexpr (REDO) {
+                const int c = col < *active ? gr.query_group[gr.slot_query[col]] : -1;
+                qcode[n] = c < 0 ? -1 : c;
+            } else {
+                qcode[n] = isc_query_code(gr, col);
+            }
+        }
+    }
+    auto load_codes = [&](auto mbe_c, int64_t gtile, i32x4 (&c)[MBMAX]) {
+        constexpr int MBE = decltype(mbe_c)::value;
+        const int32_t* src = isc_row_group_ptr(row_mask...) + gtile * TM + wave_row0 + fg * 4;
+#pragma unroll
+        for (int m = 0; m < MBE; ++m) c[m] = *reinterpret_cast<const i32x4*>(src + 16 * m);
+    };
+    auto apply_codes = [&](auto mbe_c, const i32x4 (&c)[MBMAX]) {
+        constexpr int MBE = decltype(mbe_c)::value;
+#pragma unroll
+        for (int m = 0; m < MBE; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int n = 0; n < 4; ++n)
+                    if (c[m][r] == qcode[n]) acc[m][n][r] = -INFINITY;
+    };
+    [[maybe_unused]] i32x4 sample_codes[MBMAX];
+    if constexpr (GROUP && SAMPLE && !LATE)
+        load_codes(std::integral_constant<int, MB>{}, (r0 >> 8) + tile_begin, sample_codes);
 
     const int seg = (chunk * WM + wm) * 4 + fg;
     Cand* my_ent = seg_ent + ((size_t)seg * qpad + q0 + wn * 64 + frow) * CAP;  // + n * 16 * CAP
@@ -677,10 +732,14 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
     using SUB_C = std::integral_constant<int, (TNQ == 256 && STAGGER) ? ((ASYM ? MBLO : MB) * 16) & 31 : 0>;
     int kt = 0, tile = 0;
     [[maybe_unused]] uint32_t tile_mask[MASK_WORDS];
+    [[maybe_unused]] i32x4 tile_codes[MBMAX];
     if constexpr (MODE == 22) st_prev = stamp();
     for (int step = 0; step < total_steps; ++step) {
         if constexpr (MASK && !SAMPLE) {
-            if (kt == 0) load_mask(MBE_C{}, SUB_C{}, (r0 >> 8) + tile_begin + tile, tile_mask);
+            if (kt == 0 && use_mask) load_mask(MBE_C{}, SUB_C{}, (r0 >> 8) + tile_begin + tile, tile_mask);
+        }
+        if constexpr (GROUP && !SAMPLE && !DEFER) {
+            if (kt == 0) load_codes(MBE_C{}, (r0 >> 8) + tile_begin + tile, tile_codes);
         }
         if constexpr (HM) {
             // ---- 256-query shape, half-major.  A K step is 2 MBW units: unit u = (row block u % MBW, half u / MBW), four
@@ -1021,7 +1080,10 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
             kt = 0;
             constexpr int MBE = STAGGER ? MBHI : MBLO;  // this wave's row blocks (MB when the split is symmetric)
             const int64_t trow0 = r0 + (int64_t)(tile_begin + tile) * TM + wave_row0 + fg * 4;
-            if constexpr (MASK) apply_mask(MBE_C{}, SUB_C{}, tile_mask);
+            if constexpr (MASK) {
+                if (use_mask) apply_mask(MBE_C{}, SUB_C{}, tile_mask);
+            }
+            if constexpr (GROUP && !DEFER) apply_codes(MBE_C{}, tile_codes);
             // rows past the end of the level exist only in its last tile: they become -inf there, once, instead of
             // being tested per element
             if (r0 + (int64_t)(tile_begin + tile + 1) * TM > r1) {
@@ -1114,7 +1176,11 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
         // the whole bank.  With nslots ~ 2 kp about 1.35 kp scores per query pass.  nslots = 0 (kp > 64): every score
         // is kept.  Rows past the end of the bank count as -inf.
         const int64_t trow0 = r0 + (int64_t)tile_begin * TM + wm * (TM / WM) + fg * 4;
-        if constexpr (MASK) apply_mask(std::integral_constant<int, MB>{}, std::integral_constant<int, 0>{}, sample_mask);
+        if constexpr (MASK) {
+            if (use_mask) apply_mask(std::integral_constant<int, MB>{}, std::integral_constant<int, 0>{}, sample_mask);
+        }
+        if constexpr (LATE) load_codes(std::integral_constant<int, MB>{}, (r0 >> 8) + tile_begin, sample_codes);
+        if constexpr (GROUP) apply_codes(std::integral_constant<int, MB>{}, sample_codes);
 #pragma unroll
         for (int m = 0; m < MB; ++m)
 #pragma unroll
@@ -1238,11 +1304,15 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
 #pragma unroll
                             for (int j = 0; j < 4; ++j) e[j] = src[min(i + j, c - 1)];
 #pragma unroll
-                            for (int j = 0; j < 4; ++j)
+                            for (int j = 0; j < 4; ++j) {
+                                if constexpr (DEFER) {
+                                    if (i + j < c && isc_row_group_ptr(row_mask...)[e[j].row] == qcode[n]) continue;
+                                }
                                 if (i + j < c) {
                                     const int pos = atomicAdd(&lcount[qc], 1);
                                     if (pos < LCAP) lists[qc * LCAP + pos] = e[j];
                                 }
+                            }
                         }
                     }
                 }
@@ -1851,7 +1921,19 @@ void for_each_segment(const Level& l, const Plan& p, F&& launch) {
     }
 }
 
-// RowMask: empty, or the row filter of isc_cosine_topk_masked (const uint32_t*), handed to every filter launch and k_exact
+// The pack element a launch of pass q0 (q queries) takes: a row filter as it is; the IscGroups of a grouped search with its
+// query codes moved to the pass, and with the redo filter's slot -> query map (`slots`) where one is given.
+__host__ inline const uint32_t* pass_filter(const uint32_t* m, int, int, const int32_t*) { return m; }
+__host__ inline IscGroups pass_filter(IscGroups g, int q0, int q, const int32_t* slots) {
+    g.query_group += q0;
+    g.nq = q;
+    g.slot_query = slots;
+    return g;
+}
+
+// RowMask: empty, or the row filter of isc_cosine_topk_masked (const uint32_t*), handed to every filter launch and k_exact;
+// or the IscGroups of isc_cosine_topk_grouped.  k_final and k_final2 are the masked ones in both cases: neither reads the
+// filter, and the short-list proof of k_final holds for any per-(row, query) predicate.
 template <typename T, typename TQ, typename... RowMask>
 int run(const void* bank, int64_t n, int d, const void* queries, int q_total, int64_t ldq, int k, int64_t index_base,
         const float* norm_bound, float* out_s, int64_t* out_i, int32_t* status, void* ws_base, hipStream_t stream,
@@ -1889,9 +1971,15 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q_total, in
             // 1.3 x with 127 / 483).
             for_each_segment(l, p, [&](const Level& ls) {
                 isc_timing_begin(ISC_KERNEL_DOTS_FILTER, stream);
-                if (p.tnq == 256) launch_filter<T, 256>(ls, p, w, io, bank_bytes, ksteps, status, stream, rm...);
-                else if (p.tnq == 128) launch_filter<T, 128>(ls, p, w, io, bank_bytes, ksteps, status, stream, rm...);
-                else launch_filter<T, 64>(ls, p, w, io, bank_bytes, ksteps, status, stream, rm...);
+                if (p.tnq == 256)
+                    launch_filter<T, 256>(ls, p, w, io, bank_bytes, ksteps, status, stream,
+                                          pass_filter(rm, q0, q, nullptr)...);
+                else if (p.tnq == 128)
+                    launch_filter<T, 128>(ls, p, w, io, bank_bytes, ksteps, status, stream,
+                                          pass_filter(rm, q0, q, nullptr)...);
+                else
+                    launch_filter<T, 64>(ls, p, w, io, bank_bytes, ksteps, status, stream,
+                                         pass_filter(rm, q0, q, nullptr)...);
                 isc_timing_end(ISC_KERNEL_DOTS_FILTER, stream);
             });
             if (li + 1 < p.nlevels) {
@@ -1927,17 +2015,28 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q_total, in
             all.tiles_per_chunk = isc_ceil_div(all.ntiles, want);
             all.nchunks = isc_ceil_div(all.ntiles, all.tiles_per_chunk);
             for_each_segment(all, p, [&](const Level& ls) {
-                if (p.tnq == 256) launch_filter<T, 256>(ls, p, w, rio, bank_bytes, ksteps, status, stream, rm...);
-                else if (p.tnq == 128) launch_filter<T, 128>(ls, p, w, rio, bank_bytes, ksteps, status, stream, rm...);
-                else launch_filter<T, 64>(ls, p, w, rio, bank_bytes, ksteps, status, stream, rm...);
+                if (p.tnq == 256)
+                    launch_filter<T, 256>(ls, p, w, rio, bank_bytes, ksteps, status, stream,
+                                          pass_filter(rm, q0, q, w.r_list)...);
+                else if (p.tnq == 128)
+                    launch_filter<T, 128>(ls, p, w, rio, bank_bytes, ksteps, status, stream,
+                                          pass_filter(rm, q0, q, w.r_list)...);
+                else
+                    launch_filter<T, 64>(ls, p, w, rio, bank_bytes, ksteps, status, stream,
+                                         pass_filter(rm, q0, q, w.r_list)...);
             });
             hipLaunchKernelGGL(k_final2<T>, dim3(q), dim3(SEL_THREADS), 0, stream, bank_bytes, ksteps, w.qpacked2, p.tnq, k,
                                pm, index_base, w.r_count, w.r_list, w.qcount2, w.qflag2, w.qlist, os, oi,
                                w.exact.redo_count, w.exact.redo_list, status);
         }
-        const int st = isc_exact_launch(sizeof(T) == 2 ? ISC_F16 : ISC_F32, bank, n, d, qptr,
-                                        sizeof(TQ) == 2 ? ISC_F16 : ISC_F32, ldq, k, index_base, w.exact, os, oi, status,
-                                        isc_row_mask_ptr(rm...), stream);
+        int st;
+        if constexpr (isc_grouped<RowMask...>())
+            st = isc_exact_launch(sizeof(T) == 2 ? ISC_F16 : ISC_F32, bank, n, d, qptr, sizeof(TQ) == 2 ? ISC_F16 : ISC_F32,
+                                  ldq, k, index_base, w.exact, os, oi, status, pass_filter(rm, q0, q, nullptr)..., stream);
+        else
+            st = isc_exact_launch(sizeof(T) == 2 ? ISC_F16 : ISC_F32, bank, n, d, qptr,
+                                  sizeof(TQ) == 2 ? ISC_F16 : ISC_F32, ldq, k, index_base, w.exact, os, oi, status,
+                                  isc_row_mask_ptr(rm...), stream);
         if (st != ISC_OK) return st;
     }
     return isc_launch_status();
@@ -1967,7 +2066,8 @@ namespace {
 
 int topk(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q, int64_t ldq, int k,
          int64_t index_base, const float* norm_bound, float* out_scores, int64_t* out_indices, int32_t* status,
-         void* workspace, size_t workspace_bytes, const uint32_t* row_mask, void* stream) {
+         void* workspace, size_t workspace_bytes, const uint32_t* row_mask, void* stream,
+         const IscGroups* groups = nullptr) {
     ISC_REQUIRE(bank && queries && out_scores && out_indices && status);
     ISC_REQUIRE(q_dtype == ISC_F16 || q_dtype == ISC_F32);
     const int st = check_args(dtype, N, D, Q, k);
@@ -1978,7 +2078,9 @@ int topk(const void* bank, int dtype, int64_t N, int D, const void* queries, int
     isc_cosine_topk_workspace_bytes(dtype, N, D, Q, k, &need);
     if (!workspace || workspace_bytes < need) return ISC_ERR_WORKSPACE;
 #define ISC_RUN(T_, TQ_)                                                                                             \
-    return row_mask ? run<T_, TQ_>(bank, N, D, queries, Q, ldq, k, index_base, norm_bound, out_scores, out_indices,    \
+    return groups   ? run<T_, TQ_>(bank, N, D, queries, Q, ldq, k, index_base, norm_bound, out_scores, out_indices,    \
+                                   status, workspace, isc_stream(stream), *groups)                                     \
+           : row_mask ? run<T_, TQ_>(bank, N, D, queries, Q, ldq, k, index_base, norm_bound, out_scores, out_indices,    \
                                    status, workspace, isc_stream(stream), row_mask)                                    \
                     : run<T_, TQ_>(bank, N, D, queries, Q, ldq, k, index_base, norm_bound, out_scores, out_indices,    \
                                    status, workspace, isc_stream(stream))
@@ -2008,4 +2110,17 @@ extern "C" int isc_cosine_topk_masked(const void* bank, int dtype, int64_t N, in
     ISC_REQUIRE(row_mask);
     return topk(bank, dtype, N, D, queries, q_dtype, Q, ldq, k, index_base, norm_bound, out_scores, out_indices, status,
                 workspace, workspace_bytes, row_mask, stream);
+}
+
+extern "C" int isc_cosine_topk_grouped(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,
+                                       int Q, int64_t ldq, int k, int64_t index_base, const float* norm_bound,
+                                       float* out_scores, int64_t* out_indices, int32_t* status, void* workspace,
+                                       size_t workspace_bytes, const uint32_t* row_mask, const int32_t* row_group,
+                                       const int32_t* query_group, void* stream) {
+    ISC_REQUIRE(row_group && query_group);
+    if (!isc_aligned(row_group, 16) || !isc_aligned(query_group, 4) || !isc_aligned(row_mask, 4))
+        return ISC_ERR_ALIGNMENT;
+    const IscGroups g{row_mask, row_group, query_group, nullptr, Q};
+    return topk(bank, dtype, N, D, queries, q_dtype, Q, ldq, k, index_base, norm_bound, out_scores, out_indices, status,
+                workspace, workspace_bytes, row_mask, stream, &g);
 }

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "bank_layout.h"
 #include "isc_common.h"
 
@@ -73,19 +75,54 @@ __device__ __forceinline__ unsigned long long isc_wave_max_key(unsigned long lon
 // Bit p of word p / 32 allows packed position p; a tile's 256 bits are the 8 words from 8 * tile, padding bits 0.  The masked
 // kernels take the bitmap as a trailing parameter PACK, empty in their unmasked instantiations: those keep their argument
 // list, and with it their code (kernels that read the grid size load it from just past the explicit arguments).
+//
+// Per-query group exclusion (isc_*_grouped) passes ONE IscGroups in the same pack: query q may not return a row whose code
+// equals its own.  Row codes are >= 0 (isc_row_groups_pack stores -2 for a negative code and the padding), and a query
+// code < 0 is read as -1, so it matches no row.
+struct IscGroups {
+    const uint32_t* mask;        // the packed row filter as above, or NULL: every row is allowed
+    const int32_t* row_group;    // int32 [ceil(N / 256) * 256]: code of packed position p (isc_row_groups_pack)
+    const int32_t* query_group;  // int32: code of query i of the pass (the pass's offset applied)
+    const int32_t* slot_query;   // NULL, or the slot -> query map of a redo filter launch (cosine_topk.hip, r_list)
+    int nq;                      // queries of the pass: columns >= nq carry no group
+};
+template <typename... RowMask>
+constexpr bool isc_grouped() {
+    if constexpr (sizeof...(RowMask) == 1) return (std::is_same<RowMask, IscGroups>::value && ...);
+    else return false;
+}
 template <typename... RowMask>
 __host__ __device__ __forceinline__ const uint32_t* isc_row_mask_ptr(RowMask... row_mask) {
     if constexpr (sizeof...(RowMask) == 0) return nullptr;
+    else if constexpr (isc_grouped<RowMask...>()) return (row_mask, ...).mask;
     else return (row_mask, ...);
 }
 template <typename... RowMask>
 __device__ __forceinline__ bool isc_row_allowed(int64_t p, RowMask... row_mask) {
     if constexpr (sizeof...(RowMask) == 0) {
         return true;
+    } else if constexpr (isc_grouped<RowMask...>()) {
+        const uint32_t* m = isc_row_mask_ptr(row_mask...);
+        return m == nullptr || ((m[p >> 5] >> (p & 31)) & 1u);
     } else {
         const uint32_t* m = isc_row_mask_ptr(row_mask...);
         return (m[p >> 5] >> (p & 31)) & 1u;
     }
+}
+template <typename... RowMask>
+__host__ __device__ __forceinline__ const int32_t* isc_row_group_ptr(RowMask... row_mask) {
+    if constexpr (isc_grouped<RowMask...>()) return (row_mask, ...).row_group;
+    else return nullptr;
+}
+// the group code of query i of the pass (-1: none), and whether query code qc may return packed position p
+__device__ __forceinline__ int isc_query_code(const IscGroups& g, int i) {
+    const int c = i < g.nq ? g.query_group[i] : -1;
+    return c < 0 ? -1 : c;
+}
+template <typename... RowMask>
+__device__ __forceinline__ bool isc_row_allowed_for(int64_t p, int qc, RowMask... row_mask) {
+    if constexpr (isc_grouped<RowMask...>()) return isc_row_allowed(p, row_mask...) && (row_mask, ...).row_group[p] != qc;
+    else return isc_row_allowed(p, row_mask...);
 }
 
 // ---- float64 arithmetic shared by the exact re-scores of cosine_topk.hip and search_range.hip ---------------------
@@ -155,3 +192,7 @@ IscExactWs isc_exact_ws_carve(void* base, int64_t n, int q, int k);
 int isc_exact_launch(int dtype, const void* bank, int64_t n, int d, const void* queries, int q_dtype, int64_t ldq, int k,
                      int64_t index_base, const IscExactWs& ws, float* out_s, int64_t* out_i, int32_t* status,
                      const uint32_t* row_mask, hipStream_t stream);
+// ... of a grouped search: `groups` with the query codes of these queries (redo_list indexes them)
+int isc_exact_launch(int dtype, const void* bank, int64_t n, int d, const void* queries, int q_dtype, int64_t ldq, int k,
+                     int64_t index_base, const IscExactWs& ws, float* out_s, int64_t* out_i, int32_t* status,
+                     const IscGroups& groups, hipStream_t stream);

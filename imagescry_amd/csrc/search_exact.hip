@@ -64,7 +64,8 @@ __device__ __forceinline__ double group8_sum(double v) {  // over the 8 lanes th
 // list per query and published; the workgroup that publishes last merges the chunks' lists (k-way merge of sorted
 // lists by one wave per query) and writes the result rows.
 // RowMask: empty, or the row filter of a masked search (isc_row_allowed): disallowed rows are never candidates, and a query
-// with fewer than k allowed rows ends in the ABI's padding (score NaN, index INT64_MAX) instead of empty keys.
+// with fewer than k allowed rows ends in the ABI's padding (score NaN, index INT64_MAX) instead of empty keys.  Or the
+// IscGroups of a grouped search: the same, with the rows of the query's own group disallowed for that query.
 template <typename T, int GQ, typename... RowMask>
 __global__ __launch_bounds__(EX_THREADS) void k_exact(const unsigned char* __restrict__ bank, int ks, IscPerm pm,
                                                       int ntiles, int tiles_per_chunk, const void* __restrict__ queries,
@@ -118,6 +119,11 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact(const unsigned char* __res
         double denom[GQ];
 #pragma unroll
         for (int g = 0; g < GQ; ++g) denom[g] = denom_sh[g];
+        [[maybe_unused]] int qcode[GQ];
+        if constexpr (isc_grouped<RowMask...>()) {
+#pragma unroll
+            for (int g = 0; g < GQ; ++g) qcode[g] = g < gn ? isc_query_code((row_mask, ...), redo_list[g0 + g]) : -1;
+        }
 
         for (int tile = tile_begin; tile < tile_end; ++tile) {
             for (int grp = wave; grp < ISC_TILE_ROWS / 8; grp += EX_WAVES) {
@@ -143,7 +149,8 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact(const unsigned char* __res
                     unsigned long long* wl = lists + ((size_t)g * EX_WAVES + wave) * k;
                     const unsigned long long worst = wl[k - 1];  // 0 while the list is not full
                     bool cand = ch == 0 && p < pm.n && isc_score_bits(sc) >= (unsigned)(worst >> 32);
-                    if constexpr (MASK) cand = cand && isc_row_allowed(p, row_mask...);
+                    if constexpr (isc_grouped<RowMask...>()) cand = cand && isc_row_allowed_for(p, qcode[g], row_mask...);
+                    else if constexpr (MASK) cand = cand && isc_row_allowed(p, row_mask...);
                     unsigned long long mask = __ballot(cand);
                     if (mask == 0ull) continue;
                     const unsigned long long key = cand ? isc_make_key(sc, (int)isc_perm_orig(pm, p)) : 0ull;
@@ -389,6 +396,12 @@ int isc_exact_launch(int dtype, const void* bank, int64_t n, int d, const void* 
     return exact_launch(dtype, bank, n, d, queries, q_dtype, ldq, k, index_base, ws, out_s, out_i, status, stream);
 }
 
+int isc_exact_launch(int dtype, const void* bank, int64_t n, int d, const void* queries, int q_dtype, int64_t ldq, int k,
+                     int64_t index_base, const IscExactWs& ws, float* out_s, int64_t* out_i, int32_t* status,
+                     const IscGroups& groups, hipStream_t stream) {
+    return exact_launch(dtype, bank, n, d, queries, q_dtype, ldq, k, index_base, ws, out_s, out_i, status, stream, groups);
+}
+
 extern "C" int isc_topk_merge(const float* scores, const int64_t* indices, int G, int Q, int kin, int kout,
                               int64_t stride_g_scores, int64_t stride_g_indices, float* out_scores,
                               int64_t* out_indices, void* stream) {
@@ -417,7 +430,7 @@ namespace {
 
 int exhaustive(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q, int64_t ldq, int k,
                int64_t index_base, float* out_scores, int64_t* out_indices, void* workspace, size_t workspace_bytes,
-               const uint32_t* row_mask, void* stream) {
+               const uint32_t* row_mask, void* stream, const IscGroups* groups = nullptr) {
     ISC_REQUIRE(bank && queries && out_scores && out_indices);
     ISC_REQUIRE(q_dtype == ISC_F16 || q_dtype == ISC_F32);
     const int st = ex_check(dtype, N, D, Q, k);
@@ -433,9 +446,18 @@ int exhaustive(const void* bank, int dtype, int64_t N, int D, const void* querie
         const int q = Q - q0 < qb ? Q - q0 : qb;
         hipLaunchKernelGGL(k_list_all, dim3(isc_ceil_div(q, 256)), dim3(256), 0, s, ws.redo_count, ws.redo_list, ws.done,
                            q);
-        const int st2 = isc_exact_launch(dtype, bank, N, D, static_cast<const char*>(queries) + (size_t)q0 * ldq * esz,
-                                         q_dtype, ldq, k, index_base, ws, out_scores + (size_t)q0 * k,
-                                         out_indices + (size_t)q0 * k, nullptr, row_mask, s);
+        const void* qp = static_cast<const char*>(queries) + (size_t)q0 * ldq * esz;
+        int st2;
+        if (groups) {
+            IscGroups g = *groups;
+            g.query_group += q0;
+            g.nq = q;
+            st2 = isc_exact_launch(dtype, bank, N, D, qp, q_dtype, ldq, k, index_base, ws, out_scores + (size_t)q0 * k,
+                                   out_indices + (size_t)q0 * k, nullptr, g, s);
+        } else {
+            st2 = isc_exact_launch(dtype, bank, N, D, qp, q_dtype, ldq, k, index_base, ws, out_scores + (size_t)q0 * k,
+                                   out_indices + (size_t)q0 * k, nullptr, row_mask, s);
+        }
         if (st2 != ISC_OK) return st2;
     }
     return isc_launch_status();
@@ -457,4 +479,17 @@ extern "C" int isc_cosine_topk_exhaustive_masked(const void* bank, int dtype, in
     ISC_REQUIRE(row_mask);
     return exhaustive(bank, dtype, N, D, queries, q_dtype, Q, ldq, k, index_base, out_scores, out_indices, workspace,
                       workspace_bytes, row_mask, stream);
+}
+
+extern "C" int isc_cosine_topk_exhaustive_grouped(const void* bank, int dtype, int64_t N, int D, const void* queries,
+                                                  int q_dtype, int Q, int64_t ldq, int k, int64_t index_base,
+                                                  float* out_scores, int64_t* out_indices, void* workspace,
+                                                  size_t workspace_bytes, const uint32_t* row_mask,
+                                                  const int32_t* row_group, const int32_t* query_group, void* stream) {
+    ISC_REQUIRE(row_group && query_group);
+    if (!isc_aligned(row_group, 16) || !isc_aligned(query_group, 4) || !isc_aligned(row_mask, 4))
+        return ISC_ERR_ALIGNMENT;
+    const IscGroups g{row_mask, row_group, query_group, nullptr, Q};
+    return exhaustive(bank, dtype, N, D, queries, q_dtype, Q, ldq, k, index_base, out_scores, out_indices, workspace,
+                      workspace_bytes, row_mask, stream, &g);
 }

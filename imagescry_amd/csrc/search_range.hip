@@ -46,6 +46,7 @@ namespace {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RQT = 64;                          // queries per filter workgroup (one query tile)
 constexpr int RPASS = ISC_SEARCH_PASS_QUERIES;   // queries per pass: the workspace holds one pass's packed queries
@@ -345,16 +346,36 @@ __global__ __launch_bounds__(256) void k_range_filter(const unsigned char* __res
     // row filter: disallowed rows score -inf, which no tau lets through ("A > tau" is false even for tau = -inf).  This
     // wave's 64 rows are two words; row 16 m + 4 grp + j is bit 16 (m & 1) + 4 grp + j of word m / 2.
     if constexpr (sizeof...(RowMask) > 0) {
-        const uint32_t* mw = isc_row_mask_ptr(row_mask...) + tile * (ISC_TILE_ROWS / 32) + wave * 2;
+        const uint32_t* mb = isc_row_mask_ptr(row_mask...);  // (NULL only in a grouped call without a row filter)
+        if (!isc_grouped<RowMask...>() || mb != nullptr) {
+            const uint32_t* mw = mb + tile * (ISC_TILE_ROWS / 32) + wave * 2;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const uint32_t nib = mw[m >> 1] >> ((m & 1) * 16 + grp * 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (!((nib >> j) & 1u)) {
+#pragma unroll
+                        for (int nb = 0; nb < 4; ++nb) acc[m][nb][j] = -INFINITY;
+                    }
+            }
+        }
+    }
+    // group exclusion: a row of the query's own group scores -inf for that query.  Row 16 m + 4 grp + j's code is element j
+    // of one 16-byte load per m; query column 16 nb + r16's code is read once.
+    if constexpr (isc_grouped<RowMask...>()) {
+        const IscGroups& gr = (row_mask, ...);
+        int qc[4];
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) qc[nb] = isc_query_code(gr, q0 + qt * RQT + nb * 16 + r16);
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-            const uint32_t nib = mw[m >> 1] >> ((m & 1) * 16 + grp * 4);
+            const i32x4 rc = *reinterpret_cast<const i32x4*>(gr.row_group + row0 + m * 16);
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (!((nib >> j) & 1u)) {
 #pragma unroll
-                    for (int nb = 0; nb < 4; ++nb) acc[m][nb][j] = -INFINITY;
-                }
+                for (int nb = 0; nb < 4; ++nb)
+                    if (rc[j] == qc[nb]) acc[m][nb][j] = -INFINITY;
         }
     }
     float tq[4];
@@ -390,7 +411,7 @@ __global__ __launch_bounds__(256) void k_range_filter(const unsigned char* __res
 
 // The float64 scan of the queries the filter cannot serve: one thread per bank row, the whole bank per listed query.  A row
 // is appended when its score is >= prevfloat(t) (one float32 step of margin for the summation order): the re-score decides.
-// Rows a row filter disallows (RowMask) are skipped.
+// Rows a row filter disallows (RowMask) are skipped, and with IscGroups the rows of the listed query's own group.
 template <typename T, typename... RowMask>
 __global__ __launch_bounds__(256) void k_range_scan(const unsigned char* __restrict__ bank, int64_t n, int ks,
                                                     const unsigned char* __restrict__ qpacked,
@@ -406,11 +427,13 @@ __global__ __launch_bounds__(256) void k_range_scan(const unsigned char* __restr
         const unsigned char* qrow = qrow_of(qpacked, w, ks);
         const float t_dn = nextafterf(min_score[q0 + w], -INFINITY);
         const double dn = denom[w];
+        [[maybe_unused]] int qc = -1;
+        if constexpr (isc_grouped<RowMask...>()) qc = isc_query_code((row_mask, ...), q0 + w);
         for (int64_t base = (int64_t)blockIdx.x * 256; base < n; base += (int64_t)gridDim.x * 256) {
             const int64_t row = base + threadIdx.x;
             double e = 0.0;
             bool keep = false;
-            if (row < n && isc_row_allowed(row, row_mask...)) {
+            if (row < n && isc_row_allowed_for(row, qc, row_mask...)) {
                 for (int s = 0; s < ks; ++s) {
 #pragma unroll
                     for (int ch = 0; ch < 8; ++ch) {
@@ -643,7 +666,7 @@ namespace {
 int range(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q, int64_t ldq,
           const float* min_score, int64_t index_base, const float* norm_bound, int64_t capacity, int64_t* offsets,
           float* scores, int64_t* indices, int64_t* needed, int32_t* status, void* workspace, size_t workspace_bytes,
-          const uint32_t* row_mask, void* stream) {
+          const uint32_t* row_mask, void* stream, const IscGroups* groups = nullptr) {
     ISC_REQUIRE(bank && queries && min_score && offsets && scores && indices && needed && status);
     ISC_REQUIRE(q_dtype == ISC_F16 || q_dtype == ISC_F32);
     const int st = check_args(dtype, N, D, Q, capacity);
@@ -654,7 +677,9 @@ int range(const void* bank, int dtype, int64_t N, int D, const void* queries, in
     isc_cosine_range_workspace_bytes(dtype, N, D, Q, capacity, &need);
     if (!workspace || workspace_bytes < need) return ISC_ERR_WORKSPACE;
 #define ISC_RUN(T_, TQ_)                                                                                              \
-    return row_mask ? run<T_, TQ_>(bank, N, D, queries, Q, ldq, min_score, index_base, norm_bound, capacity, offsets,   \
+    return groups   ? run<T_, TQ_>(bank, N, D, queries, Q, ldq, min_score, index_base, norm_bound, capacity, offsets,   \
+                                   scores, indices, needed, status, workspace, isc_stream(stream), *groups)             \
+           : row_mask ? run<T_, TQ_>(bank, N, D, queries, Q, ldq, min_score, index_base, norm_bound, capacity, offsets,   \
                                    scores, indices, needed, status, workspace, isc_stream(stream), row_mask)            \
                     : run<T_, TQ_>(bank, N, D, queries, Q, ldq, min_score, index_base, norm_bound, capacity, offsets,   \
                                    scores, indices, needed, status, workspace, isc_stream(stream))
@@ -685,4 +710,18 @@ extern "C" int isc_cosine_range_masked(const void* bank, int dtype, int64_t N, i
     ISC_REQUIRE(row_mask);
     return range(bank, dtype, N, D, queries, q_dtype, Q, ldq, min_score, index_base, norm_bound, capacity, offsets, scores,
                  indices, needed, status, workspace, workspace_bytes, row_mask, stream);
+}
+
+extern "C" int isc_cosine_range_grouped(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,
+                                        int Q, int64_t ldq, const float* min_score, int64_t index_base,
+                                        const float* norm_bound, int64_t capacity, int64_t* offsets, float* scores,
+                                        int64_t* indices, int64_t* needed, int32_t* status, void* workspace,
+                                        size_t workspace_bytes, const uint32_t* row_mask, const int32_t* row_group,
+                                        const int32_t* query_group, void* stream) {
+    ISC_REQUIRE(row_group && query_group);
+    if (!isc_aligned(row_group, 16) || !isc_aligned(query_group, 4) || !isc_aligned(row_mask, 4))
+        return ISC_ERR_ALIGNMENT;
+    const IscGroups g{row_mask, row_group, query_group, nullptr, Q};
+    return range(bank, dtype, N, D, queries, q_dtype, Q, ldq, min_score, index_base, norm_bound, capacity, offsets, scores,
+                 indices, needed, status, workspace, workspace_bytes, row_mask, stream, &g);
 }

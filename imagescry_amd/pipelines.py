@@ -101,17 +101,28 @@ class EmbedSearchPipeline:
     Ordering between the two streams is by events only; the host never waits inside the loop, and there is nothing to
     check afterwards: `EmbeddingBank.search` is final on the device (queries the float32 filter cannot prove are redone
     exactly by the same call).
+
+    `image_groups`: optional int64 tensor indexed by `ImageBatch.indices`, the group label of every image -- e.g. the
+    image id its cells are banked under.  Each of an image's h*w query rows then carries that label, and the bank (built
+    with `row_groups=`) skips the rows of the query's own group (`exclude_group=`): "similar cells in OTHER images".
     """
 
-    def __init__(self, *, embedding_model: EmbeddingModule, bank: EmbeddingBank, k: int = 10, overlap: bool = True) -> None:
+    def __init__(self, *, embedding_model: EmbeddingModule, bank: EmbeddingBank, k: int = 10, overlap: bool = True,
+                 image_groups: Tensor | None = None) -> None:
         if not isinstance(k, int) or isinstance(k, bool) or k < 1:
             raise ValueError(f"k must be a positive int, got {k!r}")
+        if image_groups is not None:
+            if not isinstance(image_groups, Tensor) or image_groups.dtype != torch.int64 or image_groups.ndim != 1:
+                raise TypeError("image_groups must be a 1-D int64 tensor indexed by ImageBatch.indices")
+            if bank.group_labels is None:
+                raise ValueError("image_groups needs a bank built with row_groups=")
         if embedding_model.embedding_dim != bank.dim:
             raise ValueError(f"embedder produces {embedding_model.embedding_dim}-d vectors, the bank holds {bank.dim}-d rows")
         self.embedding_model = embedding_model
         self.bank = bank
         self.k = k
         self.overlap = overlap
+        self.image_groups = image_groups
         self.exact_pass_queries: Tensor | None = None
 
     def _queries(self, emb: EmbeddingBatch) -> Tensor:
@@ -129,6 +140,25 @@ class EmbedSearchPipeline:
         gathered = torch.empty((world * src.shape[0], src.shape[1]), dtype=src.dtype, device=src.device)
         dist.all_gather_into_tensor(gathered, src, group=group)
         return gathered.to(q.device)
+
+    def _labels(self, emb: EmbeddingBatch) -> Tensor | None:
+        """The group label of every query row of `_queries` (None without `image_groups`): image b's label for each of its
+        h*w rows, in `get_flat_vectors` order; all-gathered with the queries over the ranks of a sharded bank."""
+        if self.image_groups is None:
+            return None
+        b = emb.indices.shape[0]
+        per_image = emb.get_flat_vectors().shape[0] // max(b, 1)
+        lab = self.image_groups[emb.indices.to(self.image_groups.device)].to(emb.device)
+        lab = lab.repeat_interleave(per_image)
+        group = self.bank.process_group
+        if group is None:
+            return lab
+        world = dist.get_world_size(group)
+        on_host = dist.get_backend(group) == "gloo" and lab.device.type != "cpu"
+        src = lab.cpu() if on_host else lab
+        gathered = torch.empty(world * src.shape[0], dtype=src.dtype, device=src.device)
+        dist.all_gather_into_tensor(gathered, src, group=group)
+        return gathered.to(lab.device)
 
     def _own_rows(self, t: Tensor, rows: int) -> Tensor:
         group = self.bank.process_group
@@ -169,18 +199,21 @@ class EmbedSearchPipeline:
                 with torch.cuda.stream(enc_stream):
                     emb = self.embedding_model.predict_step(batch)
                     q = self._queries(emb)
+                    labels = self._labels(emb)
                     ready = torch.cuda.Event()
                     ready.record(enc_stream)
                     rows = emb.get_flat_vectors().shape[0]
                 with torch.cuda.stream(search_stream):
                     search_stream.wait_event(ready)
                     q.record_stream(search_stream)
-                    handle = self.bank.search_async(q, self.k)
+                    if labels is not None:
+                        labels.record_stream(search_stream)
+                    handle = self.bank.search_async(q, self.k, exclude_group=labels)
             else:
                 emb = self.embedding_model.predict_step(batch)
                 q = self._queries(emb)
                 rows = emb.get_flat_vectors().shape[0]
-                handle = self.bank.search_async(q, self.k)
+                handle = self.bank.search_async(q, self.k, exclude_group=self._labels(emb))
                 if self.bank.process_group is not None:
                     handle.result()  # one stream: exchange i before search i + 1
             if pending is not None:

@@ -168,6 +168,9 @@ class EmbeddingBank:
             e.g. the output of `Embedder.predict_step`).
         index_base: global row index of local row 0 (only with `presharded=True`).
         process_group: the `torch.distributed` group the bank is sharded over (`None` = single GPU).
+        row_groups: optional integer group label of every row (e.g. its image id), sharded like `embeddings`: the full
+            `[N]` with `presharded=False`, the shard's `[N_local]` with `presharded=True`.  Searches given
+            `exclude_group=` labels per query then skip, for each query, the rows that carry its label.
     """
 
     def __init__(
@@ -179,6 +182,7 @@ class EmbeddingBank:
         index_base: int = 0,
         process_group: dist.ProcessGroup | None = None,
         presharded: bool = False,
+        row_groups: Tensor | None = None,
     ) -> None:
         if not isinstance(embeddings, Tensor) or not embeddings.dtype.is_floating_point:
             raise TypeError("embeddings must be a floating point torch.Tensor")
@@ -189,9 +193,18 @@ class EmbeddingBank:
         self.process_group = process_group
         self.world_size = dist.get_world_size(process_group) if process_group is not None else 1
         self.rank = dist.get_rank(process_group) if process_group is not None else 0
+        if row_groups is not None:
+            if not isinstance(row_groups, Tensor) or row_groups.dtype.is_floating_point or row_groups.dtype.is_complex \
+                    or row_groups.dtype == torch.bool:
+                raise TypeError("row_groups must be an integer torch.Tensor")
+            if row_groups.shape != (embeddings.shape[0],):
+                raise ValueError(f"row_groups must have shape [{embeddings.shape[0]}] (one label per row of embeddings), "
+                                 f"got {tuple(row_groups.shape)}")
         if process_group is not None and not presharded:
             lo, hi = shard_bounds(embeddings.shape[0], self.world_size, self.rank)
             embeddings = embeddings[lo:hi]
+            if row_groups is not None:
+                row_groups = row_groups[lo:hi]
             index_base = lo
         elif process_group is None and index_base != 0 and not presharded:
             raise ValueError("index_base is only meaningful for a presharded bank")
@@ -218,6 +231,14 @@ class EmbeddingBank:
         self._range_ws: Tensor | None = None  # the range search's workspace, grown on demand
         self.last_gathered_status: Tensor | None = None
         self.row_origin: Tensor | None = None  # set by from_database: (image_id, h, w) of every row
+        # row groups (`row_groups`): this rank's sorted distinct labels (int64 [G], device) and the int32 code -- the label's
+        # position among them -- of every row in the PACKED row order (`isc_row_groups_pack`)
+        self.group_labels: Tensor | None = None
+        self._row_codes: Tensor | None = None
+        if row_groups is not None:
+            labels = row_groups.to(device=self.device, dtype=torch.int64)
+            self.group_labels, codes = torch.unique(labels, sorted=True, return_inverse=True)
+            self._row_codes = self._pack_groups(codes.to(torch.int32).contiguous())
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -249,6 +270,7 @@ class EmbeddingBank:
         from imagescry_amd import storage
 
         rows, origin = storage.flat_rows(storage.read_embeddings(db, image_ids=image_ids))
+        kwargs.setdefault("row_groups", origin[:, 0])  # grouped by image: exclude_group= takes image ids
         bank = cls(rows.to(device), **kwargs)  # type: ignore[arg-type]
         bank.row_origin = origin
         return bank
@@ -390,6 +412,40 @@ class EmbeddingBank:
             return self.row_filter(mask)
         raise TypeError(f"mask must be a RowFilter or a bool tensor, got {type(mask).__name__}")
 
+    # ------------------------------------------------------------------ row groups
+    def _pack_groups(self, codes: Tensor) -> Tensor:
+        """`isc_row_groups_pack` of this rank's int32 `[N_local]` row codes: int32 `[ceil(N_local / 256) * 256]`."""
+        n = self.num_local_rows
+        if n == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device)
+        packed = torch.empty((n + 255) // 256 * 256, dtype=torch.int32, device=self.device)
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            st = lib.isc_row_groups_pack(codes.data_ptr(), n, packed.data_ptr(), _lib.stream_handle(self.device))
+        _lib.check(st, "isc_row_groups_pack")
+        return packed
+
+    def _query_codes(self, exclude_group: Tensor | None, nq: int) -> Tensor | None:
+        """The int32 `[Q]` codes of `exclude_group` labels on the bank's device: a label's position among this rank's
+        `group_labels`, -1 for a label no row of the rank carries.  Tensor ops only: no host synchronisation."""
+        if exclude_group is None:
+            return None
+        if not isinstance(exclude_group, Tensor):
+            raise TypeError(f"exclude_group must be an integer torch.Tensor, got {type(exclude_group).__name__}")
+        dt = exclude_group.dtype
+        if dt.is_floating_point or dt.is_complex or dt == torch.bool:
+            raise TypeError(f"exclude_group must be an integer tensor, got {dt}")
+        if exclude_group.shape != (nq,):
+            raise ValueError(f"exclude_group must have shape [Q] = [{nq}], got {tuple(exclude_group.shape)}")
+        if self.group_labels is None:
+            raise ValueError("exclude_group needs row groups: build the bank with row_groups= (or from_database)")
+        x = exclude_group.to(device=self.device, dtype=torch.int64)
+        labels = self.group_labels
+        if labels.numel() == 0:
+            return torch.full((nq,), -1, dtype=torch.int32, device=self.device)
+        pos = torch.searchsorted(labels, x).clamp_(max=labels.numel() - 1)
+        return torch.where(labels[pos] == x, pos, -1).to(torch.int32)
+
     # ------------------------------------------------------------------ search
     def _prepare_queries(self, queries: Tensor) -> Tensor:
         if not isinstance(queries, Tensor) or not queries.dtype.is_floating_point:
@@ -437,14 +493,16 @@ class EmbeddingBank:
 
     def _local_topk(
         self, queries: Tensor, k: int, out: tuple[Tensor, Tensor, Tensor] | None = None, lane: int = -1,
-        stream: "torch.cuda.Stream | None" = None, mask: RowFilter | None = None,
+        stream: "torch.cuda.Stream | None" = None, mask: RowFilter | None = None, groups: Tensor | None = None,
     ) -> tuple[Tensor, Tensor]:
         """Top-k of this rank's rows: `(float32 [Q, k], int64 [Q, k])` with GLOBAL row indices, final when the stream
         has run the call.  `out` optionally supplies the (scores, indices, status int32[4]) tensors to write into (the
         exchange buffer of a sharded search); `lane` / `stream`: the workspace set and the stream of an asynchronous search
         (default: the caller's current stream).  Tensors are allocated on the caller's stream whichever stream computes.
         `mask`: search the rows of a row filter only (`isc_cosine_topk_masked`); a query with fewer than k allowed rows ends
-        in the C ABI's padding (score NaN, index INT64_MAX), which the public calls map to (-inf, -1) at the very end."""
+        in the C ABI's padding (score NaN, index INT64_MAX), which the public calls map to (-inf, -1) at the very end.
+        `groups`: int32 `[Q]` query codes (`_query_codes`): query q skips the rows of its group (`isc_cosine_topk_grouped`),
+        with the masked search's padding."""
         nq = queries.shape[0]
         if out is None:
             scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
@@ -461,6 +519,9 @@ class EmbeddingBank:
                 t.record_stream(stream)
             if mask is not None:
                 mask.packed.record_stream(stream)
+            if groups is not None:
+                groups.record_stream(stream)
+                self._row_codes.record_stream(stream)
         lib = _lib.load()
         with torch.cuda.device(self.device):
             args = (
@@ -470,7 +531,11 @@ class EmbeddingBank:
                 indices.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
             )
             sh = stream.cuda_stream if stream is not None else _lib.stream_handle(self.device)
-            if mask is None:
+            if groups is not None:
+                st = lib.isc_cosine_topk_grouped(*args, None if mask is None else mask.packed.data_ptr(),
+                                                 self._row_codes.data_ptr(), groups.data_ptr(), sh)
+                _lib.check(st, "isc_cosine_topk_grouped")
+            elif mask is None:
                 st = lib.isc_cosine_topk(*args, sh)
                 _lib.check(st, "isc_cosine_topk")
             else:
@@ -479,14 +544,15 @@ class EmbeddingBank:
         self.last_status = status
         return scores, indices
 
-    def search_exhaustive(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None
-                          ) -> tuple[Tensor, Tensor]:
+    def search_exhaustive(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None,
+                          exclude_group: Tensor | None = None) -> tuple[Tensor, Tensor]:
         """The same answer from the data-independent float64 kernel (`isc_cosine_topk_exhaustive`): every score of
-        every query evaluated exactly.  Slow; the on-device reference the fast path is tested against.  `mask`: as in
-        `search`."""
+        every query evaluated exactly.  Slow; the on-device reference the fast path is tested against.  `mask`,
+        `exclude_group`: as in `search`."""
         rf = self._as_filter(mask)
         q = self._prepare_queries(queries)
         nq = q.shape[0]
+        qg = self._query_codes(exclude_group, nq)
         if self.process_group is not None:
             raise ValueError("search_exhaustive answers for one shard; merge the shards with search()")
         if not 1 <= k <= self.num_local_rows:
@@ -506,12 +572,16 @@ class EmbeddingBank:
                 self._bank.data_ptr(), code, self.num_local_rows, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
                 q.stride(0), k, self.index_base, scores.data_ptr(), indices.data_ptr(), ews.data_ptr(), ews.numel(),
             )
-            if rf is None:
+            if qg is not None:
+                st = lib.isc_cosine_topk_exhaustive_grouped(*args, None if rf is None else rf.packed.data_ptr(),
+                                                            self._row_codes.data_ptr(), qg.data_ptr(),
+                                                            _lib.stream_handle(self.device))
+            elif rf is None:
                 st = lib.isc_cosine_topk_exhaustive(*args, _lib.stream_handle(self.device))
             else:
                 st = lib.isc_cosine_topk_exhaustive_masked(*args, rf.packed.data_ptr(), _lib.stream_handle(self.device))
-        _lib.check(st, "isc_cosine_topk_exhaustive" + ("" if rf is None else "_masked"))
-        return (scores, indices) if rf is None else _unpad(scores, indices)
+        _lib.check(st, "isc_cosine_topk_exhaustive" + ("_grouped" if qg is not None else "" if rf is None else "_masked"))
+        return (scores, indices) if rf is None and qg is None else _unpad(scores, indices)
 
     def _merge_topk(self, scores: Tensor, indices: Tensor, k: int) -> tuple[Tensor, Tensor]:
         """Merge `[G, Q, kin]` partial results into `[Q, k]` by (score desc, index asc) (`isc_topk_merge`).  The two
@@ -538,7 +608,7 @@ class EmbeddingBank:
         return int(sum(counts))
 
     def search(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None,
-               check: bool = True) -> tuple[Tensor, Tensor]:
+               exclude_group: Tensor | None = None, check: bool = True) -> tuple[Tensor, Tensor]:
         """Cosine top-k of every query against the whole (possibly sharded) bank.
 
         Returns `(scores float32 [Q, k], indices int64 [Q, k])`, best first, ties by lower row index.  The call
@@ -556,15 +626,21 @@ class EmbeddingBank:
         query with fewer than k allowed rows ends in score -inf, index -1 entries.  The whole bank is streamed whatever
         the filter's density (the masked filter).
 
+        `exclude_group`: an integer `[Q]` tensor (any device) of group labels, on a bank built with `row_groups=`: query q
+        skips the rows whose label equals `exclude_group[q]` ("not my own image"), on top of `mask`.  Each query's answer
+        is the masked search of the rows it may return, bit for bit, padded as above; a label no row carries excludes
+        nothing.  The labels become codes on the device, so a grouped search stays capturable.
+
         A world-1 `search` may be captured into a CUDA / HIP graph (`torch.cuda.graph`) and replayed.  The workspace a
         capture used stays allocated for the bank's lifetime so that replays stay valid: each distinct (query bucket, k)
         captured pins one `isc_cosine_topk_workspace_bytes` buffer -- up to a few hundred MB on a large bank -- until the
         bank is dropped.
         """
         del check
-        return self._search(queries, k, lanes=False, mask=mask).result()
+        return self._search(queries, k, lanes=False, mask=mask, exclude_group=exclude_group).result()
 
-    def search_async(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None) -> SearchHandle:
+    def search_async(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None,
+                     exclude_group: Tensor | None = None) -> SearchHandle:
         """`search` that returns as soon as everything is ENQUEUED; `handle.result()` orders the caller's current stream
         behind the answer.  The local kernels of a search of up to 128 queries run on one of TWO library-owned streams
         of the device, alternately -- the bank keeps a workspace for each -- ordered behind the caller's stream as it
@@ -579,8 +655,9 @@ class EmbeddingBank:
         queries with unit inner stride are NOT copied), and writes `last_status` / `last_gathered_status` there -- so the
         caller must not overwrite the query tensor in place, nor read those status tensors, on its own stream before it
         has resolved the handle.  `search()` has no such window: everything it does is ordered on the caller's stream.
-        `mask`: as in `search` (a `RowFilter` is read on the library's stream too: keep it until the handle is resolved)."""
-        return self._search(queries, k, lanes=True, mask=mask)
+        `mask`, `exclude_group`: as in `search` (a `RowFilter` is read on the library's stream too: keep it until the handle
+        is resolved)."""
+        return self._search(queries, k, lanes=True, mask=mask, exclude_group=exclude_group)
 
     def _lane(self, cur: "torch.cuda.Stream", q: Tensor) -> tuple[int, "torch.cuda.Stream"]:
         """The next of the two search streams, ordered behind everything the caller's stream holds so far."""
@@ -598,7 +675,8 @@ class EmbeddingBank:
     # shard), and two of them sharing the GPU would stretch each other's launches.
     _LANE_MAX_QUERIES = 128
 
-    def _search(self, queries: Tensor, k: int, lanes: bool, mask: "RowFilter | Tensor | None" = None) -> SearchHandle:
+    def _search(self, queries: Tensor, k: int, lanes: bool, mask: "RowFilter | Tensor | None" = None,
+                exclude_group: Tensor | None = None) -> SearchHandle:
         rf = self._as_filter(mask)
         if not isinstance(k, int) or isinstance(k, bool):
             raise TypeError(f"k must be an int, got {type(k).__name__}")
@@ -608,6 +686,11 @@ class EmbeddingBank:
             raise ValueError(f"k must be <= {_lib.ISC_TOPK_MAX_K}, got {k}")
         q = self._prepare_queries(queries)
         nq = q.shape[0]
+        qg = self._query_codes(exclude_group, nq)
+        # a filtered search (row filter and / or groups) pads short answers; the grouped kernels get the query codes
+        filt: dict[str, object] = {} if rf is None else {"mask": rf}
+        if qg is not None:
+            filt["groups"] = qg
         lanes = lanes and nq <= self._LANE_MAX_QUERIES
         if self.process_group is None:
             if k > self.num_local_rows:
@@ -615,11 +698,11 @@ class EmbeddingBank:
             if nq == 0:
                 return SearchHandle(torch.empty((0, k), dtype=torch.float32, device=self.device),
                                     torch.empty((0, k), dtype=torch.int64, device=self.device))
-            if rf is not None:  # the padding of a masked search becomes (-inf, -1) on the stream that computed it
+            if filt:  # the padding of a filtered search becomes (-inf, -1) on the stream that computed it
                 if not (lanes and self.device.type == "cuda"):
-                    return SearchHandle(*_unpad(*self._local_topk(q, k, mask=rf)))
+                    return SearchHandle(*_unpad(*self._local_topk(q, k, **filt)))
                 lane, ls = self._lane(torch.cuda.current_stream(self.device), q)
-                out_s, out_i = self._local_topk(q, k, lane=lane, stream=ls, mask=rf)
+                out_s, out_i = self._local_topk(q, k, lane=lane, stream=ls, **filt)
                 with torch.cuda.stream(ls):
                     out_s, out_i = _unpad(out_s, out_i)
                 done = torch.cuda.Event()
@@ -671,24 +754,22 @@ class EmbeddingBank:
         status = xbuf[off_s:].view(torch.int32)
         if kl < k:  # a shard with fewer rows than k: pad with entries that rank after every real candidate
             # (a masked search pads with the C ABI's (NaN, INT64_MAX), which ranks after NaN-scored rows of other shards too)
-            part_s.fill_(-math.inf if rf is None else math.nan)
+            part_s.fill_(-math.inf if not filt else math.nan)
             part_i.fill_(_PAD_INDEX)
             status.zero_()
             if kl > 0:
-                s, i = self._local_topk(q, kl) if rf is None else self._local_topk(q, kl, mask=rf)
+                s, i = self._local_topk(q, kl, **filt)
                 part_s[:, :kl] = s
                 part_i[:, :kl] = i
-        elif rf is None:
-            self._local_topk(q, k, out=(part_s, part_i, status), lane=lane, stream=ls)
         else:
-            self._local_topk(q, k, out=(part_s, part_i, status), lane=lane, stream=ls, mask=rf)
+            self._local_topk(q, k, out=(part_s, part_i, status), lane=lane, stream=ls, **filt)
 
         def exchange() -> tuple[Tensor, Tensor, Tensor, Tensor]:
             gathered = self._all_gather_bytes(xbuf)
             all_s = gathered[:, : 4 * nq * k].view(torch.float32).view(self.world_size, nq, k)
             all_i = gathered[:, off_i:off_s].view(torch.int64).view(self.world_size, nq, k)
             out_s, out_i = self._merge_topk(all_s, all_i, k)
-            if rf is not None:
+            if filt:
                 out_s, out_i = _unpad(out_s, out_i)
             return out_s, out_i, gathered, gathered[:, off_s:].view(torch.int32)  # [G, 4]: every shard's diagnostics
 
@@ -739,8 +820,8 @@ class EmbeddingBank:
             raise ValueError("min_score is NaN")
         return torch.full((nq,), float(min_score), dtype=torch.float32, device=self.device)
 
-    def _range_call(self, q: Tensor, thr: Tensor, capacity: int, mask: RowFilter | None = None
-                    ) -> tuple[int, RangeResult, Tensor]:
+    def _range_call(self, q: Tensor, thr: Tensor, capacity: int, mask: RowFilter | None = None,
+                    groups: Tensor | None = None) -> tuple[int, RangeResult, Tensor]:
         """One `isc_cosine_range` call: (needed, result -- valid only when needed <= capacity --, status int32[4])."""
         lib = _lib.load()
         nq = q.shape[0]
@@ -764,15 +845,19 @@ class EmbeddingBank:
                 offsets.data_ptr(), scores.data_ptr(), indices.data_ptr(), needed.data_ptr(), status.data_ptr(),
                 ws.data_ptr(), ws.numel(),
             )
-            if mask is None:
+            if groups is not None:
+                st = lib.isc_cosine_range_grouped(*args, None if mask is None else mask.packed.data_ptr(),
+                                                  self._row_codes.data_ptr(), groups.data_ptr(),
+                                                  _lib.stream_handle(self.device))
+            elif mask is None:
                 st = lib.isc_cosine_range(*args, _lib.stream_handle(self.device))
             else:
                 st = lib.isc_cosine_range_masked(*args, mask.packed.data_ptr(), _lib.stream_handle(self.device))
-        _lib.check(st, "isc_cosine_range" + ("" if mask is None else "_masked"))
+        _lib.check(st, "isc_cosine_range" + ("_grouped" if groups is not None else "" if mask is None else "_masked"))
         return int(needed.item()), RangeResult(offsets, scores, indices), status
 
-    def _local_range(self, queries: Tensor, min_score: Tensor, max_results: int, mask: RowFilter | None = None
-                     ) -> tuple[int, RangeResult | None]:
+    def _local_range(self, queries: Tensor, min_score: Tensor, max_results: int, mask: RowFilter | None = None,
+                     groups: Tensor | None = None) -> tuple[int, RangeResult | None]:
         """Range search of this rank's rows with GLOBAL row indices: `(total, result)`; `result` is None when `total`
         exceeds `max_results` (then `total` is the exact row count, or, when even counting would need more than twice
         `max_results` entries, the filter's candidate count, an upper bound of it)."""
@@ -784,12 +869,13 @@ class EmbeddingBank:
             return 0, empty
         limit = min(max(max_results, 1), 0x7FFFFFFF)
         cap = min(max(1 << 16, self._RANGE_GUESS_PER_QUERY * nq), limit)
-        needed, res, status = self._range_call(queries, min_score, cap, mask)
+        grp = {} if groups is None else {"groups": groups}
+        needed, res, status = self._range_call(queries, min_score, cap, mask, **grp)
         if needed > cap:
             if needed > 2 * limit or needed > 0x7FFFFFFF:
                 self.last_range_status = status
                 return needed, None
-            needed, res, status = self._range_call(queries, min_score, needed, mask)
+            needed, res, status = self._range_call(queries, min_score, needed, mask, **grp)
         self.last_range_status = status
         total = int(res.offsets[-1].item())
         if total > max_results:
@@ -797,7 +883,7 @@ class EmbeddingBank:
         return total, RangeResult(res.offsets, res.scores[:total], res.indices[:total])
 
     def search_range(self, queries: Tensor, min_score: "float | Tensor", *, max_results: int = 1 << 26,
-                     mask: "RowFilter | Tensor | None" = None) -> RangeResult:
+                     mask: "RowFilter | Tensor | None" = None, exclude_group: Tensor | None = None) -> RangeResult:
         """Every row whose cosine score against a query is >= `min_score` (a float, or a float32 `[Q]` tensor of
         per-query thresholds): a `RangeResult` whose query q holds its rows ordered by (score descending, row index
         ascending), indices global.  Exact: the scores and the membership are those of the top-k (`search`), so with
@@ -811,14 +897,18 @@ class EmbeddingBank:
         [1] queries answered by the float64 sweep, [2] float bits of the largest filter error in units of its bound.
         A sharded bank searches its shard on every rank, all-gathers the per-rank totals and then the rows, and every
         rank merges them into the answer of the unsharded bank.  `mask`: as in `search` -- the result without the rows the
-        filter disallows, bit for bit."""
+        filter disallows, bit for bit.  `exclude_group`: as in `search` -- query q's result without the rows of its group."""
         rf = self._as_filter(mask)
         q = self._prepare_queries(queries)
         nq = q.shape[0]
+        qg = self._query_codes(exclude_group, nq)
         thr = self._range_thresholds(min_score, nq)
         if isinstance(max_results, bool) or not isinstance(max_results, int) or max_results < 0:
             raise ValueError(f"max_results must be a non-negative int, got {max_results!r}")
-        total, res = self._local_range(q, thr, max_results) if rf is None else self._local_range(q, thr, max_results, rf)
+        if qg is not None:
+            total, res = self._local_range(q, thr, max_results, rf, groups=qg)
+        else:
+            total, res = self._local_range(q, thr, max_results) if rf is None else self._local_range(q, thr, max_results, rf)
         if self.process_group is None:
             if res is None:
                 raise ValueError(f"search_range found {total} rows, more than max_results={max_results}")

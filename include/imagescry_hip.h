@@ -166,6 +166,14 @@ int isc_row_mask_words(int64_t N, size_t* words);
  *                  norm_bound); NULL = not counted */
 int isc_row_mask_pack(const uint8_t* allow, int64_t N, uint32_t* packed_mask, int64_t* allowed_count, void* stream);
 
+/* Row group codes of the grouped searches (isc_cosine_topk_grouped, isc_cosine_topk_exhaustive_grouped,
+ * isc_cosine_range_grouped), in one launch (no host synchronisation):
+ *   codes          int32 [N] in ORIGINAL row order, 4-byte aligned: the group code of every row, >= 0 (a negative code puts
+ *                  the row in no group: no query excludes it)
+ *   packed_codes   int32 [ceil(N / 256) * 256] in PACKED row order (isc_bank_permutation), 16-byte aligned: written
+ *                  entirely, the padding of the last tile included */
+int isc_row_groups_pack(const int32_t* codes, int64_t N, int32_t* packed_codes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Encoder blocks (float32, NHWC activations, KRSC weights)
  * ------------------------------------------------------------------------------------------- */
@@ -376,6 +384,20 @@ int isc_cosine_topk_masked(const void* bank, int dtype, int64_t N, int D, const 
                            int64_t* out_indices, int32_t* status, void* workspace, size_t workspace_bytes,
                            const uint32_t* row_mask, void* stream);
 
+/* Per-query group exclusion: isc_cosine_topk_masked where query q may return row r iff row_mask allows r and the code of r
+ * differs from q's, bit for bit per query -- the answer of a masked search of the rows q may return.  Same arguments,
+ * limits, workspace (isc_cosine_topk_workspace_bytes) and padding, plus
+ *   row_mask     the packed row filter of this bank (isc_row_mask_pack), or NULL: every row is allowed
+ *   row_group    int32, the packed row codes of this bank (isc_row_groups_pack), 16-byte aligned
+ *   query_group  int32 [Q], 4-byte aligned: the code of every query; a code < 0 matches no row
+ * Calls with Q > ISC_SEARCH_PASS_QUERIES offset query_group per pass as they do the queries.  The workspace and capture
+ * conventions are those of isc_cosine_topk: the workspace's contents on entry do not matter, the call synchronises nothing
+ * and may be captured; a graph replays with the codes the buffers then hold. */
+int isc_cosine_topk_grouped(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
+                            int64_t ldq, int k, int64_t index_base, const float* norm_bound, float* out_scores,
+                            int64_t* out_indices, int32_t* status, void* workspace, size_t workspace_bytes,
+                            const uint32_t* row_mask, const int32_t* row_group, const int32_t* query_group, void* stream);
+
 /* Same contract and the same limits, data-independent cost: every score of every query is evaluated in float64
  * (vector FMA, no matrix cores, about one bank stream per four queries).  The kernel isc_cosine_topk falls back to
  * per query; exported as the reference implementation of the search on the device. */
@@ -390,6 +412,14 @@ int isc_cosine_topk_exhaustive_masked(const void* bank, int dtype, int64_t N, in
                                       int Q, int64_t ldq, int k, int64_t index_base, float* out_scores,
                                       int64_t* out_indices, void* workspace, size_t workspace_bytes,
                                       const uint32_t* row_mask, void* stream);
+
+/* isc_cosine_topk_exhaustive with isc_cosine_topk_grouped's per-query exclusion, row filter (NULL: every row) and padding;
+ * the workspace of isc_cosine_topk_exhaustive_workspace_bytes, with the same conventions. */
+int isc_cosine_topk_exhaustive_grouped(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,
+                                       int Q, int64_t ldq, int k, int64_t index_base, float* out_scores,
+                                       int64_t* out_indices, void* workspace, size_t workspace_bytes,
+                                       const uint32_t* row_mask, const int32_t* row_group, const int32_t* query_group,
+                                       void* stream);
 
 /* Exact cosine range search: for every query, EVERY row with score(q, b) >= min_score[q], with the score of
  * isc_cosine_topk (the query rounded to the bank dtype first; float32(dot_f64(q, b) / max(||q||_2, 1e-12))).  NaN scores
@@ -425,6 +455,16 @@ int isc_cosine_range_masked(const void* bank, int dtype, int64_t N, int D, const
                             int64_t capacity, int64_t* offsets, float* scores, int64_t* indices, int64_t* needed,
                             int32_t* status, void* workspace, size_t workspace_bytes, const uint32_t* row_mask,
                             void* stream);
+
+/* isc_cosine_range where query q may return row r iff row_mask (NULL: every row) allows r and the codes of r and q differ
+ * (isc_cosine_topk_grouped): the ungrouped result without those rows, bit for bit.  A zero query with t <= 0 returns its
+ * allowed rows in row order.  Same arguments, limits, workspace (isc_cosine_range_workspace_bytes) and conventions;
+ * `needed` counts the rows the queries may return only. */
+int isc_cosine_range_grouped(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
+                             int64_t ldq, const float* min_score, int64_t index_base, const float* norm_bound,
+                             int64_t capacity, int64_t* offsets, float* scores, int64_t* indices, int64_t* needed,
+                             int32_t* status, void* workspace, size_t workspace_bytes, const uint32_t* row_mask,
+                             const int32_t* row_group, const int32_t* query_group, void* stream);
 
 /* Merge G partial results (e.g. one per bank shard after the all-gather) into the final top-k by
  * (score descending, index ascending): scores float [G,Q,kin], indices int64 [G,Q,kin] -> [Q,kout], kout <= G*kin <= 4096.
