@@ -188,6 +188,25 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "isc_topk_merge": (
         c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p]
     ),
+    "isc_cosine_topk_collapse_workspace_bytes": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "isc_cosine_topk_collapse": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    ),
+    "isc_cosine_topk_exhaustive_collapse_workspace_bytes": (
+        c_int, [c_int, c_int64, c_int, c_int, c_int, POINTER(c_size_t)]
+    ),
+    "isc_cosine_topk_exhaustive_collapse": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p,
+         c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "isc_topk_merge_groups": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+         c_void_p, c_void_p],
+    ),
 }
 
 _lib: ctypes.CDLL | None = None

@@ -137,16 +137,26 @@ constexpr int first_ratio() { return 16; }
 constexpr int sample_tiles_cap() { return 0; }
 #endif
 
-Plan make_plan(int64_t n, int q, int k) {
+// Collapsed search (isc_cosine_topk_collapse, group_rows = the most rows one group has, >= 1): the slot maxima of the sample
+// level bound a workgroup's kp-th best ROW, which says nothing about its kp-th best GROUP, so the sample level keeps every
+// score (nslots = 0, 16 tiles); kp is at least COLLAPSE_MIN_KP (the 256-query sample tail holds 64 entries per query at
+// kp = 16, fewer than the 256 scores of a tile); and a level's survivors per unit of ratio are up to kp groups of
+// min(group_rows, COLLAPSE_ROWS_CAP) rows each, not kp rows.  0 = the row search.
+constexpr int COLLAPSE_MIN_KP = 32;
+constexpr int COLLAPSE_ROWS_CAP = 64;
+constexpr int COLLAPSE_GROUPS = 4096;  // distinct groups a selection can hold (GroupHash)
+
+Plan make_plan(int64_t n, int q, int k, int group_rows = 0) {
     Plan p;
     p.qb = q < QBATCH ? q : QBATCH;
     p.tnq = p.qb <= 64 ? 64 : p.qb <= SMALL_Q ? 128 : 256;
     if (forced_tile() == 64 || forced_tile() == 128 || forced_tile() == 256) p.tnq = forced_tile();
     p.segs_per_chunk = (8 / (p.tnq / 64)) * 4;
     p.kp = plan_kp(k);
+    if (group_rows > 0 && p.kp < COLLAPSE_MIN_KP) p.kp = COLLAPSE_MIN_KP;
     p.qtiles = isc_ceil_div(p.qb, p.tnq);
     p.qpad = p.qtiles * p.tnq;
-    p.nslots = p.kp <= 16 ? 32 : p.kp <= 32 ? 64 : p.kp <= 64 ? 128 : 0;
+    p.nslots = group_rows > 0 ? 0 : p.kp <= 16 ? 32 : p.kp <= 32 ? 64 : p.kp <= 64 ? 128 : 0;
     int wgs = TARGET_WGS / p.qtiles;
     if (wgs < 1) wgs = 1;
     const int64_t ntiles_all = isc_ceil_div<int64_t>(n, TM);
@@ -180,8 +190,11 @@ Plan make_plan(int64_t n, int q, int k) {
         // every search of a bank that uses the full ratio paid a second pass for it.  The list now holds the mean plus
         // eight standard deviations (kp = 16: ratio 171, P < 1e-8).
         int64_t budget = (int64_t)((double)QCAP * p.kp / (p.kp + 8.0 * sqrt((double)p.kp)));
+        // collapsed: the survivors' groups must fit the selection's hash (COLLAPSE_GROUPS slots) as well
+        if (group_rows > 0) budget = (int64_t)((double)COLLAPSE_GROUPS * p.kp / (p.kp + 8.0 * sqrt((double)p.kp)));
         if (nseg * CAP / 8 < budget) budget = nseg * CAP / 8;
-        int64_t ratio = 1 + budget / p.kp;
+        const int64_t unit = (int64_t)p.kp * (group_rows > COLLAPSE_ROWS_CAP ? COLLAPSE_ROWS_CAP : group_rows > 0 ? group_rows : 1);
+        int64_t ratio = 1 + budget / unit;
         // 256-query shape with ONE query tile (128 < Q <= 256): the level after the sample would be the whole bank on
         // the sample's weak threshold -- a wave's ballot over 128 rows x 16 queries trips with probability
         // 1 - exp(-2048 kp / rows seen), 39 % after 65 536 rows, and every trip is a scan of the block.  A short
@@ -2123,4 +2136,575 @@ extern "C" int isc_cosine_topk_grouped(const void* bank, int dtype, int64_t N, i
     const IscGroups g{row_mask, row_group, query_group, nullptr, Q};
     return topk(bank, dtype, N, D, queries, q_dtype, Q, ldq, k, index_base, norm_bound, out_scores, out_indices, status,
                 workspace, workspace_bytes, row_mask, stream, &g);
+}
+
+// ==== collapsed search: the k best GROUPS per query (isc_cosine_topk_collapse) =======================================
+// The row pipeline above with group-aware stages ("Collapsed search"):
+//   sample level        nslots = 0: every score of 16 tiles is a candidate (make_plan);
+//   filter levels       unchanged (the grouped instantiations, with no query excluded when the caller gives no codes);
+//   k_select_groups     the candidates' groups in an LDS hash on the code: per group its LEADER (best filter key), its SIB
+//                       (best filter key of its other rows) and SIB3 (best filter score of the rest); the carried list is
+//                       the kp best leaders, each with its sib and sib3 (a displaced leader is a candidate row like any
+//                       other); tau <- the kp-th leader's filter score;
+//   k_final_groups      the carried leaders and sibs re-scored in float64, groups ranked by the better of the two; proven
+//                       when the kp-th leader's bound is below the k-th group score and, per carried group, the bound of
+//                       its sib3 is below its own score (first k groups) or the k-th group score (the others);
+//   k_final2_groups     the redo: every row of the redo filter re-scored in float64 and collapsed by group;
+//   k_exact_collapse    (search_exact.hip) the exhaustive float64 pass with per-wave lists of distinct groups.
+namespace {
+
+constexpr int GH = COLLAPSE_GROUPS;  // hash slots of k_select_groups / k_final_groups / k_final2_groups
+constexpr int GH_PER = GH / SEL_THREADS;
+constexpr int GH_EMPTY = INT32_MIN;
+static_assert(GH % SEL_THREADS == 0 && GH_PER <= SEL_PER && GH == 4096, "hash slots per thread; 12-bit hash");
+
+// Per group: its leader, its SIB (the best filter key of its other rows, re-scored exactly by k_final_groups) and SIB3 (the
+// best filter score of the rest).  96 KiB: with the selection's 21 KiB one workgroup per CU (k_select runs four).
+struct GroupHash {
+    int code[GH];                          // GH_EMPTY or a group code
+    unsigned long long lead[GH];           // best key of the group (0: none)
+    unsigned long long sib[GH];            // best key of its other rows (0: none)
+    unsigned sib3[GH];                     // score bits (isc_score_bits) of the best filter score of the rest, 0: none
+    unsigned long long tsib[ISC_TOPK_MAX_K + 8];  // sib / sib3 / code of the selected leaders, by rank
+    unsigned tsib3[ISC_TOPK_MAX_K + 8];
+    int tcode[ISC_TOPK_MAX_K + 8];
+    int fail;
+};
+
+__device__ __forceinline__ int gh_insert(GroupHash& gh, int code) {
+    unsigned h = ((unsigned)code * 2654435761u) >> 20;  // 12 bits
+    for (int probe = 0; probe < GH; ++probe) {
+        const int old = atomicCAS(&gh.code[h], GH_EMPTY, code);
+        if (old == GH_EMPTY || old == code) return (int)h;
+        h = (h + 1) & (GH - 1);
+    }
+    return -1;
+}
+
+__device__ void gh_clear(GroupHash& gh) {
+    for (int i = threadIdx.x; i < GH; i += SEL_THREADS) {
+        gh.code[i] = GH_EMPTY;
+        gh.lead[i] = 0ull;
+        gh.sib[i] = 0ull;
+        gh.sib3[i] = 0u;
+    }
+    if (threadIdx.x == 0) gh.fail = 0;
+}
+
+// the best kp leaders of the hash into sh.topk (best first), their sib, sib3 and code into gh.tsib / tsib3 / tcode;
+// -1: overflow
+__device__ int gh_select(SelShared& sh, GroupHash& gh, int kp) {
+    const int tid = threadIdx.x;
+    unsigned long long lk[SEL_PER + 1];
+#pragma unroll
+    for (int j = 0; j <= SEL_PER; ++j) lk[j] = j < GH_PER ? gh.lead[tid + SEL_THREADS * j] : 0ull;
+    const int n = wg_select_keys(sh, lk, kp);
+    if (n <= 0) return n;
+    const unsigned long long last = sh.topk[n - 1];
+#pragma unroll
+    for (int j = 0; j < GH_PER; ++j)
+        if (lk[j] != 0ull && lk[j] >= last) {  // a selected leader (leaders are distinct keys): its rank by bisection
+            int lo = 0, hi = n - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (sh.topk[mid] > lk[j]) lo = mid + 1;
+                else hi = mid;
+            }
+            gh.tsib[lo] = gh.sib[tid + SEL_THREADS * j];
+            gh.tsib3[lo] = gh.sib3[tid + SEL_THREADS * j];
+            gh.tcode[lo] = gh.code[tid + SEL_THREADS * j];
+        }
+    __syncthreads();
+    return n;
+}
+
+// The level's survivors plus the carried leaders and sibs (and sib3s) -> the best kp leaders by (filter score desc, packed
+// row asc) in sh.topk, with gh.tsib / tsib3 / tcode.  A displaced leader is a candidate like any other row: it becomes its
+// group's sib, or counts towards its sib3.  -1: a buffer would overflow (the caller marks the query).
+template <int SPEC>
+__device__ int wg_select_groups(SelShared& sh, GroupHash& gh, int q, int kp, const int32_t* __restrict__ qcount,
+                                const Cand* __restrict__ qlist, const float* __restrict__ carry_s,
+                                const int32_t* __restrict__ carry_r, const unsigned long long* __restrict__ carry_sib,
+                                const uint32_t* __restrict__ carry_sib3, const int32_t* __restrict__ carry_n,
+                                const int32_t* __restrict__ row_group, int64_t nrows) {
+    const int tid = threadIdx.x;
+    const Cand* src = qlist + (size_t)q * QCAP;
+    const int from_list = min(qcount[q], QCAP);
+    const int carried = min(carry_n[q], kp);
+    gh_clear(gh);
+    constexpr int NK = SEL_PER + 2;  // the list's entries, then the carried leader and the carried sib
+    unsigned long long key[NK];
+    unsigned csib3 = 0u;
+    {
+        const unsigned long long* raw = reinterpret_cast<const unsigned long long*>(src);
+#pragma unroll
+        for (int j = 0; j < SPEC; ++j) key[j] = raw[tid + SEL_THREADS * j];
+        if constexpr (SPEC < SEL_PER) {
+            if (from_list > SPEC * SEL_THREADS) {
+#pragma unroll
+                for (int j = SPEC; j < SEL_PER; ++j) key[j] = raw[tid + SEL_THREADS * j];
+            } else {
+#pragma unroll
+                for (int j = SPEC; j < SEL_PER; ++j) key[j] = 0ull;
+            }
+        }
+        const int ci = min(tid, kp - 1);
+        const float cs = carry_s[(size_t)q * kp + ci];
+        const int cr = carry_r[(size_t)q * kp + ci];
+        csib3 = tid < carried ? carry_sib3[(size_t)q * kp + ci] : 0u;
+        key[SEL_PER + 1] = tid < carried ? carry_sib[(size_t)q * kp + ci] : 0ull;
+#pragma unroll
+        for (int j = 0; j < SEL_PER; ++j) {
+            const Cand e{__uint_as_float((unsigned)key[j]), (int)(unsigned)(key[j] >> 32)};
+            key[j] = tid + SEL_THREADS * j < from_list ? isc_make_key(e.s, e.row) : 0ull;
+        }
+        key[SEL_PER] = tid < carried ? isc_make_key(cs, cr) : 0ull;
+    }
+    __syncthreads();  // the hash is clear
+    int slot[NK];
+    bool fail = false;
+#pragma unroll
+    for (int j = 0; j < NK; ++j) {
+        slot[j] = -1;
+        if (key[j] != 0ull) {
+            const int row = isc_key_row(key[j]);
+            const int s = (unsigned)row < (unsigned)nrows ? gh_insert(gh, row_group[row]) : -1;
+            if (s < 0) {
+                fail = true;
+            } else {
+                slot[j] = s;
+                atomicMax(&gh.lead[s], key[j]);
+            }
+        }
+    }
+    if (csib3 != 0u && slot[SEL_PER] >= 0) atomicMax(&gh.sib3[slot[SEL_PER]], csib3);
+    if (fail) gh.fail = 1;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NK; ++j)
+        if (slot[j] >= 0 && key[j] != gh.lead[slot[j]]) atomicMax(&gh.sib[slot[j]], key[j]);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NK; ++j)
+        if (slot[j] >= 0 && key[j] != gh.lead[slot[j]] && key[j] != gh.sib[slot[j]])
+            atomicMax(&gh.sib3[slot[j]], (unsigned)(key[j] >> 32));
+    __syncthreads();
+    if (gh.fail) return -1;
+    return gh_select(sh, gh, kp);
+}
+
+// between two levels: carried leaders, their sibs and tau of every query
+template <int SPEC>
+__global__ __launch_bounds__(SEL_THREADS) void k_select_groups(int32_t* __restrict__ qcount, const Cand* __restrict__ qlist,
+                                                               int kp, float* __restrict__ tau, float* __restrict__ carry_s,
+                                                               int32_t* __restrict__ carry_r,
+                                                               unsigned long long* __restrict__ carry_sib,
+                                                               uint32_t* __restrict__ carry_sib3,
+                                                               int32_t* __restrict__ carry_n, int32_t* __restrict__ qflag,
+                                                               const int32_t* __restrict__ row_group, int64_t nrows) {
+    __shared__ SelShared sh;
+    __shared__ GroupHash gh;
+    const int q = blockIdx.x;
+    const int n = wg_select_groups<SPEC>(sh, gh, q, kp, qcount, qlist, carry_s, carry_r, carry_sib, carry_sib3, carry_n,
+                                         row_group, nrows);
+    const int tid = threadIdx.x;
+    if (n < 0) {  // as k_select: nothing more survives, k_final_groups lists the query
+        if (tid == 0) {
+            qflag[q] = 1;
+            tau[q] = INFINITY;
+            carry_n[q] = 0;
+            qcount[q] = 0;
+        }
+        return;
+    }
+    if (tid < n) {
+        const unsigned long long key = sh.topk[tid];
+        const float sc = isc_key_score(key);
+        carry_s[(size_t)q * kp + tid] = sc;
+        carry_r[(size_t)q * kp + tid] = isc_key_row(key);
+        carry_sib[(size_t)q * kp + tid] = gh.tsib[tid];
+        carry_sib3[(size_t)q * kp + tid] = gh.tsib3[tid];
+        if (tid == kp - 1) tau[q] = sc;
+    }
+    if (tid == 0) {
+        carry_n[q] = n;
+        qcount[q] = 0;
+    }
+}
+
+// One workgroup per query: last group selection, exact float64 re-score of every carried leader and sib, group order,
+// output, and the guard.  A group's exact key is the better of its leader's and its sib's.  Every row the filter dropped
+// has a filter score <= T, the kp-th carried leader's; every other carried row of a group has a filter score <= its sib3.
+// A filter score A of a row with exact dot E has E <= A + eps, and float32 rounding is monotone, so the answer stands when
+//     float32((T + eps) / ||q||) < the k-th group score         (no dropped row reaches the first k groups)
+//     float32((sib3 + eps) / ||q||) < the group's score          (first k groups: no other row of it is better)
+//                                   < the k-th group score       (the other groups: none of their rows gets in)
+// all strict (a tie with a lower row forces the redo).  A query that carries fewer than kp leaders without an overflow
+// has had every row it may return as a candidate (tau stayed -inf), so only the sib3 conditions apply.
+template <typename T, int SPEC>
+__global__ __launch_bounds__(SEL_THREADS) void k_final_groups(
+    const unsigned char* __restrict__ bank, int ks, const unsigned char* __restrict__ qpacked, int tnq, int kp, int k,
+    IscPerm pm, int64_t index_base, const float* __restrict__ norm_bound, const int32_t* __restrict__ qcount,
+    const Cand* __restrict__ qlist, const float* __restrict__ carry_s, const int32_t* __restrict__ carry_r,
+    const unsigned long long* __restrict__ carry_sib, const uint32_t* __restrict__ carry_sib3,
+    const int32_t* __restrict__ carry_n, const int32_t* __restrict__ qflag, const int32_t* __restrict__ row_group,
+    float* __restrict__ out_s, int64_t* __restrict__ out_i, int32_t* __restrict__ out_c, RedoLists rl,
+    int32_t* __restrict__ status) {
+    constexpr int MAXG = ISC_TOPK_MAX_K + 8;
+    __shared__ SelShared sh;
+    __shared__ GroupHash gh;
+    __shared__ double exact_dot[2 * MAXG];  // [0, nc): the leaders, [MAXG, MAXG + nc): their sibs
+    __shared__ unsigned long long gkey[MAXG];  // exact key of each carried group
+    __shared__ int rank_sh[MAXG];
+    __shared__ double qnorm_sh;
+    __shared__ float kth_sh;
+    __shared__ int slot_sh;
+    const int q = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int n = wg_select_groups<SPEC>(sh, gh, q, kp, qcount, qlist, carry_s, carry_r, carry_sib, carry_sib3, carry_n,
+                                         row_group, pm.n);
+    bool redo = n < 0 || qflag[q] != 0;
+    const int nc = n < 0 ? 0 : n;
+
+    const unsigned char* qrow_base = qpacked + ((size_t)(q / tnq) * ks * tnq + (q % tnq)) * ISC_KSTEP_BYTES;
+    if (tid < 64) {
+        const double nn = wave_query_norm<T>(qrow_base, ks, tnq);
+        if (tid == 0) qnorm_sh = sqrt(nn);
+    }
+    exact_dots<T>(bank, ks, qrow_base, tnq, 2 * nc, pm.n,
+                  [&](int c) { return c < nc ? isc_key_row(sh.topk[c]) : gh.tsib[c - nc] ? isc_key_row(gh.tsib[c - nc]) : -1; },
+                  [&](int c, double dot) { exact_dot[c < nc ? c : MAXG + c - nc] = dot; });
+    __syncthreads();
+    const double qnorm = qnorm_sh;
+    const double denom = fmax(qnorm, 1e-12);
+    const double bmax = norm_bound ? (double)*norm_bound : 1.001;
+
+    // a zero or non-finite query ties every row: the exhaustive pass orders the groups by their first row
+    if ((qnorm == 0.0 || !(qnorm <= 1.7e308)) && bmax <= 1.7e308) {
+        if (tid == 0) {
+            rl.x_list[atomicAdd(rl.x_count, 1)] = q;
+            atomicAdd(&status[3], 1);
+        }
+        return;
+    }
+
+    if (tid < nc) {
+        const int row = isc_key_row(sh.topk[tid]);
+        if ((unsigned)row >= (unsigned)pm.n) redo = true;  // cannot happen; never trust such an entry
+        unsigned long long best =
+            (unsigned)row < (unsigned)pm.n ? isc_make_key((float)(exact_dot[tid] / denom), (int)isc_perm_orig(pm, row)) : 0ull;
+        const unsigned long long sib = gh.tsib[tid];
+        if (sib != 0ull) {
+            const int srow = isc_key_row(sib);
+            if ((unsigned)srow < (unsigned)pm.n) {
+                const unsigned long long sk =
+                    isc_make_key((float)(exact_dot[MAXG + tid] / denom), (int)isc_perm_orig(pm, srow));
+                best = sk > best ? sk : best;
+            } else {
+                redo = true;
+            }
+        }
+        gkey[tid] = best;
+    }
+    if (tid == 0) kth_sh = __uint_as_float(0x7fc00000u);
+    __syncthreads();
+    const double eps = (double)(ks * (ISC_KSTEP_BYTES / (int)sizeof(T))) * (1.0 / 8388608.0) * qnorm * bmax;
+    const bool filter_trusted = qnorm >= 1e-30 && qnorm * bmax <= 1e37;
+    if (tid < nc) {
+        const unsigned long long mykey = gkey[tid];
+        int rank = 0;
+        for (int j = 0; j < nc; ++j) rank += gkey[j] > mykey ? 1 : 0;
+        rank_sh[tid] = rank;
+        if (rank < k) {
+            out_s[(size_t)q * k + rank] = isc_key_score(mykey);
+            out_i[(size_t)q * k + rank] = (int64_t)isc_key_row(mykey) + index_base;
+            out_c[(size_t)q * k + rank] = gh.tcode[tid];
+        }
+        if (rank == k - 1) kth_sh = isc_key_score(mykey);
+        if (eps > 0.0) {
+            const float ratio = (float)(fabs((double)isc_key_score(sh.topk[tid]) - exact_dot[tid]) / eps);
+            if (ratio == ratio) atomicMax(reinterpret_cast<unsigned*>(&status[2]), __float_as_uint(ratio));
+        }
+    }
+    if (tid >= nc && tid < k) {  // fewer groups than k (a redo below rewrites the whole row)
+        out_s[(size_t)q * k + tid] = __uint_as_float(0x7fc00000u);
+        out_i[(size_t)q * k + tid] = INT64_MAX;
+        out_c[(size_t)q * k + tid] = -1;
+    }
+    __syncthreads();
+    if (tid < nc && gh.tsib3[tid] != 0u) {  // the sib3 conditions
+        const float sf = isc_key_score((unsigned long long)gh.tsib3[tid] << 32);
+        const float ub = (float)(((double)sf + eps) / denom);
+        const float lim = rank_sh[tid] < k ? isc_key_score(gkey[tid]) : kth_sh;
+        if (!(ub < lim)) redo = true;
+    }
+    redo = __syncthreads_or(redo ? 1 : 0) != 0;
+    if (tid == 0) {
+        slot_sh = -1;
+        if (!filter_trusted) redo = true;
+        if (!redo && nc >= kp) {
+            const float t = isc_key_score(sh.topk[kp - 1]);  // every dropped row's filter score is <= t
+            const float bound = (float)(((double)t + eps) / denom);
+            redo = !(bound < kth_sh);
+        }
+        if (redo) {
+            atomicAdd(&status[1], 1);
+            // tau2 as in k_final, from the k-th GROUP score: at least k groups have a row that scores at least that much,
+            // so the leader of every group of the answer passes "A > tau2"
+            const float kth = kth_sh;
+            double t2 = (double)__uint_as_float(0x7fc00000u);
+            if (filter_trusted && kth == kth && fabsf(kth) <= 3.0e38f) {
+                const float kth_dn = nextafterf(kth, -INFINITY);
+                const double ed = (double)kth_dn * denom;
+                t2 = ed - eps - fabs(ed) * 1e-12;
+            }
+            if (t2 == t2 && fabs(t2) <= 3.0e38) {
+                float tf = (float)t2;
+                if ((double)tf >= t2) tf = nextafterf(tf, -INFINITY);
+                const int slot = atomicAdd(rl.r_count, 1);
+                rl.r_list[slot] = q;
+                rl.tau2[slot] = tf;
+                slot_sh = slot;
+            } else {
+                const int slot = atomicAdd(rl.x_count, 1);
+                rl.x_list[slot] = q;
+                atomicAdd(&status[3], 1);
+            }
+        }
+    }
+    __syncthreads();
+    const int slot = slot_sh;
+    if (slot >= 0) {
+        unsigned char* dst = rl.qpacked2 + ((size_t)(slot / tnq) * ks * tnq + (slot % tnq)) * ISC_KSTEP_BYTES;
+        for (int i = tid; i < ks * 8; i += SEL_THREADS) {
+            const size_t off = (size_t)(i >> 3) * tnq * ISC_KSTEP_BYTES + (i & 7) * 16;
+            *reinterpret_cast<uint4*>(dst + off) = *reinterpret_cast<const uint4*>(qrow_base + off);
+        }
+    }
+}
+
+// One workgroup per redo slot: every row of the redo filter's list re-scored in float64 and collapsed by group (exact
+// keys); the best k leaders are the answer.  An overflow, or fewer than k groups, hands the query to k_exact_collapse.
+template <typename T>
+__global__ __launch_bounds__(SEL_THREADS) void k_final2_groups(
+    const unsigned char* __restrict__ bank, int ks, const unsigned char* __restrict__ qpacked2, int tnq, int k, IscPerm pm,
+    int64_t index_base, const int32_t* __restrict__ r_count, const int32_t* __restrict__ r_list,
+    const int32_t* __restrict__ qcount2, const int32_t* __restrict__ qflag2, const Cand* __restrict__ qlist,
+    const int32_t* __restrict__ row_group, float* __restrict__ out_s, int64_t* __restrict__ out_i,
+    int32_t* __restrict__ out_c, int32_t* __restrict__ x_count, int32_t* __restrict__ x_list,
+    int32_t* __restrict__ status) {
+    const int slot = blockIdx.x;
+    if (slot >= *r_count) return;
+    __shared__ SelShared sh;
+    __shared__ GroupHash gh;
+    __shared__ double qnorm_sh;
+    const int tid = threadIdx.x;
+    const int q = r_list[slot];
+    const int cnt_all = qcount2[slot];
+    const int cnt = min(cnt_all, QCAP);
+    const bool lost = qflag2[slot] != 0 || cnt_all > QCAP || cnt < k;
+    const unsigned char* qrow_base = qpacked2 + ((size_t)(slot / tnq) * ks * tnq + (slot % tnq)) * ISC_KSTEP_BYTES;
+    gh_clear(gh);
+    if (tid < 64) {
+        const double nn = wave_query_norm<T>(qrow_base, ks, tnq);
+        if (tid == 0) qnorm_sh = sqrt(nn);
+    }
+    __syncthreads();
+    const double denom = fmax(qnorm_sh, 1e-12);
+    const Cand* list = qlist + (size_t)slot * QCAP;
+    int n = -1;
+    if (!lost) {
+        exact_dots<T>(bank, ks, qrow_base, tnq, cnt, pm.n, [&](int c) { return list[c].row; },
+                      [&](int c, double dot) {
+                          const int row = list[c].row;
+                          if ((unsigned)row < (unsigned)pm.n) {
+                              const int s = gh_insert(gh, row_group[row]);
+                              if (s < 0) gh.fail = 1;
+                              else atomicMax(&gh.lead[s], isc_make_key((float)(dot / denom), (int)isc_perm_orig(pm, row)));
+                          }
+                      });
+        __syncthreads();
+        if (!gh.fail) n = gh_select(sh, gh, k);
+    }
+    if (n < k) {
+        if (tid == 0) {
+            const int xs = atomicAdd(x_count, 1);
+            x_list[xs] = q;
+            atomicAdd(&status[3], 1);
+        }
+        return;
+    }
+    if (tid < k) {
+        const unsigned long long key = sh.topk[tid];
+        out_s[(size_t)q * k + tid] = isc_key_score(key);
+        out_i[(size_t)q * k + tid] = (int64_t)isc_key_row(key) + index_base;
+        out_c[(size_t)q * k + tid] = gh.tcode[tid];
+    }
+}
+
+__global__ void k_fill_i32(int32_t* p, int n, int v) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+// what the collapsed search needs beyond the row search's workspace (carve), laid out after it
+struct CollapseWs {
+    unsigned long long* carry_sib;  // [qpad][kp]  filter keys of the carried leaders' sibs
+    uint32_t* carry_sib3;           // [qpad][kp]  ... score bits of their sib3s
+    int32_t* qnone;       // [qpad]      query codes -1: a search that excludes nothing
+    int32_t* part_code;   // group codes of k_exact_collapse's partial lists
+    size_t bytes;
+};
+
+CollapseWs carve_collapse(const Plan& p, int ks, int64_t n, int k, void* base) {
+    CollapseWs c;
+    size_t off = carve(p, ks, n, k, nullptr).bytes;
+    auto take = [&](size_t bytes) {
+        void* ptr = base ? static_cast<char*>(base) + off : nullptr;
+        off += isc_align_up(bytes, 256);
+        return ptr;
+    };
+    c.carry_sib = static_cast<unsigned long long*>(take((size_t)p.qpad * p.kp * 8));
+    c.carry_sib3 = static_cast<uint32_t*>(take((size_t)p.qpad * p.kp * 4));
+    c.qnone = static_cast<int32_t*>(take((size_t)p.qpad * 4));
+    c.part_code = static_cast<int32_t*>(take(isc_exact_collapse_ws_bytes(n, p.qb, k) - isc_exact_ws_bytes(n, p.qb, k)));
+    c.bytes = off;
+    return c;
+}
+
+template <typename T, typename TQ>
+int run_collapse(const void* bank, int64_t n, int d, const void* queries, int q_total, int64_t ldq, int k,
+                 int64_t index_base, const float* norm_bound, float* out_s, int64_t* out_i, int32_t* out_c,
+                 int32_t* status, void* ws_base, hipStream_t stream, const IscGroups& g, int group_rows) {
+    const Plan p = make_plan(n, q_total, k, group_rows);
+    const int ksteps = isc_ksteps(d, (int)sizeof(T));
+    const Workspace w = carve(p, ksteps, n, k, ws_base);
+    const CollapseWs cw = carve_collapse(p, ksteps, n, k, ws_base);
+    const unsigned char* bank_bytes = static_cast<const unsigned char*>(bank);
+    const IscPerm pm = isc_make_perm(n);
+    if (!g.query_group)
+        hipLaunchKernelGGL(k_fill_i32, dim3(isc_ceil_div(p.qpad, 256)), dim3(256), 0, stream, cw.qnone, p.qpad, -1);
+    for (int q0 = 0; q0 < q_total; q0 += p.qb) {
+        const int q = q_total - q0 < p.qb ? q_total - q0 : p.qb;
+        const TQ* qptr = static_cast<const TQ*>(queries) + (int64_t)q0 * ldq;
+        float* os = out_s + (size_t)q0 * k;
+        int64_t* oi = out_i + (size_t)q0 * k;
+        int32_t* oc = out_c + (size_t)q0 * k;
+        const bool spec_all = q <= SMALL_Q;
+        hipLaunchKernelGGL((k_prep<T, TQ>), dim3(isc_ceil_div(p.qpad * ksteps * 8, 256)), dim3(256), 0, stream, qptr, ldq, q,
+                           d, ksteps, p.qpad, p.tnq, w.qpacked, w.tau, w.carry_n, w.qcount, w.qflag,
+                           w.exact.redo_count, w.exact.done, w.r_count, w.tau2, w.qcount2, w.qflag2, status,
+                           q0 == 0 ? 1 : 0);
+        IscGroups gp = g;  // this pass's query codes
+        gp.query_group = g.query_group ? g.query_group + q0 : cw.qnone;
+        gp.nq = q;
+        gp.slot_query = nullptr;
+        IscGroups gr = gp;  // ... as the redo filter reads them, through its slot -> query map
+        gr.slot_query = w.r_list;
+        const FilterIO io{w.qpacked, w.tau, w.qcount, w.qflag, nullptr};
+        for (int li = 0; li < p.nlevels; ++li) {
+            const Level& l = p.levels[li];
+            for_each_segment(l, p, [&](const Level& ls) {
+                isc_timing_begin(ISC_KERNEL_DOTS_FILTER, stream);
+                if (p.tnq == 256) launch_filter<T, 256>(ls, p, w, io, bank_bytes, ksteps, status, stream, gp);
+                else if (p.tnq == 128) launch_filter<T, 128>(ls, p, w, io, bank_bytes, ksteps, status, stream, gp);
+                else launch_filter<T, 64>(ls, p, w, io, bank_bytes, ksteps, status, stream, gp);
+                isc_timing_end(ISC_KERNEL_DOTS_FILTER, stream);
+            });
+            if (li + 1 < p.nlevels) {
+                if (spec_all)
+                    hipLaunchKernelGGL(k_select_groups<SEL_PER>, dim3(q), dim3(SEL_THREADS), 0, stream, w.qcount, w.qlist,
+                                       p.kp, w.tau, w.carry_s, w.carry_r, cw.carry_sib, cw.carry_sib3, w.carry_n, w.qflag, g.row_group,
+                                       n);
+                else
+                    hipLaunchKernelGGL(k_select_groups<SEL_SPEC_MANY>, dim3(q), dim3(SEL_THREADS), 0, stream, w.qcount,
+                                       w.qlist, p.kp, w.tau, w.carry_s, w.carry_r, cw.carry_sib, cw.carry_sib3, w.carry_n,
+                                       w.qflag, g.row_group, n);
+            }
+        }
+        const RedoLists rl{w.r_count, w.r_list, w.tau2, w.qpacked2, w.exact.redo_count, w.exact.redo_list};
+        if (spec_all)
+            hipLaunchKernelGGL((k_final_groups<T, SEL_PER>), dim3(q), dim3(SEL_THREADS), 0, stream, bank_bytes, ksteps,
+                               w.qpacked, p.tnq, p.kp, k, pm, index_base, norm_bound, w.qcount, w.qlist, w.carry_s,
+                               w.carry_r, cw.carry_sib, cw.carry_sib3, w.carry_n, w.qflag, g.row_group, os, oi, oc, rl,
+                               status);
+        else
+            hipLaunchKernelGGL((k_final_groups<T, SEL_SPEC_MANY>), dim3(q), dim3(SEL_THREADS), 0, stream, bank_bytes, ksteps,
+                               w.qpacked, p.tnq, p.kp, k, pm, index_base, norm_bound, w.qcount, w.qlist, w.carry_s,
+                               w.carry_r, cw.carry_sib, cw.carry_sib3, w.carry_n, w.qflag, g.row_group, os, oi, oc, rl,
+                               status);
+        // the matrix-core redo of the listed queries (normally none), as in run()
+        {
+            const FilterIO rio{w.qpacked2, w.tau2, w.qcount2, w.qflag2, w.r_count};
+            Level all;
+            all.r0 = 0;
+            all.r1 = n;
+            all.sample = 0;
+            all.ntiles = (int)isc_ceil_div<int64_t>(n, TM);
+            int wgs = TARGET_WGS / p.qtiles;
+            if (wgs < 1) wgs = 1;
+            const int want = wgs < all.ntiles ? wgs : all.ntiles;
+            all.tiles_per_chunk = isc_ceil_div(all.ntiles, want);
+            all.nchunks = isc_ceil_div(all.ntiles, all.tiles_per_chunk);
+            for_each_segment(all, p, [&](const Level& ls) {
+                if (p.tnq == 256) launch_filter<T, 256>(ls, p, w, rio, bank_bytes, ksteps, status, stream, gr);
+                else if (p.tnq == 128) launch_filter<T, 128>(ls, p, w, rio, bank_bytes, ksteps, status, stream, gr);
+                else launch_filter<T, 64>(ls, p, w, rio, bank_bytes, ksteps, status, stream, gr);
+            });
+            hipLaunchKernelGGL(k_final2_groups<T>, dim3(q), dim3(SEL_THREADS), 0, stream, bank_bytes, ksteps, w.qpacked2,
+                               p.tnq, k, pm, index_base, w.r_count, w.r_list, w.qcount2, w.qflag2, w.qlist, g.row_group,
+                               os, oi, oc, w.exact.redo_count, w.exact.redo_list, status);
+        }
+        const int st = isc_exact_collapse_launch(sizeof(T) == 2 ? ISC_F16 : ISC_F32, bank, n, d, qptr,
+                                                 sizeof(TQ) == 2 ? ISC_F16 : ISC_F32, ldq, k, index_base, w.exact,
+                                                 cw.part_code, os, oi, oc, gp, stream);
+        if (st != ISC_OK) return st;
+    }
+    return isc_launch_status();
+}
+
+}  // namespace
+
+extern "C" int isc_cosine_topk_collapse_workspace_bytes(int dtype, int64_t N, int D, int Q, int k, int max_group_rows,
+                                                        size_t* bytes) {
+    ISC_REQUIRE(bytes);
+    ISC_REQUIRE(max_group_rows >= 1);
+    const int st = check_args(dtype, N, D, Q, k);
+    if (st != ISC_OK) return st;
+    const int ks = isc_ksteps(D, dtype == ISC_F16 ? 2 : 4);
+    *bytes = carve_collapse(make_plan(N, Q, k, max_group_rows), ks, N, k, nullptr).bytes;
+    return ISC_OK;
+}
+
+extern "C" int isc_cosine_topk_collapse(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,
+                                        int Q, int64_t ldq, int k, int64_t index_base, const float* norm_bound,
+                                        float* out_scores, int64_t* out_indices, int32_t* status, void* workspace,
+                                        size_t workspace_bytes, const uint32_t* row_mask, const int32_t* row_group,
+                                        const int32_t* query_group, int max_group_rows, int32_t* out_codes,
+                                        void* stream) {
+    ISC_REQUIRE(bank && queries && out_scores && out_indices && out_codes && status && row_group);
+    ISC_REQUIRE(q_dtype == ISC_F16 || q_dtype == ISC_F32);
+    ISC_REQUIRE(max_group_rows >= 1);
+    const int st = check_args(dtype, N, D, Q, k);
+    if (st != ISC_OK) return st;
+    ISC_REQUIRE(ldq >= D);
+    if (!isc_aligned(row_group, 16) || !isc_aligned(query_group, 4) || !isc_aligned(row_mask, 4) ||
+        !isc_aligned(out_codes, 4))
+        return ISC_ERR_ALIGNMENT;
+    if (!isc_aligned(bank, 16) || !isc_aligned(workspace, 256)) return ISC_ERR_ALIGNMENT;
+    size_t need = 0;
+    isc_cosine_topk_collapse_workspace_bytes(dtype, N, D, Q, k, max_group_rows, &need);
+    if (!workspace || workspace_bytes < need) return ISC_ERR_WORKSPACE;
+    const IscGroups g{row_mask, row_group, query_group, nullptr, Q};
+    hipStream_t s = isc_stream(stream);
+#define ISC_RUN_COLLAPSE(T_, TQ_)                                                                                      \
+    return run_collapse<T_, TQ_>(bank, N, D, queries, Q, ldq, k, index_base, norm_bound, out_scores, out_indices,      \
+                                 out_codes, status, workspace, s, g, max_group_rows)
+    if (dtype == ISC_F16) {
+        if (q_dtype == ISC_F16) ISC_RUN_COLLAPSE(_Float16, _Float16);
+        ISC_RUN_COLLAPSE(_Float16, float);
+    }
+    if (q_dtype == ISC_F16) ISC_RUN_COLLAPSE(float, _Float16);
+    ISC_RUN_COLLAPSE(float, float);
+#undef ISC_RUN_COLLAPSE
 }

@@ -196,3 +196,14 @@ int isc_exact_launch(int dtype, const void* bank, int64_t n, int d, const void* 
 int isc_exact_launch(int dtype, const void* bank, int64_t n, int d, const void* queries, int q_dtype, int64_t ldq, int k,
                      int64_t index_base, const IscExactWs& ws, float* out_s, int64_t* out_i, int32_t* status,
                      const IscGroups& groups, hipStream_t stream);
+
+// ---- exact float64 search of a list of queries with the rows collapsed by group (isc_cosine_topk_collapse) ---------
+// The workspace of isc_exact_ws_bytes followed by the group codes of the partial lists ([q][chunks][k] int32).
+size_t isc_exact_collapse_ws_bytes(int64_t n, int q, int k);
+int32_t* isc_exact_collapse_codes(void* base, int64_t n, int q, int k);
+// enqueue k_exact_collapse: the best k GROUPS of the listed queries (every row of `groups` carries a code; the query codes
+// may be NULL: nothing excluded), rows redo_list[i] of out_s / out_i / out_c written, short answers padded with score
+// NaN, index INT64_MAX, code -1
+int isc_exact_collapse_launch(int dtype, const void* bank, int64_t n, int d, const void* queries, int q_dtype, int64_t ldq,
+                              int k, int64_t index_base, const IscExactWs& ws, int32_t* part_code, float* out_s,
+                              int64_t* out_i, int32_t* out_c, const IscGroups& groups, hipStream_t stream);

@@ -129,6 +129,12 @@ def _unpad(scores: Tensor, indices: Tensor) -> tuple[Tensor, Tensor]:
     return scores.masked_fill(pad, -math.inf), indices.masked_fill(pad, -1)
 
 
+def _unpad_groups(scores: Tensor, indices: Tensor, labels: Tensor) -> tuple[Tensor, Tensor, Tensor]:
+    """The public form of a collapsed top-k: the padding (NaN, INT64_MAX, label -1) becomes (-inf, -1, -1)."""
+    pad = indices == _PAD_INDEX
+    return scores.masked_fill(pad, -math.inf), indices.masked_fill(pad, -1), labels.masked_fill(pad, -1)
+
+
 class RowFilter:
     """A set of allowed rows of ONE bank, made by `EmbeddingBank.row_filter`: the bitmap of this rank's rows in the bank's
     packed row order (`isc_row_mask_pack`) and the number of rows it allows (int64 [1], device).  Searches given it as
@@ -235,9 +241,13 @@ class EmbeddingBank:
         # position among them -- of every row in the PACKED row order (`isc_row_groups_pack`)
         self.group_labels: Tensor | None = None
         self._row_codes: Tensor | None = None
+        # the most rows one group of this rank holds: the collapsed search (`search_groups`) sizes its levels with it,
+        # so it is taken here, once, rather than with a host synchronisation per search
+        self._max_group_rows = 0
         if row_groups is not None:
             labels = row_groups.to(device=self.device, dtype=torch.int64)
-            self.group_labels, codes = torch.unique(labels, sorted=True, return_inverse=True)
+            self.group_labels, codes, counts = torch.unique(labels, sorted=True, return_inverse=True, return_counts=True)
+            self._max_group_rows = int(counts.max()) if counts.numel() else 0
             self._row_codes = self._pack_groups(codes.to(torch.int32).contiguous())
 
     # ------------------------------------------------------------------ construction
@@ -462,7 +472,7 @@ class EmbeddingBank:
             queries = queries.to(self.dtype)
         return queries if queries.stride(1) == 1 or queries.shape[0] == 0 else queries.contiguous()
 
-    def _workspace(self, n_queries: int, k: int, lane: int = -1) -> Tensor:
+    def _workspace(self, n_queries: int, k: int, lane: int = -1, collapse: bool = False) -> Tensor:
         """The search workspace.  The C side runs a call as passes of at most `ISC_SEARCH_PASS_QUERIES` queries over
         one workspace and cuts the queries into ONE tile of 64 (Q <= 64) or 128 (Q <= 128), or tiles of 256, so the size depends on
         (padded queries of a pass, k) only: alternating batch sizes inside one bucket -- a pipeline's short last
@@ -470,18 +480,28 @@ class EmbeddingBank:
 
         A workspace handed out while the current stream is being captured is also kept in `_captured_workspaces`, which
         the bucket cache never evicts: the graph holds its raw pointer, and a replay after the bucket had been dropped would
-        write into whatever tensor the allocator had given that memory to."""
+        write into whatever tensor the allocator had given that memory to.
+
+        `collapse`: the workspace of the collapsed search (`isc_cosine_topk_collapse_workspace_bytes`), cached apart."""
         nq = min(n_queries, _lib.ISC_SEARCH_PASS_QUERIES)
-        key = (-(-nq // 64) * 64 if nq <= 128 else -(-nq // 256) * 256, k)
+        key = (-(-nq // 64) * 64 if nq <= 128 else -(-nq // 256) * 256, k) if not collapse else \
+            (-(-nq // 64) * 64 if nq <= 128 else -(-nq // 256) * 256, k, "collapse")
         cache = self._workspaces.setdefault(lane, {})
         ws = cache.get(key)
         if ws is None:
             lib = _lib.load()
             need = _lib.c_size_t()
-            st = lib.isc_cosine_topk_workspace_bytes(
-                _lib.dtype_code(self.dtype), self.num_local_rows, self.dim, min(key[0], _lib.ISC_SEARCH_PASS_QUERIES), k, need
-            )
-            _lib.check(st, "isc_cosine_topk_workspace_bytes")
+            if collapse:
+                st = lib.isc_cosine_topk_collapse_workspace_bytes(
+                    _lib.dtype_code(self.dtype), self.num_local_rows, self.dim, min(key[0], _lib.ISC_SEARCH_PASS_QUERIES),
+                    k, max(self._max_group_rows, 1), need)
+                _lib.check(st, "isc_cosine_topk_collapse_workspace_bytes")
+            else:
+                st = lib.isc_cosine_topk_workspace_bytes(
+                    _lib.dtype_code(self.dtype), self.num_local_rows, self.dim, min(key[0], _lib.ISC_SEARCH_PASS_QUERIES), k,
+                    need
+                )
+                _lib.check(st, "isc_cosine_topk_workspace_bytes")
             ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
             if len(cache) >= 4:  # bound what a bank pins: drop the oldest bucket
                 cache.pop(next(iter(cache)))
@@ -799,6 +819,183 @@ class EmbeddingBank:
         gathered = torch.empty(self.world_size * src.numel(), dtype=torch.uint8, device=src.device)
         dist.all_gather_into_tensor(gathered, src, group=self.process_group)
         return gathered.to(xbuf.device).view(self.world_size, src.numel())
+
+    # ------------------------------------------------------------------ collapsed search
+    def _labels_of(self, codes: Tensor) -> Tensor:
+        """int64 labels of int32 group codes (`group_labels[code]`); -1 for the padding's code -1.  Tensor ops only."""
+        labels = self.group_labels
+        if labels is None or labels.numel() == 0:
+            return torch.full(codes.shape, -1, dtype=torch.int64, device=codes.device)
+        return torch.where(codes >= 0, labels[codes.clamp(min=0).long()], -1)
+
+    def _local_collapse(self, queries: Tensor, k: int, out: tuple[Tensor, Tensor, Tensor] | None = None,
+                        mask: RowFilter | None = None, groups: Tensor | None = None) -> tuple[Tensor, Tensor, Tensor]:
+        """The k best groups of this rank's rows (`isc_cosine_topk_collapse`): `(scores float32 [Q, k], indices int64
+        [Q, k] GLOBAL rows, labels int64 [Q, k])` with the C ABI's padding (NaN, INT64_MAX, label -1), final when the stream
+        has run the call.  `out`: optional (scores, indices, status int32[4]) to write into; `mask` / `groups`: as in
+        `_local_topk`.  The device hook a CPU rehearsal replaces."""
+        nq = queries.shape[0]
+        if out is None:
+            scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+            indices = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+            status = torch.empty(4, dtype=torch.int32, device=self.device)
+        else:
+            scores, indices, status = out
+        codes = torch.empty((nq, k), dtype=torch.int32, device=self.device)
+        ws = self._workspace(nq, k, collapse=True)
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            st = lib.isc_cosine_topk_collapse(
+                self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.num_local_rows, self.dim, queries.data_ptr(),
+                _lib.dtype_code(queries.dtype), nq, queries.stride(0), k, self.index_base, self._norm_bound.data_ptr(),
+                scores.data_ptr(), indices.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                None if mask is None else mask.packed.data_ptr(), self._row_codes.data_ptr(),
+                None if groups is None else groups.data_ptr(), max(self._max_group_rows, 1), codes.data_ptr(),
+                _lib.stream_handle(self.device),
+            )
+        _lib.check(st, "isc_cosine_topk_collapse")
+        self.last_status = status
+        return scores, indices, self._labels_of(codes)
+
+    def _merge_groups(self, scores: Tensor, indices: Tensor, labels: Tensor, k: int) -> tuple[Tensor, Tensor, Tensor]:
+        """Merge `[G, Q, kin]` collapsed partial results into `[Q, k]` (`isc_topk_merge_groups`): the best entry per label,
+        then the best k.  The inputs may be strided along G; their `[Q, kin]` blocks are dense."""
+        g, nq, kin = scores.shape
+        ts = (scores, indices, labels)
+        if any(t.stride(1) != kin or t.stride(2) != 1 for t in ts):
+            scores, indices, labels = (t.contiguous() for t in ts)
+        out_s = torch.empty((nq, k), dtype=torch.float32, device=scores.device)
+        out_i = torch.empty((nq, k), dtype=torch.int64, device=scores.device)
+        out_l = torch.empty((nq, k), dtype=torch.int64, device=scores.device)
+        lib = _lib.load()
+        with torch.cuda.device(scores.device):
+            st = lib.isc_topk_merge_groups(
+                scores.data_ptr(), indices.data_ptr(), labels.data_ptr(), g, nq, kin, k,
+                scores.stride(0) if g > 1 else 0, indices.stride(0) if g > 1 else 0, labels.stride(0) if g > 1 else 0,
+                out_s.data_ptr(), out_i.data_ptr(), out_l.data_ptr(), _lib.stream_handle(scores.device),
+            )
+        _lib.check(st, "isc_topk_merge_groups")
+        return out_s, out_i, out_l
+
+    def _check_groups_k(self, k: int) -> None:
+        if not isinstance(k, int) or isinstance(k, bool):
+            raise TypeError(f"k must be an int, got {type(k).__name__}")
+        if k < 1:
+            raise ValueError(f"k must be >= 1, got {k}")
+        if k > _lib.ISC_TOPK_MAX_K:
+            raise ValueError(f"k must be <= {_lib.ISC_TOPK_MAX_K}, got {k}")
+
+    def search_groups(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None,
+                      exclude_group: Tensor | None = None) -> tuple[Tensor, Tensor, Tensor]:
+        """The k best GROUPS per query ("which images look like this region?") on a bank built with `row_groups=` (or
+        `from_database`, grouped by image id).  A group's key is the best (score desc with NaN last, row asc) among the rows
+        the query may return (`mask`, `exclude_group`: as in `search`); that row is the group's leader.
+
+        Returns `(scores float32 [Q, k], indices int64 [Q, k], groups int64 [Q, k])`: per entry the leader's score, its
+        global row index and the group's label, best group first.  A query with fewer than k groups it may return ends in
+        padding: score -inf, index -1, label -1 (test the index: -1 can be a real label).  `1 <= k <= min(rows, 120)`.
+
+        Exact like `search`: on a bank whose rows are each their own group the answer is `search(q, k)`, bit for bit.
+        No host synchronisation, so a world-1 call may be captured into a graph.  `last_status` keeps its meaning ([1]:
+        queries the first pass could not prove, [3]: queries answered by the float64 sweep).  A sharded bank all-gathers
+        every rank's collapsed list with its labels and keeps the best entry per label."""
+        rf = self._as_filter(mask)
+        self._check_groups_k(k)
+        q = self._prepare_queries(queries)
+        nq = q.shape[0]
+        if self.group_labels is None:
+            raise ValueError("search_groups needs row groups: build the bank with row_groups= (or from_database)")
+        qg = self._query_codes(exclude_group, nq)
+        filt: dict[str, object] = {} if rf is None else {"mask": rf}
+        if qg is not None:
+            filt["groups"] = qg
+        if self.process_group is None:
+            if k > self.num_local_rows:
+                raise ValueError(f"k={k} exceeds the bank size {self.num_local_rows}")
+            if nq == 0:
+                return (torch.empty((0, k), dtype=torch.float32, device=self.device),
+                        torch.empty((0, k), dtype=torch.int64, device=self.device),
+                        torch.empty((0, k), dtype=torch.int64, device=self.device))
+            return _unpad_groups(*self._local_collapse(q, k, **filt))
+
+        if not hasattr(self, "_n_total"):
+            self._n_total = self._total_rows()
+        if k > self._n_total:
+            raise ValueError(f"k={k} exceeds the bank size {self._n_total}")
+        if nq == 0:
+            return (torch.empty((0, k), dtype=torch.float32, device=self.device),
+                    torch.empty((0, k), dtype=torch.int64, device=self.device),
+                    torch.empty((0, k), dtype=torch.int64, device=self.device))
+        # exchange buffer of this rank: [scores f32 Q*k | indices i64 Q*k | labels i64 Q*k | status i32 x4], gathered with
+        # ONE collective and read in place by the merge
+        off_i = (4 * nq * k + 7) // 8 * 8
+        off_l = off_i + 8 * nq * k
+        off_s = off_l + 8 * nq * k
+        xbuf = torch.empty(off_s + 16, dtype=torch.uint8, device=self.device)
+        part_s = xbuf[: 4 * nq * k].view(torch.float32).view(nq, k)
+        part_i = xbuf[off_i:off_l].view(torch.int64).view(nq, k)
+        part_l = xbuf[off_l:off_s].view(torch.int64).view(nq, k)
+        status = xbuf[off_s:].view(torch.int32)
+        kl = min(k, self.num_local_rows)
+        if kl < k:  # a shard with fewer rows than k: pad with entries that rank after every real one
+            part_s.fill_(math.nan)
+            part_i.fill_(_PAD_INDEX)
+            part_l.fill_(-1)
+            status.zero_()
+            if kl > 0:
+                s, i, lab = self._local_collapse(q, kl, **filt)
+                part_s[:, :kl] = s
+                part_i[:, :kl] = i
+                part_l[:, :kl] = lab
+        else:
+            _, _, lab = self._local_collapse(q, k, out=(part_s, part_i, status), **filt)
+            part_l.copy_(lab)
+        gathered = self._all_gather_bytes(xbuf)
+        g = self.world_size
+        all_s = gathered[:, : 4 * nq * k].view(torch.float32).view(g, nq, k)
+        all_i = gathered[:, off_i:off_l].view(torch.int64).view(g, nq, k)
+        all_l = gathered[:, off_l:off_s].view(torch.int64).view(g, nq, k)
+        self.last_gathered_status = gathered[:, off_s:].view(torch.int32)
+        return _unpad_groups(*self._merge_groups(all_s, all_i, all_l, k))
+
+    def search_groups_exhaustive(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None,
+                                 exclude_group: Tensor | None = None) -> tuple[Tensor, Tensor, Tensor]:
+        """`search_groups` from the data-independent float64 kernel (`isc_cosine_topk_exhaustive_collapse`): every score
+        evaluated exactly, one shard.  Slow; the on-device reference the fast path is tested against."""
+        rf = self._as_filter(mask)
+        self._check_groups_k(k)
+        q = self._prepare_queries(queries)
+        nq = q.shape[0]
+        if self.group_labels is None:
+            raise ValueError("search_groups_exhaustive needs row groups: build the bank with row_groups= (or from_database)")
+        qg = self._query_codes(exclude_group, nq)
+        if self.process_group is not None:
+            raise ValueError("search_groups_exhaustive answers for one shard; merge the shards with search_groups()")
+        if not 1 <= k <= self.num_local_rows:
+            raise ValueError(f"k={k} must be in [1, {self.num_local_rows}]")
+        if nq == 0:
+            return (torch.empty((0, k), dtype=torch.float32, device=self.device),
+                    torch.empty((0, k), dtype=torch.int64, device=self.device),
+                    torch.empty((0, k), dtype=torch.int64, device=self.device))
+        lib = _lib.load()
+        code = _lib.dtype_code(self.dtype)
+        need = _lib.c_size_t()
+        _lib.check(lib.isc_cosine_topk_exhaustive_collapse_workspace_bytes(code, self.num_local_rows, self.dim, nq, k,
+                                                                           need),
+                   "isc_cosine_topk_exhaustive_collapse_workspace_bytes")
+        ews = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        indices = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        codes = torch.empty((nq, k), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = lib.isc_cosine_topk_exhaustive_collapse(
+                self._bank.data_ptr(), code, self.num_local_rows, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
+                q.stride(0), k, self.index_base, scores.data_ptr(), indices.data_ptr(), ews.data_ptr(), ews.numel(),
+                None if rf is None else rf.packed.data_ptr(), self._row_codes.data_ptr(),
+                None if qg is None else qg.data_ptr(), codes.data_ptr(), _lib.stream_handle(self.device),
+            )
+        _lib.check(st, "isc_cosine_topk_exhaustive_collapse")
+        return _unpad_groups(scores, indices, self._labels_of(codes))
 
     # ------------------------------------------------------------------ range search
     # Entries the first attempt of a range search reserves per query; a larger result costs one more call with the exact

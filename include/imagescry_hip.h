@@ -473,6 +473,44 @@ int isc_cosine_range_grouped(const void* bank, int dtype, int64_t N, int D, cons
 int isc_topk_merge(const float* scores, const int64_t* indices, int G, int Q, int kin, int kout, int64_t stride_g_scores,
                    int64_t stride_g_indices, float* out_scores, int64_t* out_indices, void* stream);
 
+/* Collapsed (distinct-group) top-k: for every query the k GROUPS with the best keys, where a row's key is (score desc with
+ * NaN last, original row asc), the score that of isc_cosine_topk, and a group's key is the best key among the rows the
+ * query may return (row_mask, and query_group as in isc_cosine_topk_grouped).  That row is the group's leader: entry j of a
+ * query is its j-th group's leader score, the leader's row + index_base, and the group's code (out_codes, int32 [Q, k],
+ * 4-byte aligned).  A query with fewer than k groups it may return ends in padding: score NaN, index INT64_MAX, code -1.
+ * row_group: the packed codes of isc_row_groups_pack (required; rows with a negative code form one group); query_group:
+ * int32 [Q] or NULL (nothing excluded).  max_group_rows (>= 1): the most rows one group holds, a planning figure only --
+ * every value gives the exact answer, a far too small one only more redone queries.  The workspace comes from
+ * isc_cosine_topk_collapse_workspace_bytes with the same max_group_rows.  Final on the device, bit for bit the answer of
+ * isc_cosine_topk_exhaustive_collapse, no host synchronisation; the contents of the workspace on entry do not matter, so
+ * the call may be captured into a graph.  Status words as in isc_cosine_topk: [1] queries the first pass could not prove,
+ * [3] queries answered by the float64 sweep. */
+int isc_cosine_topk_collapse_workspace_bytes(int dtype, int64_t N, int D, int Q, int k, int max_group_rows,
+                                             size_t* bytes);
+int isc_cosine_topk_collapse(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
+                             int64_t ldq, int k, int64_t index_base, const float* norm_bound, float* out_scores,
+                             int64_t* out_indices, int32_t* status, void* workspace, size_t workspace_bytes,
+                             const uint32_t* row_mask, const int32_t* row_group, const int32_t* query_group,
+                             int max_group_rows, int32_t* out_codes, void* stream);
+
+/* The same answer from a data-independent float64 sweep (isc_cosine_topk_exhaustive's cost): the last resort of
+ * isc_cosine_topk_collapse and its on-device reference. */
+int isc_cosine_topk_exhaustive_collapse_workspace_bytes(int dtype, int64_t N, int D, int Q, int k, size_t* bytes);
+int isc_cosine_topk_exhaustive_collapse(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,
+                                        int Q, int64_t ldq, int k, int64_t index_base, float* out_scores,
+                                        int64_t* out_indices, void* workspace, size_t workspace_bytes,
+                                        const uint32_t* row_mask, const int32_t* row_group, const int32_t* query_group,
+                                        int32_t* out_codes, void* stream);
+
+/* Merge G collapsed partial results (one per bank shard) into the collapsed top-k: for each label the best entry in
+ * isc_topk_merge's order, then the best kout of those.  labels int64 [G,Q,kin] (padding entries, index INT64_MAX, are never
+ * merged and rank last) -> [Q,kout]; fewer than kout distinct labels end in padding (NaN, INT64_MAX, label -1).
+ * kout <= G*kin <= 2048; strides as in isc_topk_merge.  Exact for shards of one bank: a group's leader lies in one shard,
+ * where the group is in the local top k whenever it is in the global one. */
+int isc_topk_merge_groups(const float* scores, const int64_t* indices, const int64_t* labels, int G, int Q, int kin,
+                          int kout, int64_t stride_g_scores, int64_t stride_g_indices, int64_t stride_g_labels,
+                          float* out_scores, int64_t* out_indices, int64_t* out_labels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
