@@ -398,11 +398,18 @@ class EfficientNetEmbedder(EmbeddingModule):
 
 
 class ViTB16Embedder(EmbeddingModule):
-    """ViT-B/16 -> 768-d class-token embedding, fp16 matrix-core arithmetic (BASELINE.json configs[4]).
+    """ViT-B/16 -> 768-d embeddings, fp16 matrix-core arithmetic (BASELINE.json configs[4]).
 
-    Same constructor style as the other embedders.  A ViT has a fixed token grid, so `preprocess` resizes every batch
-    to `image_size` x `image_size` (the reference's `resize` with a tuple size, transforms.py:78-126) before the
-    batch-statistics normalisation; the output map is `[B, 768, 1, 1]`, one bank row per image.
+    Same constructor style as the other embedders.  By default (`output="cls"`, `grid="fixed"`) `preprocess` resizes
+    every batch to `image_size` x `image_size` (the reference's `resize` with a tuple size, transforms.py:78-126)
+    before the batch-statistics normalisation and the output map is the class token, `[B, 768, 1, 1]`: one bank row per
+    image.
+
+    `output="patches"` returns the spatial map the reference's contract describes (embedding.py:57-76): `[B, 768, h, w]`,
+    cell `(i, j)` = patch token `1 + i w + j` after the final LayerNorm, one bank row per 16 x 16-pixel patch of the
+    resized image.  `grid="aspect"` keeps the aspect ratio: a `[B, 3, H, W]` batch is resized to `(16 h, 16 w)` with
+    `(h, w) = vit.token_grid(H, W, config.grid ** 2)` and the position embeddings are resampled bicubically to that
+    grid (`vit.position_table`); `forward` then takes any `[B, 3, 16 h, 16 w]` with `h w <= config.grid ** 2`.
     """
 
     def __init__(
@@ -412,13 +419,25 @@ class ViTB16Embedder(EmbeddingModule):
         state_dict: dict[str, Tensor] | None = None,
         seed: int = 0,
         max_images_per_pass: int = 1024,
+        output: str = "cls",
+        grid: str = "fixed",
     ) -> None:
         super().__init__()
         if max_images_per_pass <= 0:
             raise ValueError(f"max_images_per_pass must be positive, got {max_images_per_pass}")
+        if output not in ("cls", "patches"):
+            raise ValueError(f'output must be "cls" or "patches", got {output!r}')
+        if grid not in ("fixed", "aspect"):
+            raise ValueError(f'grid must be "fixed" or "aspect", got {grid!r}')
         self.config = config
         self.max_images_per_pass = max_images_per_pass
+        self.output = output
+        self.grid = grid
         self.hparams = {"image_size": config.image_size, "patch_size": config.patch_size, "depth": config.depth}
+        if (output, grid) != ("cls", "fixed"):
+            self.hparams.update(output=output, grid=grid)
+        # the patch-token head applies F.normalize itself when predict_step asks for it (isc_vit_tokens_out)
+        self._head_normalizes = output == "patches"
         sd = state_dict if state_dict is not None else vit.make_state_dict(config, seed=seed)
         self._net = vit.prepare(sd, config)
 
@@ -434,24 +453,65 @@ class ViTB16Embedder(EmbeddingModule):
             raise TypeError("images must be a uint8 tensor")
         if images.ndim != 4:
             raise ValueError(f"images must have shape [B, C, H, W], got {tuple(images.shape)}")
-        s = self.config.image_size
-        if tuple(images.shape[-2:]) != (s, s):
-            images = resize(images, output_size=(s, s))
+        if self.grid == "aspect":
+            h, w = vit.token_grid(images.shape[-2], images.shape[-1], self.config.grid**2)
+            size = (h * self.config.patch_size, w * self.config.patch_size)
+        else:
+            size = (self.config.image_size, self.config.image_size)
+        if tuple(images.shape[-2:]) != size:
+            images = resize(images, output_size=size)
         return normalize_per_channel(images, min_value=-3, max_value=3)
 
+    def _token_grid_of(self, x: Tensor) -> tuple[int, int]:
+        """The token grid `forward` runs a float32 input on, or ValueError for a shape this mode does not take."""
+        s, p = self.config.image_size, self.config.patch_size
+        if self.grid == "fixed":
+            if x.ndim != 4 or tuple(x.shape[1:]) != (3, s, s):
+                raise ValueError(f"x must have shape [B, 3, {s}, {s}], got {tuple(x.shape)}")
+            return self.config.grid, self.config.grid
+        ok = x.ndim == 4 and x.shape[1] == 3 and x.shape[2] > 0 and x.shape[3] > 0 and x.shape[2] % p == 0 and x.shape[3] % p == 0
+        if not ok or (x.shape[2] // p) * (x.shape[3] // p) > self.config.grid**2:
+            raise ValueError(f"x must have shape [B, 3, {p} h, {p} w] with h w <= {self.config.grid ** 2}, "
+                             f"got {tuple(x.shape)}")
+        return x.shape[2] // p, x.shape[3] // p
+
     def forward(self, x: Tensor) -> Tensor:
+        return self._forward(x, normalized=False)
+
+    def _forward(self, x: Tensor, normalized: bool) -> Tensor:
         if not isinstance(x, Tensor) or x.dtype != torch.float32:
             raise TypeError("x must be a float32 tensor")
-        s = self.config.image_size
-        if x.ndim != 4 or tuple(x.shape[1:]) != (3, s, s):
-            raise ValueError(f"x must have shape [B, 3, {s}, {s}], got {tuple(x.shape)}")
+        grid = self._token_grid_of(x)
         _lib.require_device(x, "x")
         if self.device != x.device:
             raise ValueError(f"module is on {self.device} but the input is on {x.device}; call .to() first")
         x = x.contiguous()
         b = x.shape[0]
+        step = self.max_images_per_pass
+        if self.output == "patches":
+            out = torch.empty((b, self.config.dim, *grid), dtype=torch.float32, device=x.device)
+            with torch.cuda.device(x.device):
+                for b0 in range(0, b, step):
+                    vit.forward_tokens(self._net, x[b0 : b0 + step], grid, normalize=normalized, out=out[b0 : b0 + step])
+            return out
         out = torch.empty((b, self.config.dim), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            for b0 in range(0, b, self.max_images_per_pass):
-                out[b0 : b0 + self.max_images_per_pass] = vit.forward_cls(self._net, x[b0 : b0 + self.max_images_per_pass])
+            for b0 in range(0, b, step):
+                out[b0 : b0 + step] = vit.forward_cls(self._net, x[b0 : b0 + step], grid)
         return out[:, :, None, None]
+
+    def predict_step(self, batch: ImageBatch) -> EmbeddingBatch:
+        """As `EmbeddingModule.predict_step`; in patches mode the head normalises (one pass less over the map, the same
+        bits as `l2_normalize_channels(forward(preprocess(images)))`).  A subclass that overrides `forward` or
+        `preprocess` gets exactly `forward(preprocess(images))` and the separate normalisation."""
+        cls = type(self)
+        own = cls.forward is ViTB16Embedder.forward and cls._forward is ViTB16Embedder._forward
+        if not (self._head_normalizes and own):
+            return super().predict_step(batch)
+        if not isinstance(batch, ImageBatch):
+            raise TypeError(f"batch must be an ImageBatch, got {type(batch).__name__}")
+        x = self.preprocess(batch.images)
+        if x.ndim == 4 and x.shape[2] * x.shape[3] == self.config.patch_size**2:
+            # a one-cell map: isc_l2norm_channels sums a lone row in another order than the head does
+            return EmbeddingBatch(indices=batch.indices, embeddings=l2_normalize_channels(self.forward(x)))
+        return EmbeddingBatch(indices=batch.indices, embeddings=self._forward(x, normalized=True))

@@ -5,11 +5,14 @@ The reference has no ViT (its encoder is torchvision EfficientNetV2, src/imagesc
 is the build's own definition behind the same `EmbeddingModule` contract.  State dicts use timm's
 `vit_base_patch16_224` parameter names (`cls_token`, `pos_embed`, `patch_embed.proj.weight`, `blocks.3.attn.qkv.weight`,
 `blocks.3.mlp.fc1.bias`, `norm.weight`, ...) so such a checkpoint drops in.  The embedding of an image is the class
-token after the final LayerNorm (pre-LN encoder, erf-form GELU, LayerNorm eps 1e-6 by default).
+token after the final LayerNorm (pre-LN encoder, erf-form GELU, LayerNorm eps 1e-6 by default) -- `forward_cls` -- or
+the map of its patch tokens -- `forward_tokens` --, on the checkpoint's square token grid or on any `h x w` grid of at
+most as many patches (`token_grid`, `position_table`: bicubically resampled position embeddings).
 """
 
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 
 import torch
@@ -38,6 +41,16 @@ class ViTConfig:
 
 
 VIT_B16 = ViTConfig()
+
+
+def token_grid(height: int, width: int, max_patches: int = VIT_B16.grid**2) -> tuple[int, int]:
+    """The `(h, w)` token grid of an aspect-preserving ViT input: `h = clamp(round(sqrt(max_patches * H / W)), 1,
+    max_patches)` (round half to even), `w = max(1, max_patches // h)`.  `h * w <= max_patches` always, a square image
+    gets the square grid, and one input shape gets one grid."""
+    if height <= 0 or width <= 0 or max_patches <= 0:
+        raise ValueError(f"token_grid needs positive sizes, got {height} x {width}, max_patches {max_patches}")
+    h = min(max(round(math.sqrt(max_patches * height / width)), 1), max_patches)
+    return h, max(1, max_patches // h)
 
 
 def make_state_dict(cfg: ViTConfig = VIT_B16, *, seed: int = 0, randomize_affine: bool = False) -> dict[str, Tensor]:
@@ -147,6 +160,9 @@ class PreparedViT:
     patch: Linear  # [D, 3 * P * P]
     blocks: list[Block] = field(default_factory=list)
     norm: Norm | None = None
+    # resampled position tables, (h, w) -> float32 [1 + h * w, D] on pos_embed's device; belongs to THIS prepared net
+    # (`to` starts an empty one), bounded by POS_CACHE_MAX
+    pos_cache: dict[tuple[int, int], Tensor] = field(default_factory=dict, repr=False, compare=False)
 
     def to(self, device: torch.device) -> "PreparedViT":
         return PreparedViT(self.cfg, self.cls_token.to(device), self.pos_embed.to(device), self.patch.to(device),
@@ -201,14 +217,43 @@ def _layernorm_packed(x: Tensor, rows: int, nrm: Norm, eps: float, out: Tensor, 
     return out
 
 
-def forward_cls(net: PreparedViT, x: Tensor) -> Tensor:
-    """float32 `[B, 3, S, S]` (already preprocessed) on a HIP device -> float32 `[B, D]` class-token features.
+POS_CACHE_MAX = 16  # resampled position tables kept per prepared net (0.6 MB each for ViT-B/16)
+
+
+def position_table(net: PreparedViT, grid: tuple[int, int]) -> Tensor:
+    """float32 `[1 + h * w, D]` position table of an `h x w` token grid: the class row as it is, the `g x g` patch rows
+    resampled bicubically (`isc_vit_pos_resample`, the arithmetic of `F.interpolate(mode="bicubic")`).  The native
+    grid returns `net.pos_embed` itself, no launch; other grids are computed once per device and cached on `net`."""
+    h, w = grid
+    g = net.cfg.grid
+    if (h, w) == (g, g):
+        return net.pos_embed
+    table = net.pos_cache.get((h, w))
+    if table is None or table.device != net.pos_embed.device:
+        _lib.require_device(net.pos_embed, "pos_embed")
+        dev = net.pos_embed.device
+        table = torch.empty((1 + h * w, net.cfg.dim), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = _lib.load().isc_vit_pos_resample(net.pos_embed.data_ptr(), g, h, w, net.cfg.dim, table.data_ptr(),
+                                                  _lib.stream_handle(dev))
+        _lib.check(st, "isc_vit_pos_resample")
+        net.pos_cache.pop((h, w), None)
+        if len(net.pos_cache) >= POS_CACHE_MAX:  # bound what a net pins: drop the oldest grid
+            net.pos_cache.pop(next(iter(net.pos_cache)))
+        net.pos_cache[(h, w)] = table
+    return table
+
+
+def _encode(net: PreparedViT, x: Tensor, grid: tuple[int, int]) -> Tensor:
+    """float32 `[B, 3, P h, P w]` (already preprocessed) on a HIP device -> the float32 residual stream `[B * T, D]`
+    after the last block, `T = h w + 1` (the final LayerNorm is the caller's).
 
     Every fp16 activation (patches, LayerNorm outputs, qkv, attention output, MLP hidden) lives in the packed layout;
     the float32 residual stream is row-major."""
     cfg = net.cfg
     b = x.shape[0]
-    t, d = cfg.tokens, cfg.dim
+    gh, gw = grid
+    t, d = gh * gw + 1, cfg.dim
     m = b * t
     dev = x.device
     lib = _lib.load()
@@ -221,15 +266,16 @@ def forward_cls(net: PreparedViT, x: Tensor) -> Tensor:
         # enough not to matter, and every consumer masks them, so the buffer is left uninitialised
         return torch.empty(packed_elems(rows, cols), dtype=f16, device=dev)
 
+    pos = position_table(net, grid)
     patches = packed(b * (t - 1), kdim)
-    _lib.check(lib.isc_patchify_f16(x.data_ptr(), b, 3, cfg.image_size, cfg.image_size, cfg.patch_size,
+    _lib.check(lib.isc_patchify_f16(x.data_ptr(), b, 3, gh * cfg.patch_size, gw * cfg.patch_size, cfg.patch_size,
                                     patches.data_ptr(), 1, stream), "isc_patchify_f16")
     pe = torch.empty((b * (t - 1), d), dtype=f32, device=dev)
     _gemm(patches, b * (t - 1), net.patch, pe, stream=stream)
     del patches
     xa = torch.empty((m, d), dtype=f32, device=dev)  # residual stream (ping)
     xb = torch.empty((m, d), dtype=f32, device=dev)  # residual stream (pong)
-    _lib.check(lib.isc_vit_assemble(pe.data_ptr(), net.cls_token.data_ptr(), net.pos_embed.data_ptr(), b, t, d,
+    _lib.check(lib.isc_vit_assemble(pe.data_ptr(), net.cls_token.data_ptr(), pos.data_ptr(), b, t, d,
                                     xa.data_ptr(), stream), "isc_vit_assemble")
     del pe
     hbuf, qkv, att, mlp = packed(m, d), packed(m, 3 * d), packed(m, d), packed(m, cfg.mlp_dim)
@@ -242,11 +288,55 @@ def forward_cls(net: PreparedViT, x: Tensor) -> Tensor:
         _layernorm_packed(xb, m, blk.norm2, cfg.ln_eps, hbuf, stream)
         _gemm(hbuf, m, blk.fc1, mlp, act=_lib.ISC_ACT_GELU, stream=stream)
         _gemm(mlp, m, blk.fc2, xa, residual=xb, stream=stream)
-    out = torch.empty((b, d), dtype=f32, device=dev)
-    st = lib.isc_layernorm(xa.data_ptr(), b, d, t * d, net.norm.weight.data_ptr(), net.norm.bias.data_ptr(), cfg.ln_eps,
-                           out.data_ptr(), _lib.ISC_F32, d, 0, stream)  # class-token rows only (row stride T * D)
+    return xa
+
+
+def _check_grid(net: PreparedViT, x: Tensor, grid: tuple[int, int]) -> None:
+    h, w = grid
+    p = net.cfg.patch_size
+    if h < 1 or w < 1 or h * w > net.cfg.grid**2:
+        raise ValueError(f"a token grid holds 1 .. {net.cfg.grid ** 2} patches, got {h} x {w}")
+    if x.ndim != 4 or tuple(x.shape[1:]) != (3, h * p, w * p):
+        raise ValueError(f"x must have shape [B, 3, {h * p}, {w * p}] for a {h} x {w} grid, got {tuple(x.shape)}")
+
+
+def forward_cls(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = None) -> Tensor:
+    """float32 `[B, 3, P h, P w]` (already preprocessed; `grid = (h, w)`, the native square grid by default) on a HIP
+    device -> float32 `[B, D]` class-token features."""
+    cfg = net.cfg
+    grid = (cfg.grid, cfg.grid) if grid is None else grid
+    _check_grid(net, x, grid)
+    b, d, t = x.shape[0], cfg.dim, grid[0] * grid[1] + 1
+    xa = _encode(net, x, grid)
+    out = torch.empty((b, d), dtype=torch.float32, device=x.device)
+    st = _lib.load().isc_layernorm(xa.data_ptr(), b, d, t * d, net.norm.weight.data_ptr(), net.norm.bias.data_ptr(),
+                                   cfg.ln_eps, out.data_ptr(), _lib.ISC_F32, d, 0,
+                                   _lib.stream_handle(x.device))  # class-token rows only (row stride T * D)
     _lib.check(st, "isc_layernorm")
     return out
 
 
-__all__ = ["VIT_B16", "ViTConfig", "forward_cls", "gemm_flops", "make_state_dict", "pack_rows", "prepare", "unpack_rows"]
+def forward_tokens(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = None, normalize: bool = False,
+                   out: Tensor | None = None) -> Tensor:
+    """float32 `[B, 3, P h, P w]` -> the float32 patch-token map `[B, D, h, w]`: cell `(i, j)` is token `1 + i w + j`
+    after the final LayerNorm, L2-normalised per cell (`F.normalize`, eps 1e-12) when `normalize` -- LayerNorm,
+    normalisation and the transposition into the channels-first map are one kernel (`isc_vit_tokens_out`).  `out`: a
+    contiguous `[B, D, h, w]` tensor to write into."""
+    cfg = net.cfg
+    grid = (cfg.grid, cfg.grid) if grid is None else grid
+    _check_grid(net, x, grid)
+    h, w = grid
+    b, d, t = x.shape[0], cfg.dim, h * w + 1
+    if out is None:
+        out = torch.empty((b, d, h, w), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (b, d, h, w) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"out must be a contiguous float32 [{b}, {d}, {h}, {w}] tensor on {x.device}")
+    xa = _encode(net, x, grid)
+    st = _lib.load().isc_vit_tokens_out(xa.data_ptr(), b, t, d, net.norm.weight.data_ptr(), net.norm.bias.data_ptr(),
+                                        cfg.ln_eps, int(normalize), 1e-12, out.data_ptr(), _lib.stream_handle(x.device))
+    _lib.check(st, "isc_vit_tokens_out")
+    return out
+
+
+__all__ = ["VIT_B16", "ViTConfig", "forward_cls", "forward_tokens", "gemm_flops", "make_state_dict", "pack_rows",
+           "position_table", "prepare", "token_grid", "unpack_rows"]

@@ -307,6 +307,20 @@ int isc_patchify_f16(const float* x, int B, int C, int H, int W, int patch, void
 int isc_vit_assemble(const float* patch_embed, const float* cls_token, const float* pos_embed, int B, int T, int D,
                      float* tokens, void* stream);
 
+/* Position table of an h x w token grid from the g x g one: out[0] = pos_embed[0] (class token); the patch rows, seen
+ * as [D, g, g], resampled to [D, h, w] by bicubic interpolation -- align_corners = False, no antialias, A = -0.75,
+ * source coordinate (dst + 0.5) * g / h - 0.5, tap indices clamped (torch.nn.functional.interpolate(mode="bicubic")).
+ * pos_embed float32 [1 + g * g, D], out float32 [1 + h * w, D]; D % 4 == 0, both pointers 16-byte aligned. */
+int isc_vit_pos_resample(const float* pos_embed, int g, int h, int w, int D, float* out, void* stream);
+
+/* The patch-token head: out[b][e][t - 1] = LayerNorm(tokens[b][t])[e] for t = 1 .. T - 1 (the class row of every image
+ * is skipped), each cell divided by max(||cell||_2, l2_eps) when normalize != 0 (F.normalize over the channel axis,
+ * the same bits as isc_l2norm_channels on the unnormalised map).  tokens float32 [B * T, D] row-major, out float32
+ * [B, D, T - 1]; LayerNorm as isc_layernorm (biased variance, float32 statistics).  T >= 2, D % 4 == 0, D <= 1024,
+ * all pointers 16-byte aligned. */
+int isc_vit_tokens_out(const float* tokens, int B, int T, int D, const float* gamma, const float* beta, float eps,
+                       int normalize, float l2_eps, float* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * PCA fit (reference src/imagescry/models/decomposition.py:118-131: mean, centring, SVD of the [N, F] rows on
  * the host).  The N-sized work runs here -- float64 feature sums, centred + transposed chunks, their F x F Gram matrices
