@@ -78,6 +78,15 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
          c_void_p],
     ),
     "isc_bank_unpack": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "isc_bank_append": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_int64, c_int64, c_int64, c_int, c_float, c_void_p, c_int, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "isc_bank_repack": (
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
     "isc_nchw_to_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "isc_conv2d_nhwc": (
         c_int,

@@ -1,6 +1,7 @@
 // Packing of embedding rows into the tile-contiguous, row-permuted bank layout (include/imagescry_hip.h:
 // isc_bank_pack, isc_bank_unpack, isc_bank_packed_bytes, isc_bank_permutation), and of a row filter into the same row
-// order (isc_row_mask_words, isc_row_mask_pack), and of row group codes (isc_row_groups_pack).
+// order (isc_row_mask_words, isc_row_mask_pack), and of row group codes (isc_row_groups_pack); in-place append to a bank
+// packed for a reserved capacity and its growth (isc_bank_append, isc_bank_repack).
 #include "bank_layout.h"
 #include "isc_common.h"
 
@@ -9,16 +10,12 @@ namespace {
 // One wave per row: optional L2 normalisation (float32, the F.normalize formula), cast, scatter the row's
 // 16-byte chunks to their K-step blocks at the row's PERMUTED position; columns past D are zero.  The norm of the
 // row AS STORED (after the cast) feeds `norm_bound` (atomic max): the search's rounding-error guard needs an upper
-// bound of the stored rows' norms.
+// bound of the stored rows' norms.  The body of k_bank_pack and k_bank_append: this wave stores source row `p` at packed
+// position `row`.
 template <typename TIN, typename TOUT>
-__global__ __launch_bounds__(256) void k_bank_pack(const TIN* __restrict__ x, int64_t n_rows, int d, int64_t ldx,
-                                                   int64_t first_row, IscPerm pm, int normalize, float eps,
-                                                   unsigned char* __restrict__ packed, int ks,
-                                                   unsigned* __restrict__ norm_bound) {
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= n_rows) return;
-    const int lane = threadIdx.x & 63;
-    const TIN* p = x + r * ldx;
+__device__ __forceinline__ void isc_pack_row(const TIN* __restrict__ p, int d, int64_t row, int normalize, float eps,
+                                             unsigned char* __restrict__ packed, int ks,
+                                             unsigned* __restrict__ norm_bound, int lane) {
     float denom = 1.f;
     if (normalize) {  // (element order of the sum: lane, lane + 64, ... -- kept as it was: the stored values depend on it)
         float acc = 0.f;
@@ -31,7 +28,6 @@ __global__ __launch_bounds__(256) void k_bank_pack(const TIN* __restrict__ x, in
     constexpr int PER_CHUNK = 16 / (int)sizeof(TOUT);
     constexpr int IN_VECS = PER_CHUNK * (int)sizeof(TIN) / 16;  // 16-byte input loads per output chunk: 1, 2, or 0 (f16 -> f32)
     const int chunks = ks * 8;
-    const int64_t row = isc_perm_pos(pm, first_row + r);
     // rows whose chunks can be fetched with 16-byte loads (a wave instruction then reads 1 KiB of the row instead of 64
     // scattered 2- or 4-byte elements)
     const bool vec_ok = IN_VECS > 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0);
@@ -73,6 +69,62 @@ __global__ __launch_bounds__(256) void k_bank_pack(const TIN* __restrict__ x, in
             const unsigned mine = nb == nb ? __float_as_uint(nb) : 0x7f800000u;
             if (mine > __hip_atomic_load(norm_bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(norm_bound, mine);
         }
+    }
+}
+
+template <typename TIN, typename TOUT>
+__global__ __launch_bounds__(256) void k_bank_pack(const TIN* __restrict__ x, int64_t n_rows, int d, int64_t ldx,
+                                                   int64_t first_row, IscPerm pm, int normalize, float eps,
+                                                   unsigned char* __restrict__ packed, int ks,
+                                                   unsigned* __restrict__ norm_bound) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n_rows) return;
+    isc_pack_row<TIN, TOUT>(x + r * ldx, d, isc_perm_pos(pm, first_row + r), normalize, eps, packed, ks, norm_bound,
+                            threadIdx.x & 63);
+}
+
+// In-place append to a bank laid out for `pm.n` = capacity rows (isc_bank_append): k_bank_pack's row, then the row's bit
+// in the fill bitmap -- an atomic OR: 32 positions share a word and other waves of the launch set its other bits -- and
+// its group code (negative -> -2, as k_row_groups_pack writes it).
+template <typename TIN, typename TOUT>
+__global__ __launch_bounds__(256) void k_bank_append(const TIN* __restrict__ x, int64_t n_rows, int d, int64_t ldx,
+                                                     int64_t first_row, IscPerm pm, int normalize, float eps,
+                                                     unsigned char* __restrict__ packed, int ks,
+                                                     unsigned* __restrict__ norm_bound, uint32_t* __restrict__ fill_mask,
+                                                     const int32_t* __restrict__ codes,
+                                                     int32_t* __restrict__ packed_codes) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n_rows) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t row = isc_perm_pos(pm, first_row + r);
+    isc_pack_row<TIN, TOUT>(x + r * ldx, d, row, normalize, eps, packed, ks, norm_bound, lane);
+    if (lane == 0) {
+        atomicOr(fill_mask + (row >> 5), 1u << (row & 31));
+        if (packed_codes) {
+            const int32_t c = codes[r];
+            packed_codes[row] = c < 0 ? -2 : c;
+        }
+    }
+}
+
+// Growth of an appendable bank (isc_bank_repack): one wave per ORIGINAL row moves the row's K-step segments, 16 bytes a
+// lane (8 lanes per 128-byte segment), from its position under the source permutation to its position under the
+// destination's, byte for byte; its group code moves with it and its fill bit is set.
+__global__ __launch_bounds__(256) void k_bank_repack(const unsigned char* __restrict__ src, IscPerm spm,
+                                                     unsigned char* __restrict__ dst, IscPerm dpm, int ks,
+                                                     int64_t first_row, int64_t n_rows,
+                                                     const int32_t* __restrict__ src_codes,
+                                                     int32_t* __restrict__ dst_codes, uint32_t* __restrict__ dst_fill) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n_rows) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t from = isc_perm_pos(spm, first_row + r), to = isc_perm_pos(dpm, first_row + r);
+    for (int c = lane; c < ks * 8; c += 64)
+        *reinterpret_cast<uint4*>(dst + isc_packed_offset(to, c >> 3, ks) + (c & 7) * 16) =
+            *reinterpret_cast<const uint4*>(src + isc_packed_offset(from, c >> 3, ks) + (c & 7) * 16);
+    if (lane == 0) {
+        atomicOr(dst_fill + (to >> 5), 1u << (to & 31));
+        if (dst_codes) dst_codes[to] = src_codes[from];
     }
 }
 
@@ -192,6 +244,54 @@ extern "C" int isc_bank_pack(const void* rows, int in_dtype, int64_t n_rows, int
     else if (in_dtype == ISC_F16 && dtype == ISC_F16) ISC_PACK(_Float16, _Float16);
     else ISC_PACK(_Float16, float);
 #undef ISC_PACK
+    return isc_launch_status();
+}
+
+extern "C" int isc_bank_append(const void* rows, int in_dtype, int64_t n_rows, int D, int64_t ldx, int64_t first_row,
+                               int64_t capacity, int normalize, float eps, void* packed, int dtype, float* norm_bound,
+                               uint32_t* fill_mask, const int32_t* codes, int32_t* packed_codes, void* stream) {
+    ISC_REQUIRE(rows && packed && fill_mask && check_dtype(in_dtype) && check_dtype(dtype));
+    ISC_REQUIRE(n_rows > 0 && D > 0 && ldx >= D && first_row >= 0);
+    ISC_REQUIRE(capacity >= first_row + n_rows && capacity <= 0x7ffffffe);
+    ISC_REQUIRE((codes == nullptr) == (packed_codes == nullptr));
+    if (!isc_aligned(packed, 16) || !isc_aligned(fill_mask, 4) || !isc_aligned(codes, 4) || !isc_aligned(packed_codes, 16))
+        return ISC_ERR_ALIGNMENT;
+    const int64_t blocks = isc_ceil_div<int64_t>(n_rows, 4);
+    if (blocks > 0x7fffffff) return ISC_ERR_UNSUPPORTED;
+    const int ks = isc_ksteps(D, dtype == ISC_F16 ? 2 : 4);
+    unsigned char* out = static_cast<unsigned char*>(packed);
+    hipStream_t s = isc_stream(stream);
+    const IscPerm pm = isc_make_perm(capacity);
+    const dim3 grid((unsigned)blocks), block(256);
+#define ISC_APPEND(TIN, TOUT)                                                                                         \
+    hipLaunchKernelGGL((k_bank_append<TIN, TOUT>), grid, block, 0, s, static_cast<const TIN*>(rows), n_rows, D, ldx, \
+                       first_row, pm, normalize, eps, out, ks, reinterpret_cast<unsigned*>(norm_bound), fill_mask,    \
+                       codes, packed_codes)
+    if (in_dtype == ISC_F32 && dtype == ISC_F16) ISC_APPEND(float, _Float16);
+    else if (in_dtype == ISC_F32 && dtype == ISC_F32) ISC_APPEND(float, float);
+    else if (in_dtype == ISC_F16 && dtype == ISC_F16) ISC_APPEND(_Float16, _Float16);
+    else ISC_APPEND(_Float16, float);
+#undef ISC_APPEND
+    return isc_launch_status();
+}
+
+extern "C" int isc_bank_repack(const void* src_packed, int64_t src_capacity, void* dst_packed, int64_t dst_capacity,
+                               int dtype, int D, int64_t first_row, int64_t n_rows, const int32_t* src_codes,
+                               int32_t* dst_codes, uint32_t* dst_fill_mask, void* stream) {
+    ISC_REQUIRE(src_packed && dst_packed && dst_fill_mask && src_packed != dst_packed && check_dtype(dtype));
+    ISC_REQUIRE(n_rows > 0 && D > 0 && first_row >= 0);
+    ISC_REQUIRE(src_capacity >= first_row + n_rows && dst_capacity >= first_row + n_rows);
+    ISC_REQUIRE(src_capacity <= 0x7ffffffe && dst_capacity <= 0x7ffffffe);
+    ISC_REQUIRE((src_codes == nullptr) == (dst_codes == nullptr));
+    if (!isc_aligned(src_packed, 16) || !isc_aligned(dst_packed, 16) || !isc_aligned(dst_fill_mask, 4) ||
+        !isc_aligned(src_codes, 4) || !isc_aligned(dst_codes, 16))
+        return ISC_ERR_ALIGNMENT;
+    const int64_t blocks = isc_ceil_div<int64_t>(n_rows, 4);
+    if (blocks > 0x7fffffff) return ISC_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_bank_repack, dim3((unsigned)blocks), dim3(256), 0, isc_stream(stream),
+                       static_cast<const unsigned char*>(src_packed), isc_make_perm(src_capacity),
+                       static_cast<unsigned char*>(dst_packed), isc_make_perm(dst_capacity),
+                       isc_ksteps(D, dtype == ISC_F16 ? 2 : 4), first_row, n_rows, src_codes, dst_codes, dst_fill_mask);
     return isc_launch_status();
 }
 

@@ -138,14 +138,16 @@ def _unpad_groups(scores: Tensor, indices: Tensor, labels: Tensor) -> tuple[Tens
 class RowFilter:
     """A set of allowed rows of ONE bank, made by `EmbeddingBank.row_filter`: the bitmap of this rank's rows in the bank's
     packed row order (`isc_row_mask_pack`) and the number of rows it allows (int64 [1], device).  Searches given it as
-    `mask=` answer as if the bank held the allowed rows only, with their indices in the whole bank."""
+    `mask=` answer as if the bank held the allowed rows only, with their indices in the whole bank.  A filter describes
+    the bank as it was when the filter was made: after `EmbeddingBank.append` or `reserve` it is refused."""
 
-    __slots__ = ("packed", "allowed_count", "_bank")
+    __slots__ = ("packed", "allowed_count", "_bank", "_revision")
 
-    def __init__(self, bank: "EmbeddingBank", packed: Tensor, allowed_count: Tensor) -> None:
-        self.packed = packed  # int32 [isc_row_mask_words(N_local)] (uint32 bit patterns); empty for a shard with no row
+    def __init__(self, bank: "EmbeddingBank", packed: Tensor, allowed_count: Tensor | None) -> None:
+        self.packed = packed  # int32 [isc_row_mask_words(capacity)] (uint32 bit patterns); empty for a shard with no row
         self.allowed_count = allowed_count
         self._bank = weakref.ref(bank)
+        self._revision = bank._revision
 
     def belongs_to(self, bank: "EmbeddingBank") -> bool:
         return self._bank() is bank
@@ -177,7 +179,20 @@ class EmbeddingBank:
         row_groups: optional integer group label of every row (e.g. its image id), sharded like `embeddings`: the full
             `[N]` with `presharded=False`, the shard's `[N_local]` with `presharded=True`.  Searches given
             `exclude_group=` labels per query then skip, for each query, the rows that carry its label.
+        capacity: lay the packed image out for this many rows (>= N; `embeddings` may then be `[0, D]`): `append` adds rows
+            in place, one launch each, until the capacity is used up.  `None` (default): no room is reserved.
     """
+
+    # An appendable bank (`capacity=`, `reserve`, `append`): the row count the packed image is laid out for (None: the
+    # number of rows, nothing reserved), the bitmap of the filled packed positions (isc_row_mask_words(capacity) words, the
+    # `mask` of every search while capacity > len) and the counter stale `RowFilter`s are told by.  Class-level defaults:
+    # a bank that never reserves carries none of it.
+    _capacity: int | None = None
+    _fill: Tensor | None = None
+    _fill_filter: RowFilter | None = None
+    _group_counts: Tensor | None = None
+    _revision = 0
+    _GROW_BLOCK = 1 << 20  # rows per isc_bank_pack / isc_bank_append / isc_bank_repack launch
 
     def __init__(
         self,
@@ -189,6 +204,7 @@ class EmbeddingBank:
         process_group: dist.ProcessGroup | None = None,
         presharded: bool = False,
         row_groups: Tensor | None = None,
+        capacity: int | None = None,
     ) -> None:
         if not isinstance(embeddings, Tensor) or not embeddings.dtype.is_floating_point:
             raise TypeError("embeddings must be a floating point torch.Tensor")
@@ -221,7 +237,16 @@ class EmbeddingBank:
         self.num_local_rows = int(embeddings.shape[0])
         if self.dim == 0:
             raise ValueError("embedding dimension must be positive")
-        self._bank = self._store(embeddings, normalize)
+        self.normalize = bool(normalize)
+        if capacity is None:
+            self._bank = self._store(embeddings, normalize)
+        else:
+            self._check_capacity(capacity)
+            self._norm_bound = torch.zeros(1, dtype=torch.float32, device=embeddings.device)
+            self._capacity = capacity
+            self._bank, self._fill, _ = self._alloc_image(capacity, embeddings.device, False)
+            self._fill_filter = RowFilter(self, self._fill, None)
+            self._append_rows(embeddings, 0, normalize, None)
         # search workspaces per LANE: -1 = the caller's stream (`search`), 0 / 1 = the two streams `search_async` alternates
         # between -- two searches in flight must not share a workspace
         self._workspaces: dict[int, dict[tuple[int, int], Tensor]] = {}
@@ -248,6 +273,7 @@ class EmbeddingBank:
             labels = row_groups.to(device=self.device, dtype=torch.int64)
             self.group_labels, codes, counts = torch.unique(labels, sorted=True, return_inverse=True, return_counts=True)
             self._max_group_rows = int(counts.max()) if counts.numel() else 0
+            self._group_counts = counts
             self._row_codes = self._pack_groups(codes.to(torch.int32).contiguous())
 
     # ------------------------------------------------------------------ construction
@@ -318,6 +344,197 @@ class EmbeddingBank:
                 _lib.check(st, "isc_bank_pack")
         return packed
 
+    # ------------------------------------------------------------------ reserved capacity and append
+    def _check_capacity(self, capacity: object) -> None:
+        if not isinstance(capacity, int) or isinstance(capacity, bool):
+            raise TypeError(f"capacity must be an int, got {type(capacity).__name__}")
+        if capacity < max(self.num_local_rows, 1):
+            raise ValueError(f"capacity={capacity} must be at least the bank's {self.num_local_rows} rows (and positive)")
+        if capacity > 0x7FFFFFFE:
+            raise ValueError(f"capacity={capacity} exceeds the packed layout's limit of {0x7FFFFFFE} rows")
+        if self.process_group is not None:
+            raise ValueError("a sharded bank (process_group=) cannot reserve capacity or append: its global indices are "
+                             "contiguous per rank and would shift")
+
+    def _alloc_image(self, capacity: int, device: torch.device, grouped: bool) -> tuple[Tensor, Tensor, Tensor | None]:
+        """The empty image of a `capacity`-row bank: (packed rows, all zero; fill bitmap, all zero; packed group codes, all
+        -2, when `grouped`).  A device hook, like `_store`."""
+        lib = _lib.load()
+        need, words = _lib.c_size_t(), _lib.c_size_t()
+        _lib.check(lib.isc_bank_packed_bytes(_lib.dtype_code(self.dtype), capacity, self.dim, need), "isc_bank_packed_bytes")
+        _lib.check(lib.isc_row_mask_words(capacity, words), "isc_row_mask_words")
+        packed = torch.zeros(need.value, dtype=torch.uint8, device=device)
+        fill = torch.zeros(words.value, dtype=torch.int32, device=device)
+        codes = torch.full(((capacity + 255) // 256 * 256,), -2, dtype=torch.int32, device=device) if grouped else None
+        return packed, fill, codes
+
+    def _append_rows(self, embeddings: Tensor, first_row: int, normalize: bool, codes: Tensor | None) -> None:
+        """`isc_bank_append` of `embeddings` as rows `[first_row, first_row + m)` of the image laid out for `capacity` rows
+        (one launch per 2^20 rows, on the current stream): the rows, their fill bits and -- `codes`: int32 `[m]` -- their
+        group codes.  A device hook."""
+        _lib.require_device(embeddings, "embeddings")
+        m, d = embeddings.shape
+        if embeddings.dtype not in (torch.float16, torch.float32):
+            embeddings = embeddings.float()
+        lib = _lib.load()
+        with torch.cuda.device(embeddings.device):
+            for r0 in range(0, m, self._GROW_BLOCK):
+                rows = embeddings[r0 : r0 + self._GROW_BLOCK]
+                if rows.stride(1) != 1:
+                    rows = rows.contiguous()
+                cs = None if codes is None else codes[r0 : r0 + self._GROW_BLOCK]
+                st = lib.isc_bank_append(
+                    rows.data_ptr(), _lib.dtype_code(rows.dtype), rows.shape[0], d, rows.stride(0), first_row + r0,
+                    self.capacity, int(normalize), 1e-12, self._bank.data_ptr(), _lib.dtype_code(self.dtype),
+                    self._norm_bound.data_ptr(), self._fill.data_ptr(), _lib.ptr(cs),
+                    None if cs is None else self._row_codes.data_ptr(), _lib.stream_handle(embeddings.device),
+                )
+                _lib.check(st, "isc_bank_append")
+
+    def _repack_rows(self, src: Tensor, src_capacity: int, src_codes: Tensor | None, dst: Tensor, dst_capacity: int,
+                     dst_codes: Tensor | None, dst_fill: Tensor) -> None:
+        """`isc_bank_repack` of every row of the bank from the image laid out for `src_capacity` rows into the (empty) one
+        laid out for `dst_capacity`, in blocks of 2^20 rows.  A device hook."""
+        lib = _lib.load()
+        with torch.cuda.device(dst.device):
+            for r0 in range(0, self.num_local_rows, self._GROW_BLOCK):
+                st = lib.isc_bank_repack(
+                    src.data_ptr(), src_capacity, dst.data_ptr(), dst_capacity, _lib.dtype_code(self.dtype), self.dim, r0,
+                    min(self._GROW_BLOCK, self.num_local_rows - r0), _lib.ptr(src_codes), _lib.ptr(dst_codes),
+                    dst_fill.data_ptr(), _lib.stream_handle(dst.device),
+                )
+                _lib.check(st, "isc_bank_repack")
+
+    def _wait_for_issued(self) -> None:
+        """Order the caller's current stream behind everything this bank has issued elsewhere: both lane streams of
+        `search_async` and the exchange stream.  An unresolved asynchronous search then never reads a half-updated image."""
+        if self.device.type != "cuda":
+            return
+        cur = torch.cuda.current_stream(self.device)
+        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        for stream in (*_LANE_STREAMS.get(idx, ()), self._xstream):
+            if stream is not None:
+                issued = torch.cuda.Event()
+                issued.record(stream)
+                cur.wait_event(issued)
+
+    def _relayout(self, capacity: int) -> None:
+        """Move the bank into a fresh image laid out for `capacity` rows (`isc_bank_repack`)."""
+        old = (self._bank, self._fill, self._row_codes)
+        packed, fill, codes = self._alloc_image(capacity, self.device, self.group_labels is not None)
+        if self.num_local_rows:
+            self._repack_rows(self._bank, self.capacity, self._row_codes, packed, capacity, codes, fill)
+        if self._captured_workspaces:
+            # a graph captured before the growth still holds the old pointers: a stale replay must read stale memory,
+            # never memory the allocator has handed to somebody else
+            self.__dict__.setdefault("_retired", []).append(old)
+        self._bank, self._fill, self._capacity = packed, fill, capacity
+        if self.group_labels is not None:
+            self._row_codes = codes
+        # sized by the image's row count
+        self._workspaces = {}
+        self._range_ws = None
+
+    def reserve(self, capacity: int) -> None:
+        """Lay the packed image out for `capacity >= len(self)` rows, so that `append` up to it works in place.  A no-op
+        when the image already holds that many; otherwise the rows move into a new image (`isc_bank_repack`: peak memory is
+        the old image plus the new one), which invalidates graphs captured on this bank.  `RowFilter`s made before the
+        call are refused afterwards."""
+        self._check_capacity(capacity)
+        if self._fill is None or capacity > self.capacity:
+            self._wait_for_issued()
+            self._relayout(capacity)
+        self._revision += 1
+        self._fill_filter = RowFilter(self, self._fill, None)
+
+    def append(self, rows: Tensor, *, row_groups: Tensor | None = None, row_origin: Tensor | None = None,
+               normalize: bool | None = None) -> range:
+        """Add `rows` (floating `[m, D]`, on the bank's device) to the bank and return the global indices they received,
+        `range(index_base + len_before, index_base + len_after)`.  Searches issued afterwards see them.
+
+        Within the reserved capacity (`capacity=`, `reserve`) this is ONE launch that touches only the new rows
+        (`isc_bank_append`): the packed image, the fill bitmap and the norm bound are updated in place, no pointer and no
+        size changes, so a `search` captured into a graph before the append replays over the new rows.  The bank then
+        equals, bit for bit in every search, the bank built from all the rows at once: it is that bank's rows in an image
+        laid out for `capacity` rows, searched through the bitmap of the filled positions.
+
+        Past the capacity the bank first grows to `max(2 * capacity, len + m)` rows: every row moves into a new image
+        (`isc_bank_repack`, byte for byte).  Peak memory during a growth is the old image plus the new one.  A growth
+        invalidates graphs captured on this bank (a bank that has seen a capture keeps the old image alive, so a stale
+        replay reads stale rows, not freed memory) and drops the cached search workspaces.
+
+        `row_groups` (integer `[m]`) is required iff the bank has row groups, `row_origin` (`[m, 3]`) iff it has one;
+        `normalize` defaults to the bank's own setting.  Labels not seen before are merged into the sorted `group_labels`
+        (the stored codes are re-mapped on the device; a grouped append reads one group count back to the host).
+
+        Runs on the caller's current stream, ordered behind everything the bank has issued on its own streams
+        (unresolved `search_async` handles see the bank as it was).  `RowFilter`s made before the call are refused
+        afterwards: make them again.  A sharded bank (`process_group=`) cannot append."""
+        if self.process_group is not None:
+            raise ValueError("a sharded bank (process_group=) cannot append: its global indices are contiguous per rank "
+                             "and would shift")
+        if not isinstance(rows, Tensor) or not rows.dtype.is_floating_point:
+            raise TypeError("rows must be a floating point torch.Tensor")
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"rows must have shape [m, {self.dim}], got {tuple(rows.shape)}")
+        if rows.device != self.device:
+            raise ValueError(f"rows are on {rows.device} but the bank is on {self.device}")
+        m = int(rows.shape[0])
+        if (row_groups is not None) != (self.group_labels is not None):
+            raise ValueError("row_groups must be given iff the bank was built with row groups")
+        if row_groups is not None:
+            dt = row_groups.dtype if isinstance(row_groups, Tensor) else None
+            if dt is None or dt.is_floating_point or dt.is_complex or dt == torch.bool:
+                raise TypeError("row_groups must be an integer torch.Tensor")
+            if row_groups.shape != (m,):
+                raise ValueError(f"row_groups must have shape [{m}] (one label per row), got {tuple(row_groups.shape)}")
+        if (row_origin is not None) != (self.row_origin is not None):
+            raise ValueError("row_origin must be given iff the bank has one (EmbeddingBank.from_database)")
+        if row_origin is not None and (not isinstance(row_origin, Tensor) or row_origin.shape != (m, 3)):
+            raise ValueError(f"row_origin must be a tensor of shape [{m}, 3] (image_id, h, w)")
+        first = self.num_local_rows
+        if m == 0:
+            return range(self.index_base + first, self.index_base + first)
+        if first + m > 0x7FFFFFFE:
+            raise ValueError(f"{first + m} rows exceed the packed layout's limit of {0x7FFFFFFE}")
+        self._wait_for_issued()
+        if self._fill is None or first + m > self.capacity:
+            self._relayout(max(2 * self.capacity, first + m))
+        codes = None
+        if row_groups is not None:
+            codes = self._merge_labels(row_groups.to(device=self.device, dtype=torch.int64))
+        self._append_rows(rows, first, self.normalize if normalize is None else bool(normalize), codes)
+        self.num_local_rows = first + m
+        if row_origin is not None:
+            self.row_origin = torch.cat([self.row_origin, row_origin.to(device=self.row_origin.device,
+                                                                        dtype=self.row_origin.dtype)])
+        self._revision += 1
+        self._fill_filter = RowFilter(self, self._fill, None)
+        return range(self.index_base + first, self.index_base + first + m)
+
+    def _merge_labels(self, new: Tensor) -> Tensor:
+        """The int32 codes of an append's labels after merging them into `group_labels`, which stays sorted: a code is the
+        label's position in it, so labels not seen before re-map the stored codes -- in place, through the old -> new
+        position table, -2 kept -- before the launch.  Updates `_max_group_rows` (the one host read of a grouped append)."""
+        old = self.group_labels
+        merged = torch.unique(torch.cat([old, new]), sorted=True)
+        counts = self._group_counts
+        if counts is None:  # (a bare bank whose codes were set by hand)
+            c = self._row_codes[self._row_codes >= 0].long()
+            counts = torch.bincount(c, minlength=old.numel())
+        if merged.numel() != old.numel():
+            table = torch.searchsorted(merged, old)
+            stored = self._row_codes
+            if old.numel():
+                stored.copy_(torch.where(stored >= 0, table.to(torch.int32)[stored.clamp(min=0).long()], stored))
+            counts = torch.zeros(merged.numel(), dtype=counts.dtype, device=counts.device).index_add_(0, table, counts)
+            self.group_labels = merged
+        codes = torch.searchsorted(merged, new)
+        counts = counts + torch.bincount(codes, minlength=merged.numel())
+        self._group_counts = counts
+        self._max_group_rows = int(counts.max())
+        return codes.to(torch.int32).contiguous()
+
     # ------------------------------------------------------------------ properties
     @property
     def device(self) -> torch.device:
@@ -331,7 +548,7 @@ class EmbeddingBank:
             lib = _lib.load()
             with torch.cuda.device(self.device):
                 st = lib.isc_bank_unpack(
-                    self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.dim, self.num_local_rows, 0,
+                    self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.dim, self.capacity, 0,
                     self.num_local_rows, out.data_ptr(), self.dim, _lib.stream_handle(self.device),
                 )
             _lib.check(st, "isc_bank_unpack")
@@ -339,6 +556,12 @@ class EmbeddingBank:
 
     def __len__(self) -> int:
         return self.num_local_rows
+
+    @property
+    def capacity(self) -> int:
+        """The row count the packed image is laid out for: `len(self)` unless room was reserved (`capacity=`, `reserve`,
+        or the growth of an `append`)."""
+        return self.num_local_rows if self._capacity is None else self._capacity
 
     # ------------------------------------------------------------------ row filters
     def _global_rows(self) -> int | None:
@@ -395,9 +618,9 @@ class EmbeddingBank:
         return self._pack_filter(keep[self.index_base : self.index_base + self.num_local_rows])
 
     def _pack_filter(self, local: Tensor) -> RowFilter:
-        """`isc_row_mask_pack` of this rank's bool `[N_local]` rows."""
+        """`isc_row_mask_pack` of this rank's bool `[N_local]` rows (zero-padded to the capacity the image is laid out for)."""
         count = torch.zeros(1, dtype=torch.int64, device=self.device)
-        n = self.num_local_rows
+        n = self.capacity
         if n == 0:
             return RowFilter(self, torch.empty(0, dtype=torch.int32, device=self.device), count)
         lib = _lib.load()
@@ -405,6 +628,8 @@ class EmbeddingBank:
         _lib.check(lib.isc_row_mask_words(n, words), "isc_row_mask_words")
         packed = torch.empty(words.value, dtype=torch.int32, device=self.device)
         allow = local.to(torch.uint8).contiguous()
+        if n > allow.shape[0]:  # the reserved room past the last row is never allowed
+            allow = torch.nn.functional.pad(allow, (0, n - allow.shape[0]))
         with torch.cuda.device(self.device):
             st = lib.isc_row_mask_pack(allow.data_ptr(), n, packed.data_ptr(), count.data_ptr(),
                                        _lib.stream_handle(self.device))
@@ -412,11 +637,13 @@ class EmbeddingBank:
         return RowFilter(self, packed, count)
 
     def _as_filter(self, mask: "RowFilter | Tensor | None") -> RowFilter | None:
-        if mask is None:
-            return None
+        if mask is None:  # a bank with spare capacity searches its filled rows: the fill bitmap is the filter
+            return self._fill_filter if self.num_local_rows < self.capacity else None
         if isinstance(mask, RowFilter):
             if not mask.belongs_to(self):
                 raise ValueError("this RowFilter belongs to another EmbeddingBank")
+            if mask._revision != self._revision:
+                raise ValueError("this RowFilter was made before the bank changed; make it again")
             return mask
         if isinstance(mask, Tensor):
             return self.row_filter(mask)
@@ -424,10 +651,13 @@ class EmbeddingBank:
 
     # ------------------------------------------------------------------ row groups
     def _pack_groups(self, codes: Tensor) -> Tensor:
-        """`isc_row_groups_pack` of this rank's int32 `[N_local]` row codes: int32 `[ceil(N_local / 256) * 256]`."""
-        n = self.num_local_rows
+        """`isc_row_groups_pack` of this rank's int32 `[N_local]` row codes: int32 `[ceil(N_local / 256) * 256]` (of the
+        capacity the image is laid out for, the rows past `N_local` coded -2 like the padding)."""
+        n = self.capacity
         if n == 0:
             return torch.empty(0, dtype=torch.int32, device=self.device)
+        if n > codes.shape[0]:
+            codes = torch.nn.functional.pad(codes, (0, n - codes.shape[0]), value=-2)
         packed = torch.empty((n + 255) // 256 * 256, dtype=torch.int32, device=self.device)
         lib = _lib.load()
         with torch.cuda.device(self.device):
@@ -493,12 +723,12 @@ class EmbeddingBank:
             need = _lib.c_size_t()
             if collapse:
                 st = lib.isc_cosine_topk_collapse_workspace_bytes(
-                    _lib.dtype_code(self.dtype), self.num_local_rows, self.dim, min(key[0], _lib.ISC_SEARCH_PASS_QUERIES),
+                    _lib.dtype_code(self.dtype), self.capacity, self.dim, min(key[0], _lib.ISC_SEARCH_PASS_QUERIES),
                     k, max(self._max_group_rows, 1), need)
                 _lib.check(st, "isc_cosine_topk_collapse_workspace_bytes")
             else:
                 st = lib.isc_cosine_topk_workspace_bytes(
-                    _lib.dtype_code(self.dtype), self.num_local_rows, self.dim, min(key[0], _lib.ISC_SEARCH_PASS_QUERIES), k,
+                    _lib.dtype_code(self.dtype), self.capacity, self.dim, min(key[0], _lib.ISC_SEARCH_PASS_QUERIES), k,
                     need
                 )
                 _lib.check(st, "isc_cosine_topk_workspace_bytes")
@@ -545,7 +775,7 @@ class EmbeddingBank:
         lib = _lib.load()
         with torch.cuda.device(self.device):
             args = (
-                self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.num_local_rows, self.dim, queries.data_ptr(),
+                self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.capacity, self.dim, queries.data_ptr(),
                 _lib.dtype_code(queries.dtype), nq, queries.stride(0), k, self.index_base, self._norm_bound.data_ptr(),
                 scores.data_ptr(),
                 indices.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -581,7 +811,7 @@ class EmbeddingBank:
         code = _lib.dtype_code(self.dtype)
         need = _lib.c_size_t()
         _lib.check(
-            lib.isc_cosine_topk_exhaustive_workspace_bytes(code, self.num_local_rows, self.dim, nq, k, need),
+            lib.isc_cosine_topk_exhaustive_workspace_bytes(code, self.capacity, self.dim, nq, k, need),
             "isc_cosine_topk_exhaustive_workspace_bytes",
         )
         ews = torch.empty(need.value, dtype=torch.uint8, device=self.device)
@@ -589,7 +819,7 @@ class EmbeddingBank:
         indices = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
             args = (
-                self._bank.data_ptr(), code, self.num_local_rows, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
+                self._bank.data_ptr(), code, self.capacity, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
                 q.stride(0), k, self.index_base, scores.data_ptr(), indices.data_ptr(), ews.data_ptr(), ews.numel(),
             )
             if qg is not None:
@@ -846,7 +1076,7 @@ class EmbeddingBank:
         lib = _lib.load()
         with torch.cuda.device(self.device):
             st = lib.isc_cosine_topk_collapse(
-                self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.num_local_rows, self.dim, queries.data_ptr(),
+                self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.capacity, self.dim, queries.data_ptr(),
                 _lib.dtype_code(queries.dtype), nq, queries.stride(0), k, self.index_base, self._norm_bound.data_ptr(),
                 scores.data_ptr(), indices.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
                 None if mask is None else mask.packed.data_ptr(), self._row_codes.data_ptr(),
@@ -980,7 +1210,7 @@ class EmbeddingBank:
         lib = _lib.load()
         code = _lib.dtype_code(self.dtype)
         need = _lib.c_size_t()
-        _lib.check(lib.isc_cosine_topk_exhaustive_collapse_workspace_bytes(code, self.num_local_rows, self.dim, nq, k,
+        _lib.check(lib.isc_cosine_topk_exhaustive_collapse_workspace_bytes(code, self.capacity, self.dim, nq, k,
                                                                            need),
                    "isc_cosine_topk_exhaustive_collapse_workspace_bytes")
         ews = torch.empty(need.value, dtype=torch.uint8, device=self.device)
@@ -989,7 +1219,7 @@ class EmbeddingBank:
         codes = torch.empty((nq, k), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
             st = lib.isc_cosine_topk_exhaustive_collapse(
-                self._bank.data_ptr(), code, self.num_local_rows, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
+                self._bank.data_ptr(), code, self.capacity, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
                 q.stride(0), k, self.index_base, scores.data_ptr(), indices.data_ptr(), ews.data_ptr(), ews.numel(),
                 None if rf is None else rf.packed.data_ptr(), self._row_codes.data_ptr(),
                 None if qg is None else qg.data_ptr(), codes.data_ptr(), _lib.stream_handle(self.device),
@@ -1024,7 +1254,7 @@ class EmbeddingBank:
         nq = q.shape[0]
         code = _lib.dtype_code(self.dtype)
         need = _lib.c_size_t()
-        _lib.check(lib.isc_cosine_range_workspace_bytes(code, self.num_local_rows, self.dim, nq, capacity, need),
+        _lib.check(lib.isc_cosine_range_workspace_bytes(code, self.capacity, self.dim, nq, capacity, need),
                    "isc_cosine_range_workspace_bytes")
         if self._range_ws is None or self._range_ws.numel() < need.value:
             self._range_ws = None
@@ -1037,7 +1267,7 @@ class EmbeddingBank:
         status = torch.empty(4, dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
             args = (
-                self._bank.data_ptr(), code, self.num_local_rows, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
+                self._bank.data_ptr(), code, self.capacity, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
                 q.stride(0), thr.data_ptr(), self.index_base, self._norm_bound.data_ptr(), capacity,
                 offsets.data_ptr(), scores.data_ptr(), indices.data_ptr(), needed.data_ptr(), status.data_ptr(),
                 ws.data_ptr(), ws.numel(),

@@ -152,6 +152,30 @@ int isc_bank_pack(const void* rows, int in_dtype, int64_t n_rows, int D, int64_t
 int isc_bank_unpack(const void* packed, int dtype, int D, int64_t n_total, int64_t first_row, int64_t n_rows,
                     void* rows, int64_t ldy, void* stream);
 
+/* In-place append to a bank packed for a reserved capacity: rows [first_row, first_row + n_rows) of a bank laid out for
+ * `capacity` >= first_row + n_rows rows, in one launch (no host synchronisation; capturable).  The stored bytes and the
+ * norm_bound update are isc_bank_pack's with n_total = capacity (one kernel body).  A bank packed for `capacity` rows and
+ * searched through `fill_mask` (the masked searches) answers as the bank of the filled rows alone, bit for bit, so an
+ * append touches only the new rows.
+ *   fill_mask     uint32 [isc_row_mask_words(capacity)], 4-byte aligned: the bit of every stored row's packed position is
+ *                 set with an atomic OR (zero it before the first call)
+ *   codes         optional int32 [n_rows], the new rows' group codes; written to packed_codes[position], a negative code
+ *                 as -2 (isc_row_groups_pack's convention)
+ *   packed_codes  int32 [ceil(capacity / 256) * 256], 16-byte aligned, filled with -2 before the first call; NULL iff
+ *                 `codes` is NULL (exactly one of the two NULL: ISC_ERR_INVALID_ARG) */
+int isc_bank_append(const void* rows, int in_dtype, int64_t n_rows, int D, int64_t ldx, int64_t first_row,
+                    int64_t capacity, int normalize, float eps, void* packed, int dtype, float* norm_bound,
+                    uint32_t* fill_mask, const int32_t* codes, int32_t* packed_codes, void* stream);
+
+/* Growth of such a bank without a row-major detour: ORIGINAL rows [first_row, first_row + n_rows) move from their
+ * positions in the image packed for `src_capacity` rows to their positions in the image packed for `dst_capacity` rows,
+ * byte for byte (stored values are untouched, so norm_bound carries over), one launch.  Their group codes move with them
+ * (src_codes / dst_codes: both or neither) and their bits are set in dst_fill_mask.  The caller pre-fills dst_packed and
+ * dst_fill_mask with zeros and dst_codes with -2; the two images must not overlap. */
+int isc_bank_repack(const void* src_packed, int64_t src_capacity, void* dst_packed, int64_t dst_capacity, int dtype, int D,
+                    int64_t first_row, int64_t n_rows, const int32_t* src_codes, int32_t* dst_codes,
+                    uint32_t* dst_fill_mask, void* stream);
+
 /* Row filter of the masked searches (isc_cosine_topk_masked, isc_cosine_topk_exhaustive_masked, isc_cosine_range_masked):
  * a bitmap in the PACKED row order of an N-row bank.  Bit p of word p / 32 allows packed position p, i.e. ORIGINAL row
  * (mul * p) mod N (isc_bank_permutation); the bank's padding to 256-row tiles is included and its bits are 0, so one
