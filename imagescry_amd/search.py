@@ -30,6 +30,7 @@ from __future__ import annotations
 
 import math
 import weakref
+from contextlib import nullcontext
 from dataclasses import dataclass
 from os import PathLike
 from typing import Sequence
@@ -135,6 +136,37 @@ def _unpad_groups(scores: Tensor, indices: Tensor, labels: Tensor) -> tuple[Tens
     return scores.masked_fill(pad, -math.inf), indices.masked_fill(pad, -1), labels.masked_fill(pad, -1)
 
 
+def _check_labels(labels: object, name: str, n: int, shape: str, got: bool = False) -> None:
+    """`labels` must be an integer tensor of shape `[n]`; `shape` is how the message words that, and `got` says whether
+    the type errors name what came instead."""
+    if not isinstance(labels, Tensor):
+        raise TypeError(f"{name} must be an integer torch.Tensor" + (f", got {type(labels).__name__}" if got else ""))
+    dt = labels.dtype
+    if dt.is_floating_point or dt.is_complex or dt == torch.bool:
+        raise TypeError(f"{name} must be an integer tensor, got {dt}" if got else f"{name} must be an integer torch.Tensor")
+    if labels.shape != (n,):
+        raise ValueError(f"{name} must have shape {shape}, got {tuple(labels.shape)}")
+
+
+def _exchange_layout(nq: int, k: int, with_labels: bool = False):
+    """The exchange buffer of a sharded search, `[scores f32 Q*k | pad to 8 | indices i64 Q*k | (labels i64 Q*k) | status
+    i32 x4]`: its size in bytes and `views(buf)`, the `(scores, indices, (labels,) status)` planes of one rank's uint8
+    `[nbytes]` buffer (`[Q, k]` each, status `[4]`) or of the all-gathered `[G, nbytes]` one (`[G, Q, k]`, `[G, 4]`).  The
+    search kernels write the planes in place, ONE collective gathers them and the merge kernel reads them in place."""
+    n = nq * k
+    off_i = (4 * n + 7) // 8 * 8
+    off_s = off_i + (16 if with_labels else 8) * n
+
+    def views(buf: Tensor) -> tuple[Tensor, ...]:
+        lead = buf.shape[:-1]
+        planes = [buf[..., : 4 * n].view(torch.float32).view(*lead, nq, k)]
+        for lo in (off_i, off_i + 8 * n)[: 2 if with_labels else 1]:
+            planes.append(buf[..., lo : lo + 8 * n].view(torch.int64).view(*lead, nq, k))
+        return (*planes, buf[..., off_s:].view(torch.int32))
+
+    return off_s + 16, views
+
+
 class RowFilter:
     """A set of allowed rows of ONE bank, made by `EmbeddingBank.row_filter`: the bitmap of this rank's rows in the bank's
     packed row order (`isc_row_mask_pack`) and the number of rows it allows (int64 [1], device).  Searches given it as
@@ -193,6 +225,7 @@ class EmbeddingBank:
     _group_counts: Tensor | None = None
     _revision = 0
     _GROW_BLOCK = 1 << 20  # rows per isc_bank_pack / isc_bank_append / isc_bank_repack launch
+    _n_total: int | None = None  # rows of the whole sharded bank, learnt by `_global_rows`
 
     def __init__(
         self,
@@ -216,12 +249,8 @@ class EmbeddingBank:
         self.world_size = dist.get_world_size(process_group) if process_group is not None else 1
         self.rank = dist.get_rank(process_group) if process_group is not None else 0
         if row_groups is not None:
-            if not isinstance(row_groups, Tensor) or row_groups.dtype.is_floating_point or row_groups.dtype.is_complex \
-                    or row_groups.dtype == torch.bool:
-                raise TypeError("row_groups must be an integer torch.Tensor")
-            if row_groups.shape != (embeddings.shape[0],):
-                raise ValueError(f"row_groups must have shape [{embeddings.shape[0]}] (one label per row of embeddings), "
-                                 f"got {tuple(row_groups.shape)}")
+            n = embeddings.shape[0]
+            _check_labels(row_groups, "row_groups", n, f"[{n}] (one label per row of embeddings)")
         if process_group is not None and not presharded:
             lo, hi = shard_bounds(embeddings.shape[0], self.world_size, self.rank)
             embeddings = embeddings[lo:hi]
@@ -328,14 +357,8 @@ class EmbeddingBank:
         packed = torch.empty(need.value, dtype=torch.uint8, device=embeddings.device)
         tile_bytes = need.value // ((n + 255) // 256)
         packed[-tile_bytes:].zero_()  # padding rows of the last tile (isc_bank_pack writes real rows only)
-        if embeddings.dtype not in (torch.float16, torch.float32):
-            embeddings = embeddings.float()
-        block = 1 << 20
         with torch.cuda.device(embeddings.device):
-            for r0 in range(0, n, block):
-                rows = embeddings[r0 : r0 + block]
-                if rows.stride(1) != 1:
-                    rows = rows.contiguous()
+            for r0, rows in self._row_blocks(embeddings):
                 st = lib.isc_bank_pack(
                     rows.data_ptr(), _lib.dtype_code(rows.dtype), rows.shape[0], d, rows.stride(0), r0, n,
                     int(normalize), 1e-12, packed.data_ptr(), code, self._norm_bound.data_ptr(),
@@ -343,6 +366,15 @@ class EmbeddingBank:
                 )
                 _lib.check(st, "isc_bank_pack")
         return packed
+
+    def _row_blocks(self, embeddings: Tensor):
+        """`(r0, rows)` for every `_GROW_BLOCK` rows of `embeddings` from row `r0` on, float16 or float32 with unit inner
+        stride: the input of one `isc_bank_pack` / `isc_bank_append` launch."""
+        if embeddings.dtype not in (torch.float16, torch.float32):
+            embeddings = embeddings.float()
+        for r0 in range(0, embeddings.shape[0], self._GROW_BLOCK):
+            rows = embeddings[r0 : r0 + self._GROW_BLOCK]
+            yield r0, rows if rows.stride(1) == 1 else rows.contiguous()
 
     # ------------------------------------------------------------------ reserved capacity and append
     def _check_capacity(self, capacity: object) -> None:
@@ -373,15 +405,10 @@ class EmbeddingBank:
         (one launch per 2^20 rows, on the current stream): the rows, their fill bits and -- `codes`: int32 `[m]` -- their
         group codes.  A device hook."""
         _lib.require_device(embeddings, "embeddings")
-        m, d = embeddings.shape
-        if embeddings.dtype not in (torch.float16, torch.float32):
-            embeddings = embeddings.float()
+        d = embeddings.shape[1]
         lib = _lib.load()
         with torch.cuda.device(embeddings.device):
-            for r0 in range(0, m, self._GROW_BLOCK):
-                rows = embeddings[r0 : r0 + self._GROW_BLOCK]
-                if rows.stride(1) != 1:
-                    rows = rows.contiguous()
+            for r0, rows in self._row_blocks(embeddings):
                 cs = None if codes is None else codes[r0 : r0 + self._GROW_BLOCK]
                 st = lib.isc_bank_append(
                     rows.data_ptr(), _lib.dtype_code(rows.dtype), rows.shape[0], d, rows.stride(0), first_row + r0,
@@ -483,11 +510,7 @@ class EmbeddingBank:
         if (row_groups is not None) != (self.group_labels is not None):
             raise ValueError("row_groups must be given iff the bank was built with row groups")
         if row_groups is not None:
-            dt = row_groups.dtype if isinstance(row_groups, Tensor) else None
-            if dt is None or dt.is_floating_point or dt.is_complex or dt == torch.bool:
-                raise TypeError("row_groups must be an integer torch.Tensor")
-            if row_groups.shape != (m,):
-                raise ValueError(f"row_groups must have shape [{m}] (one label per row), got {tuple(row_groups.shape)}")
+            _check_labels(row_groups, "row_groups", m, f"[{m}] (one label per row)")
         if (row_origin is not None) != (self.row_origin is not None):
             raise ValueError("row_origin must be given iff the bank has one (EmbeddingBank.from_database)")
         if row_origin is not None and (not isinstance(row_origin, Tensor) or row_origin.shape != (m, 3)):
@@ -570,7 +593,7 @@ class EmbeddingBank:
         size only the caller knows."""
         if self.process_group is None:
             return None if self.presharded else self.num_local_rows
-        if not hasattr(self, "_n_total"):
+        if self._n_total is None:
             self._n_total = self._total_rows()
         return self._n_total
 
@@ -670,13 +693,7 @@ class EmbeddingBank:
         `group_labels`, -1 for a label no row of the rank carries.  Tensor ops only: no host synchronisation."""
         if exclude_group is None:
             return None
-        if not isinstance(exclude_group, Tensor):
-            raise TypeError(f"exclude_group must be an integer torch.Tensor, got {type(exclude_group).__name__}")
-        dt = exclude_group.dtype
-        if dt.is_floating_point or dt.is_complex or dt == torch.bool:
-            raise TypeError(f"exclude_group must be an integer tensor, got {dt}")
-        if exclude_group.shape != (nq,):
-            raise ValueError(f"exclude_group must have shape [Q] = [{nq}], got {tuple(exclude_group.shape)}")
+        _check_labels(exclude_group, "exclude_group", nq, f"[Q] = [{nq}]", got=True)
         if self.group_labels is None:
             raise ValueError("exclude_group needs row groups: build the bank with row_groups= (or from_database)")
         x = exclude_group.to(device=self.device, dtype=torch.int64)
@@ -714,8 +731,7 @@ class EmbeddingBank:
 
         `collapse`: the workspace of the collapsed search (`isc_cosine_topk_collapse_workspace_bytes`), cached apart."""
         nq = min(n_queries, _lib.ISC_SEARCH_PASS_QUERIES)
-        key = (-(-nq // 64) * 64 if nq <= 128 else -(-nq // 256) * 256, k) if not collapse else \
-            (-(-nq // 64) * 64 if nq <= 128 else -(-nq // 256) * 256, k, "collapse")
+        key = (-(-nq // 64) * 64 if nq <= 128 else -(-nq // 256) * 256, k) + (("collapse",) if collapse else ())
         cache = self._workspaces.setdefault(lane, {})
         ws = cache.get(key)
         if ws is None:
@@ -741,6 +757,28 @@ class EmbeddingBank:
                 self._captured_workspaces.append(ws)
         return ws
 
+    def _new_out(self, nq: int, k: int) -> tuple[Tensor, Tensor, Tensor]:
+        """What a local search writes when the caller gave no `out`: (scores [Q, k], indices [Q, k], status int32[4])."""
+        return (torch.empty((nq, k), dtype=torch.float32, device=self.device),
+                torch.empty((nq, k), dtype=torch.int64, device=self.device),
+                torch.empty(4, dtype=torch.int32, device=self.device))
+
+    def _row_search(self, base: str, args: tuple, mask: RowFilter | None, groups: Tensor | None, stream: int) -> None:
+        """One row-search call of the C ABI on `stream` (a raw handle): `base` itself, `base_masked` with the row filter's
+        bitmap, or -- `groups`: int32 `[Q]` query codes -- `base_grouped` with the bitmap (or NULL), the packed row codes
+        and the query codes, each behind the arguments `args` the three share."""
+        if groups is not None:
+            name = base + "_grouped"
+            args += (None if mask is None else mask.packed.data_ptr(), self._row_codes.data_ptr(), groups.data_ptr())
+        elif mask is not None:
+            name = base + "_masked"
+            args += (mask.packed.data_ptr(),)
+        else:
+            name = base
+        with torch.cuda.device(self.device):
+            st = getattr(_lib.load(), name)(*args, stream)
+        _lib.check(st, name)
+
     def _local_topk(
         self, queries: Tensor, k: int, out: tuple[Tensor, Tensor, Tensor] | None = None, lane: int = -1,
         stream: "torch.cuda.Stream | None" = None, mask: RowFilter | None = None, groups: Tensor | None = None,
@@ -754,12 +792,7 @@ class EmbeddingBank:
         `groups`: int32 `[Q]` query codes (`_query_codes`): query q skips the rows of its group (`isc_cosine_topk_grouped`),
         with the masked search's padding."""
         nq = queries.shape[0]
-        if out is None:
-            scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            indices = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-            status = torch.empty(4, dtype=torch.int32, device=self.device)
-        else:
-            scores, indices, status = out
+        scores, indices, status = out if out is not None else self._new_out(nq, k)
         ws = self._workspace(nq, k, lane)
         if stream is not None:
             # every tensor this call touches was allocated on some other stream: tell the allocator the lane uses it, so
@@ -772,25 +805,13 @@ class EmbeddingBank:
             if groups is not None:
                 groups.record_stream(stream)
                 self._row_codes.record_stream(stream)
-        lib = _lib.load()
-        with torch.cuda.device(self.device):
-            args = (
-                self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.capacity, self.dim, queries.data_ptr(),
-                _lib.dtype_code(queries.dtype), nq, queries.stride(0), k, self.index_base, self._norm_bound.data_ptr(),
-                scores.data_ptr(),
-                indices.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
-            )
-            sh = stream.cuda_stream if stream is not None else _lib.stream_handle(self.device)
-            if groups is not None:
-                st = lib.isc_cosine_topk_grouped(*args, None if mask is None else mask.packed.data_ptr(),
-                                                 self._row_codes.data_ptr(), groups.data_ptr(), sh)
-                _lib.check(st, "isc_cosine_topk_grouped")
-            elif mask is None:
-                st = lib.isc_cosine_topk(*args, sh)
-                _lib.check(st, "isc_cosine_topk")
-            else:
-                st = lib.isc_cosine_topk_masked(*args, mask.packed.data_ptr(), sh)
-                _lib.check(st, "isc_cosine_topk_masked")
+        args = (
+            self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.capacity, self.dim, queries.data_ptr(),
+            _lib.dtype_code(queries.dtype), nq, queries.stride(0), k, self.index_base, self._norm_bound.data_ptr(),
+            scores.data_ptr(), indices.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+        )
+        self._row_search("isc_cosine_topk", args, mask, groups,
+                         stream.cuda_stream if stream is not None else _lib.stream_handle(self.device))
         self.last_status = status
         return scores, indices
 
@@ -817,20 +838,11 @@ class EmbeddingBank:
         ews = torch.empty(need.value, dtype=torch.uint8, device=self.device)
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         indices = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            args = (
-                self._bank.data_ptr(), code, self.capacity, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
-                q.stride(0), k, self.index_base, scores.data_ptr(), indices.data_ptr(), ews.data_ptr(), ews.numel(),
-            )
-            if qg is not None:
-                st = lib.isc_cosine_topk_exhaustive_grouped(*args, None if rf is None else rf.packed.data_ptr(),
-                                                            self._row_codes.data_ptr(), qg.data_ptr(),
-                                                            _lib.stream_handle(self.device))
-            elif rf is None:
-                st = lib.isc_cosine_topk_exhaustive(*args, _lib.stream_handle(self.device))
-            else:
-                st = lib.isc_cosine_topk_exhaustive_masked(*args, rf.packed.data_ptr(), _lib.stream_handle(self.device))
-        _lib.check(st, "isc_cosine_topk_exhaustive" + ("_grouped" if qg is not None else "" if rf is None else "_masked"))
+        args = (
+            self._bank.data_ptr(), code, self.capacity, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
+            q.stride(0), k, self.index_base, scores.data_ptr(), indices.data_ptr(), ews.data_ptr(), ews.numel(),
+        )
+        self._row_search("isc_cosine_topk_exhaustive", args, rf, qg, _lib.stream_handle(self.device))
         return (scores, indices) if rf is None and qg is None else _unpad(scores, indices)
 
     def _merge_topk(self, scores: Tensor, indices: Tensor, k: int) -> tuple[Tensor, Tensor]:
@@ -928,59 +940,33 @@ class EmbeddingBank:
     def _search(self, queries: Tensor, k: int, lanes: bool, mask: "RowFilter | Tensor | None" = None,
                 exclude_group: Tensor | None = None) -> SearchHandle:
         rf = self._as_filter(mask)
-        if not isinstance(k, int) or isinstance(k, bool):
-            raise TypeError(f"k must be an int, got {type(k).__name__}")
-        if k < 1:
-            raise ValueError(f"k must be >= 1, got {k}")
-        if k > _lib.ISC_TOPK_MAX_K:
-            raise ValueError(f"k must be <= {_lib.ISC_TOPK_MAX_K}, got {k}")
+        self._check_k(k)
         q = self._prepare_queries(queries)
         nq = q.shape[0]
-        qg = self._query_codes(exclude_group, nq)
-        # a filtered search (row filter and / or groups) pads short answers; the grouped kernels get the query codes
-        filt: dict[str, object] = {} if rf is None else {"mask": rf}
-        if qg is not None:
-            filt["groups"] = qg
-        lanes = lanes and nq <= self._LANE_MAX_QUERIES
+        filt = self._filter_kwargs(rf, self._query_codes(exclude_group, nq))
+        # sharded: the first search learns the bank's size with a collective of every rank
+        n_rows = self.num_local_rows if self.process_group is None else self._global_rows()
+        if k > n_rows:
+            raise ValueError(f"k={k} exceeds the bank size {n_rows}")
+        if nq == 0:
+            return SearchHandle(*self._empty_topk(k))
+        on_gpu = self.device.type == "cuda"
+        lanes = lanes and on_gpu and nq <= self._LANE_MAX_QUERIES
         if self.process_group is None:
-            if k > self.num_local_rows:
-                raise ValueError(f"k={k} exceeds the bank size {self.num_local_rows}")
-            if nq == 0:
-                return SearchHandle(torch.empty((0, k), dtype=torch.float32, device=self.device),
-                                    torch.empty((0, k), dtype=torch.int64, device=self.device))
+            lane, ls = self._lane(torch.cuda.current_stream(self.device), q) if lanes else (-1, None)
+            out = self._local_topk(q, k, lane=lane, stream=ls, **filt)
             if filt:  # the padding of a filtered search becomes (-inf, -1) on the stream that computed it
-                if not (lanes and self.device.type == "cuda"):
-                    return SearchHandle(*_unpad(*self._local_topk(q, k, **filt)))
-                lane, ls = self._lane(torch.cuda.current_stream(self.device), q)
-                out_s, out_i = self._local_topk(q, k, lane=lane, stream=ls, **filt)
-                with torch.cuda.stream(ls):
-                    out_s, out_i = _unpad(out_s, out_i)
-                done = torch.cuda.Event()
-                done.record(ls)
-                return SearchHandle(out_s, out_i, done)
-            if not (lanes and self.device.type == "cuda"):
-                return SearchHandle(*self._local_topk(q, k))
-            lane, ls = self._lane(torch.cuda.current_stream(self.device), q)
-            out_s, out_i = self._local_topk(q, k, lane=lane, stream=ls)
+                with torch.cuda.stream(ls) if ls is not None else nullcontext():
+                    out = _unpad(*out)
+            if ls is None:
+                return SearchHandle(*out)
             done = torch.cuda.Event()
             done.record(ls)
-            return SearchHandle(out_s, out_i, done)
+            return SearchHandle(*out, done)
 
         # ---- sharded: local partial top-k -> ONE all-gather -> merge on every rank.  Every rank issues exactly one
         # collective per search whatever its shard holds, so the ranks cannot fall out of step.
-        if not hasattr(self, "_n_total"):
-            self._n_total = self._total_rows()
-        if k > self._n_total:
-            raise ValueError(f"k={k} exceeds the bank size {self._n_total}")
-        if nq == 0:
-            return SearchHandle(torch.empty((0, k), dtype=torch.float32, device=self.device),
-                                torch.empty((0, k), dtype=torch.int64, device=self.device))
-        # exchange buffer of this rank: [scores f32 Q*k | indices i64 Q*k | status i32 x4], written in place by the
-        # search kernels, gathered with ONE collective and read in place by the merge kernel
-        off_i = (4 * nq * k + 7) // 8 * 8
-        off_s = off_i + 8 * nq * k
-        nbytes = off_s + 16
-        on_gpu = self.device.type == "cuda"
+        nbytes, views = _exchange_layout(nq, k)
         slot = self._slots[self._slot_next]
         self._slot_next ^= 1
         lane, ls = -1, None
@@ -999,32 +985,21 @@ class EmbeddingBank:
         elif slot.buf is None or slot.buf.numel() < nbytes:
             slot.buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         xbuf = slot.buf[:nbytes]
-        part_s = xbuf[: 4 * nq * k].view(torch.float32).view(nq, k)
-        part_i = xbuf[off_i:off_s].view(torch.int64).view(nq, k)
-        status = xbuf[off_s:].view(torch.int32)
-        if kl < k:  # a shard with fewer rows than k: pad with entries that rank after every real candidate
-            # (a masked search pads with the C ABI's (NaN, INT64_MAX), which ranks after NaN-scored rows of other shards too)
-            part_s.fill_(-math.inf if not filt else math.nan)
-            part_i.fill_(_PAD_INDEX)
-            status.zero_()
-            if kl > 0:
-                s, i = self._local_topk(q, kl, **filt)
-                part_s[:, :kl] = s
-                part_i[:, :kl] = i
+        part_s, part_i, status = views(xbuf)
+        if kl < k:
+            # (an unfiltered search pads with -inf; a filtered one with the C ABI's NaN, which ranks after the NaN-scored
+            # rows of other shards too)
+            self._short_shard(self._local_topk, q, kl, filt, (part_s, part_i), status, math.nan if filt else -math.inf)
         else:
             self._local_topk(q, k, out=(part_s, part_i, status), lane=lane, stream=ls, **filt)
 
-        def exchange() -> tuple[Tensor, Tensor, Tensor, Tensor]:
-            gathered = self._all_gather_bytes(xbuf)
-            all_s = gathered[:, : 4 * nq * k].view(torch.float32).view(self.world_size, nq, k)
-            all_i = gathered[:, off_i:off_s].view(torch.int64).view(self.world_size, nq, k)
-            out_s, out_i = self._merge_topk(all_s, all_i, k)
-            if filt:
-                out_s, out_i = _unpad(out_s, out_i)
-            return out_s, out_i, gathered, gathered[:, off_s:].view(torch.int32)  # [G, 4]: every shard's diagnostics
+        def exchange() -> tuple[Tensor, Tensor, Tensor]:
+            all_s, all_i, gstatus = views(self._all_gather_bytes(xbuf))  # gstatus [G, 4]: every shard's diagnostics
+            out = self._merge_topk(all_s, all_i, k)
+            return (*(_unpad(*out) if filt else out), gstatus)
 
         if not on_gpu:  # CPU tensors (the gloo rehearsal of the host logic): nothing to overlap
-            out_s, out_i, gathered, gstatus = exchange()
+            out_s, out_i, gstatus = exchange()
             self.last_gathered_status = gstatus
             return SearchHandle(out_s, out_i, None, gstatus)
         if self._xstream is None:
@@ -1034,12 +1009,24 @@ class EmbeddingBank:
         with torch.cuda.stream(self._xstream):
             self._xstream.wait_event(local_done)
             xbuf.record_stream(self._xstream)  # (allocated on the caller's stream, read by the all-gather on this one)
-            out_s, out_i, gathered, gstatus = exchange()
+            out_s, out_i, gstatus = exchange()
             done = torch.cuda.Event()
             done.record(self._xstream)
         slot.done = done
         self.last_gathered_status = gstatus  # valid once the handle has been resolved
         return SearchHandle(out_s, out_i, done, gstatus)
+
+    def _short_shard(self, local, q: Tensor, kl: int, filt: dict, planes: tuple[Tensor, ...], status: Tensor,
+                     pad_score: float) -> None:
+        """The exchange planes of a shard with `kl` < k rows: its `local(q, kl, **filt)` answer -- `_local_topk`, or
+        `_local_collapse` with a labels plane -- in the first `kl` columns, the rest entries that rank after every real
+        candidate (`pad_score`, INT64_MAX, label -1); status zero."""
+        for plane, pad in zip(planes, (pad_score, _PAD_INDEX, -1)):
+            plane.fill_(pad)
+        status.zero_()
+        if kl > 0:
+            for plane, part in zip(planes, local(q, kl, **filt)):
+                plane[:, :kl] = part
 
     def _all_gather_bytes(self, xbuf: Tensor) -> Tensor:
         """`[G, nbytes]` uint8: every rank's exchange buffer (one all-gather; RCCL over xGMI on the GPUs)."""
@@ -1065,12 +1052,7 @@ class EmbeddingBank:
         has run the call.  `out`: optional (scores, indices, status int32[4]) to write into; `mask` / `groups`: as in
         `_local_topk`.  The device hook a CPU rehearsal replaces."""
         nq = queries.shape[0]
-        if out is None:
-            scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            indices = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-            status = torch.empty(4, dtype=torch.int32, device=self.device)
-        else:
-            scores, indices, status = out
+        scores, indices, status = out if out is not None else self._new_out(nq, k)
         codes = torch.empty((nq, k), dtype=torch.int32, device=self.device)
         ws = self._workspace(nq, k, collapse=True)
         lib = _lib.load()
@@ -1107,13 +1089,27 @@ class EmbeddingBank:
         _lib.check(st, "isc_topk_merge_groups")
         return out_s, out_i, out_l
 
-    def _check_groups_k(self, k: int) -> None:
+    def _check_k(self, k: int) -> None:
         if not isinstance(k, int) or isinstance(k, bool):
             raise TypeError(f"k must be an int, got {type(k).__name__}")
         if k < 1:
             raise ValueError(f"k must be >= 1, got {k}")
         if k > _lib.ISC_TOPK_MAX_K:
             raise ValueError(f"k must be <= {_lib.ISC_TOPK_MAX_K}, got {k}")
+
+    @staticmethod
+    def _filter_kwargs(rf: RowFilter | None, qg: Tensor | None) -> dict[str, object]:
+        """`mask=` / `groups=` of a local search hook, each only when set (a hook without that filter need not know the
+        argument).  A filtered search (non-empty) pads short answers; the grouped kernels get the query codes."""
+        filt: dict[str, object] = {} if rf is None else {"mask": rf}
+        if qg is not None:
+            filt["groups"] = qg
+        return filt
+
+    def _empty_topk(self, k: int, labels: bool = False) -> tuple[Tensor, ...]:
+        """The answer to no query: `(scores [0, k], indices [0, k])` and, with `labels`, the labels."""
+        dtypes = (torch.float32, torch.int64, torch.int64) if labels else (torch.float32, torch.int64)
+        return tuple(torch.empty((0, k), dtype=dt, device=self.device) for dt in dtypes)
 
     def search_groups(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None,
                       exclude_group: Tensor | None = None) -> tuple[Tensor, Tensor, Tensor]:
@@ -1130,62 +1126,31 @@ class EmbeddingBank:
         queries the first pass could not prove, [3]: queries answered by the float64 sweep).  A sharded bank all-gathers
         every rank's collapsed list with its labels and keeps the best entry per label."""
         rf = self._as_filter(mask)
-        self._check_groups_k(k)
+        self._check_k(k)
         q = self._prepare_queries(queries)
         nq = q.shape[0]
         if self.group_labels is None:
             raise ValueError("search_groups needs row groups: build the bank with row_groups= (or from_database)")
-        qg = self._query_codes(exclude_group, nq)
-        filt: dict[str, object] = {} if rf is None else {"mask": rf}
-        if qg is not None:
-            filt["groups"] = qg
+        filt = self._filter_kwargs(rf, self._query_codes(exclude_group, nq))
+        n_rows = self.num_local_rows if self.process_group is None else self._global_rows()
+        if k > n_rows:
+            raise ValueError(f"k={k} exceeds the bank size {n_rows}")
+        if nq == 0:
+            return self._empty_topk(k, labels=True)
         if self.process_group is None:
-            if k > self.num_local_rows:
-                raise ValueError(f"k={k} exceeds the bank size {self.num_local_rows}")
-            if nq == 0:
-                return (torch.empty((0, k), dtype=torch.float32, device=self.device),
-                        torch.empty((0, k), dtype=torch.int64, device=self.device),
-                        torch.empty((0, k), dtype=torch.int64, device=self.device))
             return _unpad_groups(*self._local_collapse(q, k, **filt))
 
-        if not hasattr(self, "_n_total"):
-            self._n_total = self._total_rows()
-        if k > self._n_total:
-            raise ValueError(f"k={k} exceeds the bank size {self._n_total}")
-        if nq == 0:
-            return (torch.empty((0, k), dtype=torch.float32, device=self.device),
-                    torch.empty((0, k), dtype=torch.int64, device=self.device),
-                    torch.empty((0, k), dtype=torch.int64, device=self.device))
-        # exchange buffer of this rank: [scores f32 Q*k | indices i64 Q*k | labels i64 Q*k | status i32 x4], gathered with
-        # ONE collective and read in place by the merge
-        off_i = (4 * nq * k + 7) // 8 * 8
-        off_l = off_i + 8 * nq * k
-        off_s = off_l + 8 * nq * k
-        xbuf = torch.empty(off_s + 16, dtype=torch.uint8, device=self.device)
-        part_s = xbuf[: 4 * nq * k].view(torch.float32).view(nq, k)
-        part_i = xbuf[off_i:off_l].view(torch.int64).view(nq, k)
-        part_l = xbuf[off_l:off_s].view(torch.int64).view(nq, k)
-        status = xbuf[off_s:].view(torch.int32)
+        # sharded like `_search`, but not pipelined: a fresh exchange buffer per call, the all-gather on the caller's stream
+        nbytes, views = _exchange_layout(nq, k, with_labels=True)
+        xbuf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        part_s, part_i, part_l, status = views(xbuf)
         kl = min(k, self.num_local_rows)
-        if kl < k:  # a shard with fewer rows than k: pad with entries that rank after every real one
-            part_s.fill_(math.nan)
-            part_i.fill_(_PAD_INDEX)
-            part_l.fill_(-1)
-            status.zero_()
-            if kl > 0:
-                s, i, lab = self._local_collapse(q, kl, **filt)
-                part_s[:, :kl] = s
-                part_i[:, :kl] = i
-                part_l[:, :kl] = lab
+        if kl < k:
+            self._short_shard(self._local_collapse, q, kl, filt, (part_s, part_i, part_l), status, math.nan)
         else:
             _, _, lab = self._local_collapse(q, k, out=(part_s, part_i, status), **filt)
             part_l.copy_(lab)
-        gathered = self._all_gather_bytes(xbuf)
-        g = self.world_size
-        all_s = gathered[:, : 4 * nq * k].view(torch.float32).view(g, nq, k)
-        all_i = gathered[:, off_i:off_l].view(torch.int64).view(g, nq, k)
-        all_l = gathered[:, off_l:off_s].view(torch.int64).view(g, nq, k)
-        self.last_gathered_status = gathered[:, off_s:].view(torch.int32)
+        all_s, all_i, all_l, self.last_gathered_status = views(self._all_gather_bytes(xbuf))
         return _unpad_groups(*self._merge_groups(all_s, all_i, all_l, k))
 
     def search_groups_exhaustive(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None,
@@ -1193,7 +1158,7 @@ class EmbeddingBank:
         """`search_groups` from the data-independent float64 kernel (`isc_cosine_topk_exhaustive_collapse`): every score
         evaluated exactly, one shard.  Slow; the on-device reference the fast path is tested against."""
         rf = self._as_filter(mask)
-        self._check_groups_k(k)
+        self._check_k(k)
         q = self._prepare_queries(queries)
         nq = q.shape[0]
         if self.group_labels is None:
@@ -1204,9 +1169,7 @@ class EmbeddingBank:
         if not 1 <= k <= self.num_local_rows:
             raise ValueError(f"k={k} must be in [1, {self.num_local_rows}]")
         if nq == 0:
-            return (torch.empty((0, k), dtype=torch.float32, device=self.device),
-                    torch.empty((0, k), dtype=torch.int64, device=self.device),
-                    torch.empty((0, k), dtype=torch.int64, device=self.device))
+            return self._empty_topk(k, labels=True)
         lib = _lib.load()
         code = _lib.dtype_code(self.dtype)
         need = _lib.c_size_t()
@@ -1247,6 +1210,11 @@ class EmbeddingBank:
             raise ValueError("min_score is NaN")
         return torch.full((nq,), float(min_score), dtype=torch.float32, device=self.device)
 
+    def _empty_range(self, nq: int) -> RangeResult:
+        return RangeResult(torch.zeros(nq + 1, dtype=torch.int64, device=self.device),
+                           torch.empty(0, dtype=torch.float32, device=self.device),
+                           torch.empty(0, dtype=torch.int64, device=self.device))
+
     def _range_call(self, q: Tensor, thr: Tensor, capacity: int, mask: RowFilter | None = None,
                     groups: Tensor | None = None) -> tuple[int, RangeResult, Tensor]:
         """One `isc_cosine_range` call: (needed, result -- valid only when needed <= capacity --, status int32[4])."""
@@ -1265,22 +1233,13 @@ class EmbeddingBank:
         indices = torch.empty(capacity, dtype=torch.int64, device=self.device)
         needed = torch.empty(1, dtype=torch.int64, device=self.device)
         status = torch.empty(4, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            args = (
-                self._bank.data_ptr(), code, self.capacity, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
-                q.stride(0), thr.data_ptr(), self.index_base, self._norm_bound.data_ptr(), capacity,
-                offsets.data_ptr(), scores.data_ptr(), indices.data_ptr(), needed.data_ptr(), status.data_ptr(),
-                ws.data_ptr(), ws.numel(),
-            )
-            if groups is not None:
-                st = lib.isc_cosine_range_grouped(*args, None if mask is None else mask.packed.data_ptr(),
-                                                  self._row_codes.data_ptr(), groups.data_ptr(),
-                                                  _lib.stream_handle(self.device))
-            elif mask is None:
-                st = lib.isc_cosine_range(*args, _lib.stream_handle(self.device))
-            else:
-                st = lib.isc_cosine_range_masked(*args, mask.packed.data_ptr(), _lib.stream_handle(self.device))
-        _lib.check(st, "isc_cosine_range" + ("_grouped" if groups is not None else "" if mask is None else "_masked"))
+        args = (
+            self._bank.data_ptr(), code, self.capacity, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
+            q.stride(0), thr.data_ptr(), self.index_base, self._norm_bound.data_ptr(), capacity,
+            offsets.data_ptr(), scores.data_ptr(), indices.data_ptr(), needed.data_ptr(), status.data_ptr(),
+            ws.data_ptr(), ws.numel(),
+        )
+        self._row_search("isc_cosine_range", args, mask, groups, _lib.stream_handle(self.device))
         return int(needed.item()), RangeResult(offsets, scores, indices), status
 
     def _local_range(self, queries: Tensor, min_score: Tensor, max_results: int, mask: RowFilter | None = None,
@@ -1290,10 +1249,7 @@ class EmbeddingBank:
         `max_results` entries, the filter's candidate count, an upper bound of it)."""
         nq = queries.shape[0]
         if self.num_local_rows == 0 or nq == 0:
-            empty = RangeResult(torch.zeros(nq + 1, dtype=torch.int64, device=self.device),
-                                torch.empty(0, dtype=torch.float32, device=self.device),
-                                torch.empty(0, dtype=torch.int64, device=self.device))
-            return 0, empty
+            return 0, self._empty_range(nq)
         limit = min(max(max_results, 1), 0x7FFFFFFF)
         cap = min(max(1 << 16, self._RANGE_GUESS_PER_QUERY * nq), limit)
         grp = {} if groups is None else {"groups": groups}
@@ -1354,8 +1310,7 @@ class EmbeddingBank:
             raise ValueError(f"search_range found {merged}{'' if not all_tot[:, 1].any() else ' or more'} rows, more "
                              f"than max_results={max_results}")
         if merged == 0:
-            return RangeResult(torch.zeros(nq + 1, dtype=torch.int64, device=dev),
-                               torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int64, device=dev))
+            return self._empty_range(nq)
         width = int(all_tot[:, 0].max())
         # payload of this rank: [query int64 | index int64 | score float32 (as 8 bytes)] x width, padding rows unused
         pay = torch.zeros((3, width), dtype=torch.int64, device=dev)

@@ -29,29 +29,43 @@ def _free_port() -> int:
         return s.getsockname()[1]
 
 
+def _oracle_bank_class(calls: dict | None = None):
+    """`EmbeddingBank` with the device hooks replaced by the oracle; `calls["gather"]` counts its all-gathers.  Built
+    inside the worker: the spawned process imports the package there."""
+    from imagescry_amd import EmbeddingBank
+    from oracle import search_oracle
+
+    class OracleBank(EmbeddingBank):
+        def _store(self, embeddings, normalize):  # keep the rows on the CPU
+            return embeddings.contiguous()
+
+        def _local_topk(self, queries, kk, out=None, lane=-1, stream=None):  # `out`: the product's exchange buffer, filled in place
+            s, i = search_oracle.cosine_topk(self._bank, queries, kk, index_base=self.index_base)
+            s, i = torch.from_numpy(s), torch.from_numpy(i)
+            if out is not None:
+                out[0].copy_(s), out[1].copy_(i), out[2].zero_()
+            return s, i
+
+        def _merge_topk(self, scores, indices, kk):
+            s, i = search_oracle.topk_merge(scores.numpy(), indices.numpy(), kk)
+            return torch.from_numpy(s), torch.from_numpy(i)
+
+        def _all_gather_bytes(self, xbuf):
+            if calls is not None:
+                calls["gather"] += 1
+            return super()._all_gather_bytes(xbuf)
+
+    return OracleBank
+
+
 def _worker(rank: int, world: int, port: int, n: int, k: int, out_dir: str) -> None:
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         import cases
-        from imagescry_amd import EmbeddingBank
-        from oracle import search_oracle
 
-        class OracleBank(EmbeddingBank):
-            def _store(self, embeddings, normalize):  # keep the rows on the CPU
-                return embeddings.contiguous()
-
-            def _local_topk(self, queries, kk, out=None, lane=-1, stream=None):  # `out`: the product's exchange buffer, filled in place
-                s, i = search_oracle.cosine_topk(self._bank, queries, kk, index_base=self.index_base)
-                s, i = torch.from_numpy(s), torch.from_numpy(i)
-                if out is not None:
-                    out[0].copy_(s), out[1].copy_(i), out[2].zero_()
-                return s, i
-
-            def _merge_topk(self, scores, indices, kk):
-                s, i = search_oracle.topk_merge(scores.numpy(), indices.numpy(), kk)
-                return torch.from_numpy(s), torch.from_numpy(i)
+        OracleBank = _oracle_bank_class()
 
         bank, queries = cases.search_case(n, 64, 9, torch.float16, seed=5)
         queries[2] = 0  # all-tie row
@@ -94,29 +108,11 @@ def _uneven_worker(rank: int, world: int, port: int, k: int, out_dir: str) -> No
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         import cases
-        from imagescry_amd import EmbeddingBank
         from oracle import search_oracle
 
         calls = {"gather": 0}
 
-        class OracleBank(EmbeddingBank):
-            def _store(self, embeddings, normalize):
-                return embeddings.contiguous()
-
-            def _local_topk(self, queries, kk, out=None, lane=-1, stream=None):  # `out`: the product's exchange buffer, filled in place
-                s, i = search_oracle.cosine_topk(self._bank, queries, kk, index_base=self.index_base)
-                s, i = torch.from_numpy(s), torch.from_numpy(i)
-                if out is not None:
-                    out[0].copy_(s), out[1].copy_(i), out[2].zero_()
-                return s, i
-
-            def _merge_topk(self, scores, indices, kk):
-                s, i = search_oracle.topk_merge(scores.numpy(), indices.numpy(), kk)
-                return torch.from_numpy(s), torch.from_numpy(i)
-
-            def _all_gather_bytes(self, xbuf):
-                calls["gather"] += 1
-                return super()._all_gather_bytes(xbuf)
+        OracleBank = _oracle_bank_class(calls)
 
         n = 3000
         bank, queries = cases.search_case(n, 32, 6, torch.float16, seed=17)
@@ -154,23 +150,10 @@ def _pipeline_worker(rank: int, world: int, port: int, n: int, k: int, out_dir: 
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         import cases
-        from imagescry_amd import EmbeddingBank, EmbeddingBatch, EmbeddingModule, EmbedSearchPipeline, ImageBatch
+        from imagescry_amd import EmbeddingBatch, EmbeddingModule, EmbedSearchPipeline, ImageBatch
         from oracle import search_oracle
 
-        class OracleBank(EmbeddingBank):
-            def _store(self, embeddings, normalize):
-                return embeddings.contiguous()
-
-            def _local_topk(self, queries, kk, out=None, lane=-1, stream=None):  # `out`: the product's exchange buffer, filled in place
-                s, i = search_oracle.cosine_topk(self._bank, queries, kk, index_base=self.index_base)
-                s, i = torch.from_numpy(s), torch.from_numpy(i)
-                if out is not None:
-                    out[0].copy_(s), out[1].copy_(i), out[2].zero_()
-                return s, i
-
-            def _merge_topk(self, scores, indices, kk):
-                s, i = search_oracle.topk_merge(scores.numpy(), indices.numpy(), kk)
-                return torch.from_numpy(s), torch.from_numpy(i)
+        OracleBank = _oracle_bank_class()
 
         class StubEmbedder(EmbeddingModule):
             proj = torch.randn(3 * 8, 64, generator=torch.Generator().manual_seed(3))
