@@ -24,6 +24,28 @@ __device__ __forceinline__ T isc_packed_load(const void* bank, int64_t row, int 
     return *reinterpret_cast<const T*>(p);
 }
 
+// ---- int8 shadow of an fp16 bank (isc_bank_quantize; the last filter level of large query batches streams it) -----
+// The same scheme with 128 int8 per K step: [tile of 256 rows][K step of 128 dims][row][128 B], element e of a row at
+// byte e % 128 of K step e / 128, rows in the fp16 bank's order, padding rows and columns zero.  One fp32 record per tile
+// follows the data (256-byte aligned):
+//   scale      a_t = (largest |x| of the tile) / 127            (1 for an all-zero tile)
+//   inv_scale  c_t: the tile is quantised as X = rint(x * c_t); every bound below is about x * c_t, so the filter is
+//              exact for this very float whatever its distance from 1 / a_t
+//   resid      e_t >= max over the tile's rows of || x * c_t - X ||_2
+//   qnorm      n_t >= max over the tile's rows of || X ||_2;  +inf: the tile holds a non-finite value, every row passes
+struct IscShadowRec {
+    float scale, inv_scale, resid, qnorm;
+};
+#define ISC_SHADOW_KSTEP_DIMS 128
+__host__ __device__ inline int isc_shadow_ksteps(int d) { return (d + ISC_SHADOW_KSTEP_DIMS - 1) / ISC_SHADOW_KSTEP_DIMS; }
+__host__ __device__ inline size_t isc_shadow_data_bytes(int64_t n, int d) {
+    return (size_t)((n + ISC_TILE_ROWS - 1) / ISC_TILE_ROWS) * isc_shadow_ksteps(d) * ISC_TILE_KSTEP_BYTES;
+}
+__host__ __device__ inline size_t isc_shadow_bytes(int64_t n, int d) {
+    const size_t rec = (size_t)((n + ISC_TILE_ROWS - 1) / ISC_TILE_ROWS) * sizeof(IscShadowRec);
+    return isc_shadow_data_bytes(n, d) + (rec + 255) / 256 * 256;
+}
+
 // ---- row permutation of a packed bank ------------------------------------------------------------------------
 // A bank of N rows is stored in a fixed pseudo-random order: packed position p holds ORIGINAL row
 //     orig(p) = (mul * p) mod N,          p = (mul_inv * orig) mod N,

@@ -1,7 +1,8 @@
 // Packing of embedding rows into the tile-contiguous, row-permuted bank layout (include/imagescry_hip.h:
 // isc_bank_pack, isc_bank_unpack, isc_bank_packed_bytes, isc_bank_permutation), and of a row filter into the same row
 // order (isc_row_mask_words, isc_row_mask_pack), and of row group codes (isc_row_groups_pack); in-place append to a bank
-// packed for a reserved capacity and its growth (isc_bank_append, isc_bank_repack).
+// packed for a reserved capacity and its growth (isc_bank_append, isc_bank_repack); the int8 shadow of an fp16 bank
+// (isc_bank_shadow_bytes, isc_bank_quantize).
 #include "bank_layout.h"
 #include "isc_common.h"
 
@@ -161,6 +162,107 @@ __global__ __launch_bounds__(256) void k_row_groups_pack(const int32_t* __restri
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int32_t c = p < pm.n ? codes[isc_perm_orig(pm, p)] : -2;
     packed_codes[p] = c < 0 ? -2 : c;
+}
+
+// int8 shadow of a packed fp16 bank (bank_layout.h: IscShadowRec; isc_bank_quantize).  One workgroup per tile: a first
+// sweep finds the tile's largest magnitude, a second one (the tile's 32 KiB blocks come from the L2 then) quantises with
+// round to nearest and writes the int8 blocks; the per-row sums of the squared residuals and of the squared integers are
+// taken in float64 -- (double)x * (double)c_t - X is exact there: 11 x 24 significant bits minus a small integer -- and
+// their square roots go to the record rounded UP (x (1 + 1e-6) covers the float64 sum of <= 8192 terms, the sqrt and the
+// conversion to float32).  Thread t covers 16-byte output chunk t & 7 of rows (t >> 3) + 32 i: the eight lanes of a row
+// are neighbours, so a row's sums are three shuffles.
+__global__ __launch_bounds__(256) void k_bank_quantize(const unsigned char* __restrict__ bank, int ks, int ks8,
+                                                       unsigned char* __restrict__ shadow,
+                                                       IscShadowRec* __restrict__ recs) {
+    __shared__ float mx_sh[4];
+    __shared__ double sum_sh[2][4];
+    const int64_t tile = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned char* src = bank + tile * ks * (int64_t)ISC_TILE_KSTEP_BYTES;
+    float mx = 0.f;
+    int bad = 0;
+    for (int i = tid; i < ks * (ISC_TILE_KSTEP_BYTES / 16); i += 256) {
+        const uint4 raw = *reinterpret_cast<const uint4*>(src + (size_t)i * 16);
+        const _Float16* h = reinterpret_cast<const _Float16*>(&raw);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float v = fabsf((float)h[j]);
+            bad |= !(v <= 65504.f) ? 1 : 0;  // inf or NaN
+            mx = fmaxf(mx, v);
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    if (lane == 0) mx_sh[wave] = mx;
+    bad = __syncthreads_or(bad);
+    mx = fmaxf(fmaxf(mx_sh[0], mx_sh[1]), fmaxf(mx_sh[2], mx_sh[3]));
+    const float c = mx > 0.f ? 127.f / mx : 1.f;  // <= 127 / 2^-24: finite
+    const int row0 = tid >> 3, c8 = tid & 7;
+    double rs[8], qs[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) rs[i] = qs[i] = 0.0;
+    unsigned char* dst = shadow + tile * ks8 * (int64_t)ISC_TILE_KSTEP_BYTES;
+    for (int s8 = 0; s8 < ks8; ++s8) {
+        const int s = 2 * s8 + (c8 >> 2);  // the fp16 K step that holds dims 128 s8 + 16 c8 .. + 15
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int row = row0 + 32 * i;
+            _Float16 h[16];
+            if (s < ks) {
+                const uint4* p = reinterpret_cast<const uint4*>(src + ((size_t)s * ISC_TILE_ROWS + row) * ISC_KSTEP_BYTES +
+                                                                (c8 & 3) * 32);
+                reinterpret_cast<uint4*>(h)[0] = p[0];
+                reinterpret_cast<uint4*>(h)[1] = p[1];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) h[j] = (_Float16)0.f;
+            }
+            signed char out[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const float v = (float)h[j];
+                float x = bad ? 0.f : rintf(v * c);
+                x = fminf(fmaxf(x, -127.f), 127.f);
+                const double r = bad ? 0.0 : (double)v * (double)c - (double)x;
+                rs[i] = fma(r, r, rs[i]);
+                qs[i] = fma((double)x, (double)x, qs[i]);
+                out[j] = (signed char)(int)x;
+            }
+            *reinterpret_cast<uint4*>(dst + ((size_t)s8 * ISC_TILE_ROWS + row) * ISC_KSTEP_BYTES + c8 * 16) =
+                *reinterpret_cast<const uint4*>(out);
+        }
+    }
+    double rmax = 0.0, qmax = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+        for (int off = 1; off < 8; off <<= 1) {
+            rs[i] += __shfl_xor(rs[i], off, 64);
+            qs[i] += __shfl_xor(qs[i], off, 64);
+        }
+        rmax = fmax(rmax, rs[i]);
+        qmax = fmax(qmax, qs[i]);
+    }
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1) {
+        rmax = fmax(rmax, __shfl_xor(rmax, off, 64));
+        qmax = fmax(qmax, __shfl_xor(qmax, off, 64));
+    }
+    if (lane == 0) {
+        sum_sh[0][wave] = rmax;
+        sum_sh[1][wave] = qmax;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        rmax = fmax(fmax(sum_sh[0][0], sum_sh[0][1]), fmax(sum_sh[0][2], sum_sh[0][3]));
+        qmax = fmax(fmax(sum_sh[1][0], sum_sh[1][1]), fmax(sum_sh[1][2], sum_sh[1][3]));
+        IscShadowRec rec;
+        rec.scale = mx > 0.f ? mx / 127.f : 1.f;
+        rec.inv_scale = c;
+        rec.resid = (float)sqrt(rmax) * (1.f + 1e-6f);
+        rec.qnorm = bad ? INFINITY : (float)sqrt(qmax) * (1.f + 1e-6f);
+        recs[tile] = rec;
+    }
 }
 
 int check_dtype(int dtype) { return dtype == ISC_F16 || dtype == ISC_F32; }
@@ -334,5 +436,23 @@ extern "C" int isc_row_groups_pack(const int32_t* codes, int64_t N, int32_t* pac
     const int64_t tiles = isc_ceil_div<int64_t>(N, ISC_TILE_ROWS);
     hipLaunchKernelGGL(k_row_groups_pack, dim3((unsigned)tiles), dim3(256), 0, isc_stream(stream), codes,
                        isc_make_perm(N), packed_codes);
+    return isc_launch_status();
+}
+
+extern "C" int isc_bank_shadow_bytes(int64_t N, int D, size_t* bytes) {
+    ISC_REQUIRE(bytes && N > 0 && N <= 0x7ffffffe && D > 0);
+    *bytes = isc_shadow_bytes(N, D);
+    return ISC_OK;
+}
+
+extern "C" int isc_bank_quantize(const void* packed, int64_t N, int D, void* shadow, size_t shadow_bytes, void* stream) {
+    ISC_REQUIRE(packed && shadow && N > 0 && N <= 0x7ffffffe && D > 0);
+    if (!isc_aligned(packed, 16) || !isc_aligned(shadow, 256)) return ISC_ERR_ALIGNMENT;
+    if (shadow_bytes < isc_shadow_bytes(N, D)) return ISC_ERR_WORKSPACE;
+    const int64_t tiles = isc_ceil_div<int64_t>(N, ISC_TILE_ROWS);
+    unsigned char* out = static_cast<unsigned char*>(shadow);
+    hipLaunchKernelGGL(k_bank_quantize, dim3((unsigned)tiles), dim3(256), 0, isc_stream(stream),
+                       static_cast<const unsigned char*>(packed), isc_ksteps(D, 2), isc_shadow_ksteps(D), out,
+                       reinterpret_cast<IscShadowRec*>(out + isc_shadow_data_bytes(N, D)));
     return isc_launch_status();
 }

@@ -99,6 +99,7 @@ struct Plan {
     int qpad;            // qtiles * tnq
     int max_seg;         // segs_per_chunk * max chunks over the levels
     int nlevels;
+    int64_t budget;      // survivors per query a filter level is sized for (make_plan)
     Level levels[MAX_LEVELS];
 };
 
@@ -163,6 +164,7 @@ Plan make_plan(int64_t n, int q, int k, int group_rows = 0) {
 
     p.nlevels = 0;
     p.max_seg = 0;
+    p.budget = 0;
     auto add = [&](int64_t r0, int64_t r1, int sample) {
         Level& l = p.levels[p.nlevels++];
         l.r0 = r0;
@@ -193,6 +195,7 @@ Plan make_plan(int64_t n, int q, int k, int group_rows = 0) {
         // collapsed: the survivors' groups must fit the selection's hash (COLLAPSE_GROUPS slots) as well
         if (group_rows > 0) budget = (int64_t)((double)COLLAPSE_GROUPS * p.kp / (p.kp + 8.0 * sqrt((double)p.kp)));
         if (nseg * CAP / 8 < budget) budget = nseg * CAP / 8;
+        p.budget = budget;
         const int64_t unit = (int64_t)p.kp * (group_rows > COLLAPSE_ROWS_CAP ? COLLAPSE_ROWS_CAP : group_rows > 0 ? group_rows : 1);
         int64_t ratio = 1 + budget / unit;
         // 256-query shape with ONE query tile (128 < Q <= 256): the level after the sample would be the whole bank on
@@ -232,6 +235,9 @@ struct Workspace {
     int32_t* qflag2;          // [qpad]  slot -> a candidate buffer overflowed
     unsigned char* qpacked2;  // [qtiles][ks][tnq][128 B]  packed query rows by slot
     IscExactWs exact;        // list + partial lists of k_exact (the exhaustive float64 pass, the last resort)
+    // the int8 level of an fp16 search (run(): use_i8): the pass's queries quantised, and their records
+    unsigned char* qpacked8;  // [qtiles][K steps of 128 dims][tnq][128 B]
+    float4* qrec8;            // [qpad]  (c_q, ||Q||_2, e_q, unused)
     size_t bytes;
 };
 
@@ -260,6 +266,9 @@ Workspace carve(const Plan& p, int ks, int64_t n, int k, void* base) {
     w.qpacked2 = static_cast<unsigned char*>(take((size_t)p.qpad * ks * ISC_KSTEP_BYTES));
     const size_t ex = isc_exact_ws_bytes(n, p.qb, k);
     w.exact = isc_exact_ws_carve(take(ex), n, p.qb, k);
+    const int ks8 = (ks + 1) / 2;  // (sized by the fp16 K steps: an fp32 bank never uses them)
+    w.qpacked8 = static_cast<unsigned char*>(take((size_t)p.qpad * ks8 * ISC_KSTEP_BYTES));
+    w.qrec8 = static_cast<float4*>(take((size_t)p.qpad * sizeof(float4)));
     w.bytes = off;
     return w;
 }
@@ -311,12 +320,66 @@ __global__ __launch_bounds__(256) void k_prep(const TQ* __restrict__ queries, in
     *reinterpret_cast<uint4*>(packed + (size_t)i * 16) = *reinterpret_cast<const uint4*>(v);
 }
 
+// The queries of a pass once more as int8, for the last level of a large-batch fp16 search (run(): use_i8).  One wave per
+// query row of the padded pass.  The query is first rounded to fp16 -- it is the fp16-rounded query whose dot products the
+// thresholds are about -- then quantised like a bank tile (bank_pack.hip: k_bank_quantize) with its own inverse scale
+// c_q = 127 / max |q|: Q = rint(q c_q), e_q >= ||q c_q - Q||_2 and ||Q||_2, both from float64 sums and rounded up.
+// A query that is zero, non-finite or padding gets c_q = NaN and passes nothing: k_final answers a zero or non-finite
+// query without looking at its candidates, or hands it to the exhaustive pass.
+template <typename TQ>
+__global__ __launch_bounds__(256) void k_prep_i8(const TQ* __restrict__ queries, int64_t ldq, int q, int d, int ks8,
+                                                 int tnq, unsigned char* __restrict__ packed8,
+                                                 float4* __restrict__ qrec) {
+    const int lane = threadIdx.x & 63;
+    const int qrow = blockIdx.x * 4 + (threadIdx.x >> 6);  // < qpad (the grid is qpad / 4, tnq a multiple of 4)
+    const TQ* src = queries + (int64_t)qrow * ldq;
+    float mx = 0.f;
+    int bad = 0;
+    if (qrow < q) {
+        for (int e = lane; e < d; e += 64) {
+            const float v = fabsf((float)(_Float16)src[e]);
+            bad |= !(v <= 65504.f) ? 1 : 0;
+            mx = fmaxf(mx, v);
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+        bad |= __shfl_xor(bad, off, 64);
+    }
+    const bool live = qrow < q && !bad && mx > 0.f;
+    const float c = live ? 127.f / mx : 0.f;
+    double rs = 0.0, qs = 0.0;
+    unsigned char* dst = packed8 + ((size_t)(qrow / tnq) * ks8 * tnq + (qrow % tnq)) * ISC_KSTEP_BYTES;
+    for (int ch = lane; ch < ks8 * 8; ch += 64) {  // 16-byte chunk ch: dims 16 ch .. 16 ch + 15
+        signed char out[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int e = ch * 16 + j;
+            const float v = (live && e < d) ? (float)(_Float16)src[e] : 0.f;
+            const float x = fminf(fmaxf(rintf(v * c), -127.f), 127.f);
+            const double r = (double)v * (double)c - (double)x;
+            rs = fma(r, r, rs);
+            qs = fma((double)x, (double)x, qs);
+            out[j] = (signed char)(int)x;
+        }
+        *reinterpret_cast<uint4*>(dst + (size_t)(ch >> 3) * tnq * ISC_KSTEP_BYTES + (ch & 7) * 16) =
+            *reinterpret_cast<const uint4*>(out);
+    }
+    rs = isc_wave_sum(rs);
+    qs = isc_wave_sum(qs);
+    if (lane == 0)
+        qrec[qrow] = make_float4(live ? c : __uint_as_float(0x7fc00000u), (float)sqrt(qs) * (1.f + 1e-6f),
+                                 (float)sqrt(rs) * (1.f + 1e-6f), 0.f);
+}
+
 // --- operand traits -------------------------------------------------------------------------------------------
 template <typename T>
 struct Mma;
 
 template <>
 struct Mma<_Float16> {
+    typedef f32x4 Acc;
     // acc[n] += A(16 rows) . B(16 queries x n) over the 64 halves of one K step.  One 16-byte chunk = 8 halves = the
     // k-slice one lane feeds to v_mfma_f32_16x16x32_f16; a0/b[0] hold chunks 0-3, a1/b[1] chunks 4-7.
     static __device__ __forceinline__ void half(const u32x4& a, const u32x4 (&b)[4], f32x4 (&acc)[4]) {
@@ -342,6 +405,7 @@ struct Mma<_Float16> {
 
 template <>
 struct Mma<float> {
+    typedef f32x4 Acc;
     // one 16-byte chunk = 4 floats: element j of every lane's chunk goes to the j-th v_mfma_f32_16x16x4_f32.
     // Lane group g therefore supplies k = 4 * chunk + j instead of k = g: a permutation of the K axis applied
     // identically to both operands, which leaves the dot products unchanged.
@@ -367,6 +431,28 @@ struct Mma<float> {
                 acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[j]), __uint_as_float(b[n][j]), acc[n],
                                                               0, 0, 0);
     }
+};
+
+// int8 (the shadow bank of an fp16 bank, bank_layout.h): one 16-byte chunk = 16 int8 = the k-slice one lane feeds to
+// v_mfma_i32_16x16x64_i8, so a 128-byte K step is 128 dimensions in the same two halves of four chunks and the loop
+// around it is the fp16 one, instruction for instruction.  Only the half-major loop (`part`) is instantiated.
+template <>
+struct Mma<signed char> {
+    typedef i32x4 Acc;
+    template <int N0, int N1>
+    static __device__ __forceinline__ void part(const u32x4& a, const u32x4 (&b)[4], i32x4 (&acc)[4]) {
+#pragma unroll
+        for (int n = N0; n < N1; ++n)
+            acc[n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b[n]),
+                                                           acc[n], 0, 0, 0);
+    }
+};
+
+// What the int8 instantiation of k_dots_filter takes in the place of a row filter: the shadow bank's tile records and the
+// per-query records k_prep_i8 wrote beside the int8 query tiles.
+struct IscShadowArgs {
+    const IscShadowRec* recs;  // [tiles of the whole bank]
+    const float4* qrec;        // [qpad]: (c_q, ||Q||_2 bound, e_q bound, unused); c_q = NaN: the query passes nothing
 };
 
 // LDS fragment read, hidden from the compiler: a C++ load from the staging array would make hipcc drain the
@@ -446,8 +532,13 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
                                                           Cand* __restrict__ qlist, int kp, int nslots,
                                                           int32_t* __restrict__ qflag, int32_t* __restrict__ status,
                                                           const int32_t* __restrict__ active, RowMask... row_mask) {
-    constexpr bool MASK = sizeof...(RowMask) > 0;
+    // I8: the last level of a large-batch search on the int8 shadow bank (run(): use_i8).  T = signed char, the pack holds
+    // one IscShadowArgs, the accumulators are integers and the threshold test at a tile's end is the one derived there.
+    constexpr bool I8 = std::is_same<T, signed char>::value;
+    typedef typename Mma<T>::Acc Acc;
+    constexpr bool MASK = sizeof...(RowMask) > 0 && !I8;
     constexpr bool GROUP = isc_grouped<RowMask...>();  // (MASK as well; its bitmap may then be NULL)
+    static_assert(!I8 || (TNQ == 256 && DBG == 12 && !SAMPLE && sizeof...(RowMask) == 1), "the int8 filter is one kernel");
     // DBG 20 / 32 / 33 are the REDO instantiations of 0 / 12 / 13 (k_final2's feeder: the whole bank against the fixed
     // thresholds of the listed queries).  They are kernels of their own so that a profile lists them apart from the
     // search's streaming launches; `active` counts the listed query slots -- normally zero, and the launch ends here.
@@ -521,6 +612,18 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
         if (!SAMPLE && g_abl_thr_inf) thr[n] = fabsf(thr[n]) + 3.0e38f;  // ISC_THR_INF: the price of scanning + the tail
 #endif
         cnt[n] = 0;
+    }
+    // int8: thr holds tau * c_q (NaN for a query that passes nothing); the two error norms of the lane's four queries
+    [[maybe_unused]] float qn8[4], eq8[4];
+    if constexpr (I8) {
+        const IscShadowArgs& sa = (row_mask, ...);
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const float4 qr = sa.qrec[q0 + wn * 64 + n * 16 + frow];
+            thr[n] *= qr.x;
+            qn8[n] = qr.y;
+            eq8[n] = qr.z;
+        }
     }
 
     // --- staging: a K-step block is contiguous in memory ([row][128 B]); staging round i moves slots
@@ -613,11 +716,11 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
     const int a_wave_off = wave_row0 * 128;
     const int b_wave_off = wn * 64 * 128;
 
-    f32x4 acc[MBMAX][4];
+    Acc acc[MBMAX][4];
 #pragma unroll
     for (int m = 0; m < MBMAX; ++m)
 #pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < 4; ++n) acc[m][n] = Acc{0, 0, 0, 0};
 
     // ---- row filter (MASK).  A wave's rows of a tile are MBE blocks of 16 from wave_row0; block m is bits
     // (SUB + 16 m) % 32 .. + 15 of word (SUB + 16 m) / 32 of the wave's words, which start at word wave_row0 / 32 of the
@@ -651,7 +754,8 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
         }
     };
     // a grouped search without a row filter skips the bitmap (kernel argument: uniform)
-    [[maybe_unused]] const bool use_mask = !GROUP || isc_row_mask_ptr(row_mask...) != nullptr;
+    [[maybe_unused]] bool use_mask = true;
+    if constexpr (GROUP) use_mask = isc_row_mask_ptr(row_mask...) != nullptr;
     [[maybe_unused]] uint32_t sample_mask[MASK_WORDS];
     if constexpr (MASK && SAMPLE) {  // the one tile of a sample workgroup: its words are in flight during the whole loop
         if (use_mask)
@@ -746,6 +850,7 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
     int kt = 0, tile = 0;
     [[maybe_unused]] uint32_t tile_mask[MASK_WORDS];
     [[maybe_unused]] i32x4 tile_codes[MBMAX];
+    [[maybe_unused]] float tile_ct = 0.f, tile_et = 0.f, tile_nt = 0.f;  // (I8) IscShadowRec of the current tile
     if constexpr (MODE == 22) st_prev = stamp();
     for (int step = 0; step < total_steps; ++step) {
         if constexpr (MASK && !SAMPLE) {
@@ -753,6 +858,15 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
         }
         if constexpr (GROUP && !SAMPLE && !DEFER) {
             if (kt == 0) load_codes(MBE_C{}, (r0 >> 8) + tile_begin + tile, tile_codes);
+        }
+        if constexpr (I8) {  // the tile's record: scalar loads like the row filter's words, consumed at the tile's end
+            if (kt == 0) {
+                typedef const __attribute__((address_space(4))) float ConstFloat;
+                ConstFloat* src = (ConstFloat*)((row_mask, ...).recs + ((r0 >> 8) + tile_begin + tile));
+                tile_ct = src[1];
+                tile_et = src[2];
+                tile_nt = src[3];
+            }
         }
         if constexpr (HM) {
             // ---- 256-query shape, half-major.  A K step is 2 MBW units: unit u = (row block u % MBW, half u / MBW), four
@@ -1097,6 +1211,65 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
                 if (use_mask) apply_mask(MBE_C{}, SUB_C{}, tile_mask);
             }
             if constexpr (GROUP && !DEFER) apply_codes(MBE_C{}, tile_codes);
+            if constexpr (I8) {
+                // ---- int8 test.  With q = (Q + dq) / c_q and x = (X + dx) / c_t (Q, X the stored integers; c_q, c_t the
+                // stored floats, so both identities are exact):   q.x c_q c_t = Q.X + Q.dx + dq.(X + dx),   and by
+                // Cauchy-Schwarz |Q.dx| <= ||Q|| e_t, |dq.(X + dx)| <= e_q (n_t + e_t).  Hence q.x > tau implies
+                //     Q.X > tau c_q c_t - M,     M = ||Q|| e_t + e_q (n_t + e_t)
+                // for every row of the tile: testing acc = Q.X (exact in int32) against any number <= the right-hand
+                // side keeps every row the fp16 filter could keep.  The right-hand side is evaluated in float32 with at
+                // most two roundings in t and four in M and t - M, each relative 2^-24 of |t| or M (all terms of M are
+                // non-negative): the error is below 6 * 2^-24 (|t| + M), and delta = 2^-20 (|t| + M) + 1e-30 covers it
+                // (the constant: a t that underflows to zero while the true bound is a hair below an integer).  acc is
+                // an integer, so acc > x <=> acc > floor(x).  t = +inf (the true bound exceeds every possible acc) and a
+                // NaN (a query that takes no part: k_prep_i8) pass nothing; t = -inf passes everything.
+                int thr_i[4];
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    const float t = thr[n] * tile_ct;
+                    const float mg = fmaf(qn8[n], tile_et, eq8[n] * (tile_nt + tile_et));
+                    const float lo = (t - mg) - (fabsf(t) + mg) * 9.5367431640625e-7f - 1e-30f;
+                    thr_i[n] = !(lo <= 2.0e9f) ? INT32_MAX : lo < -2.0e9f ? INT32_MIN : (int)floorf(lo);
+                    // a tile with a non-finite value (n_t = +inf): every row passes
+                    if (!(tile_nt < INFINITY)) thr_i[n] = thr[n] < INFINITY ? INT32_MIN : INT32_MAX;
+                }
+                if (r0 + (int64_t)(tile_begin + tile + 1) * TM > r1) {  // rows past the end: below every threshold
+#pragma unroll
+                    for (int m = 0; m < MBE; ++m)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (trow0 + m * 16 + r >= r1) {
+#pragma unroll
+                                for (int n = 0; n < 4; ++n) acc[m][n][r] = INT32_MIN;
+                            }
+                }
+                // the two-stage ballot of the float filter below, on integers; the survivor's score is a placeholder
+                // (k_rescore replaces it)
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    int bm[MBE];
+                    int mx = INT32_MIN;
+#pragma unroll
+                    for (int m = 0; m < MBE; ++m) {
+                        bm[m] = max(max(acc[m][n][0], acc[m][n][1]), max(acc[m][n][2], acc[m][n][3]));
+                        mx = max(mx, bm[m]);
+                    }
+                    if (__ballot(mx > thr_i[n]) != 0ull) {
+#pragma unroll
+                        for (int m = 0; m < MBE; ++m) {
+                            if (__ballot(bm[m] > thr_i[n]) == 0ull) continue;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                if (acc[m][n][r] > thr_i[n]) {
+                                    const int pos = cnt[n]++;
+                                    if (pos < CAP)
+                                        my_ent[n * 16 * CAP + pos] = Cand{(float)acc[m][n][r], (int32_t)(trow0 + m * 16 + r)};
+                                }
+                            }
+                        }
+                    }
+                }
+            } else {
             // rows past the end of the level exist only in its last tile: they become -inf there, once, instead of
             // being tested per element
             if (r0 + (int64_t)(tile_begin + tile + 1) * TM > r1) {
@@ -1137,10 +1310,11 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
                     }
                 }
             }
+            }  // !I8
 #pragma unroll
             for (int m = 0; m < MBE; ++m)
 #pragma unroll
-                for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int n = 0; n < 4; ++n) acc[m][n] = Acc{0, 0, 0, 0};
             ++tile;
         }
         }
@@ -1513,6 +1687,76 @@ __global__ __launch_bounds__(SEL_THREADS, 4) void k_select(int32_t* __restrict__
         carry_n[q] = n;
         qcount[q] = 0;  // ready for the next level
     }
+}
+
+// After the int8 level: one workgroup per query gives every entry of the query's list its float32 score -- the dot of the
+// packed fp16 row and the packed fp16 query; products of two halves are exact in float32, and k_final's eps bounds the
+// accumulation error of ANY order -- and keeps the entries with score > tau, the float filter's strict test, compacted in
+// place; qcount becomes their number.  What the list holds afterwards is what an fp16 level could have put there.
+// One wave per entry, four entries of a wave in flight; lane l covers 16-byte chunks l and l + 64 of the row (ks <= 16).
+__global__ __launch_bounds__(SEL_THREADS, 2) void k_rescore(const unsigned char* __restrict__ bank, int ks,
+                                                            const unsigned char* __restrict__ qpacked, int tnq,
+                                                            const float* __restrict__ tau, int32_t* __restrict__ qcount,
+                                                            Cand* __restrict__ qlist, int64_t nrows) {
+    __shared__ float score[QCAP];
+    __shared__ int kept;
+    const int q = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int NW = SEL_THREADS / 64;
+    const int n = min(qcount[q], QCAP);
+    Cand* list = qlist + (size_t)q * QCAP;
+    const unsigned char* qrow_base = qpacked + ((size_t)(q / tnq) * ks * tnq + (q % tnq)) * ISC_KSTEP_BYTES;
+    const int nch = ks * 8;
+    float qv[2][8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int ch = lane + 64 * h;
+        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+        if (ch < nch) raw = *reinterpret_cast<const uint4*>(qrow_base + (size_t)(ch >> 3) * tnq * ISC_KSTEP_BYTES + (ch & 7) * 16);
+        const _Float16* hv = reinterpret_cast<const _Float16*>(&raw);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qv[h][j] = (float)hv[j];
+    }
+    if (tid == 0) kept = 0;
+    for (int c0 = wave; c0 < n; c0 += 4 * NW) {
+        float acc[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = c0 + u * NW;
+            int row = c < n ? list[c].row : 0;
+            if ((unsigned)row >= (unsigned)nrows) row = 0;  // cannot happen; k_final refuses such an entry
+            acc[u] = 0.f;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int ch = lane + 64 * h;
+                if (ch < nch) {
+                    const uint4 raw = *reinterpret_cast<const uint4*>(bank + isc_packed_offset(row, ch >> 3, ks) + (ch & 7) * 16);
+                    const _Float16* hv = reinterpret_cast<const _Float16*>(&raw);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc[u] = fmaf((float)hv[j], qv[h][j], acc[u]);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float tot = isc_wave_sum(acc[u]);
+            if (lane == 0 && c0 + u * NW < n) score[c0 + u * NW] = tot;
+        }
+    }
+    __syncthreads();
+    // every entry is read before any is written: the compaction is in place
+    const float t = tau[q];
+    int rows[SEL_PER];
+#pragma unroll
+    for (int j = 0; j < SEL_PER; ++j) rows[j] = tid + SEL_THREADS * j < n ? list[tid + SEL_THREADS * j].row : 0;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < SEL_PER; ++j) {
+        const int i = tid + SEL_THREADS * j;
+        if (i < n && score[i] > t) list[atomicAdd(&kept, 1)] = Cand{score[i], rows[j]};
+    }
+    __syncthreads();
+    if (tid == 0) qcount[q] = kept;
 }
 
 // Exact float64 dots of `nc` candidates with one query: one wave per candidate, a lane covers the 16-byte chunk `ch` of
@@ -1947,12 +2191,28 @@ __host__ inline IscGroups pass_filter(IscGroups g, int q0, int q, const int32_t*
 // RowMask: empty, or the row filter of isc_cosine_topk_masked (const uint32_t*), handed to every filter launch and k_exact;
 // or the IscGroups of isc_cosine_topk_grouped.  k_final and k_final2 are the masked ones in both cases: neither reads the
 // filter, and the short-list proof of k_final holds for any per-(row, query) predicate.
+// The int8 level ("The int8 level"): an fp16 search with several 256-query tiles runs its LAST level on
+// the bank's int8 shadow when the plan has a level between the sample and the last one -- the last level is where the time is
+// and the only one whose threshold is strong enough to absorb what the loosened int8 test lets through.  The loosening
+// multiplies the survivors by a data-dependent factor (about 8 on unit rows of 768 iid dimensions); the level is taken
+// only if I8_INFLATION times the float filter's expected survivors, kp (rows of the level / rows before it), still fit the
+// budget the level's lists are sized for.  A bank that inflates more overflows a list: the query is flagged and redone by
+// the fp16 filter, as after any overflow.  Dpad 127^2 < 2^24 keeps an accumulator exactly convertible to float32.
+constexpr int I8_INFLATION = 16;
+bool plan_uses_i8(const Plan& p, int d) {
+    if (p.tnq != 256 || p.qtiles <= 1 || p.nlevels < 3) return false;
+    if ((int64_t)isc_shadow_ksteps(d) * ISC_SHADOW_KSTEP_DIMS * 127 * 127 >= (1 << 24)) return false;
+    const Level& l = p.levels[p.nlevels - 1];
+    return (double)p.kp * (double)(l.r1 - l.r0) / (double)l.r0 * I8_INFLATION <= (double)p.budget;
+}
+
 template <typename T, typename TQ, typename... RowMask>
 int run(const void* bank, int64_t n, int d, const void* queries, int q_total, int64_t ldq, int k, int64_t index_base,
         const float* norm_bound, float* out_s, int64_t* out_i, int32_t* status, void* ws_base, hipStream_t stream,
-        RowMask... rm) {
+        const void* shadow, RowMask... rm) {
     constexpr bool MASK = sizeof...(RowMask) > 0;
     const Plan p = make_plan(n, q_total, k);
+    const bool use_i8 = std::is_same<T, _Float16>::value && !MASK && shadow != nullptr && plan_uses_i8(p, d);
 #ifdef ISC_ABLATION
     static const bool thr_inf_set = [] {
         const int v = getenv("ISC_THR_INF") != nullptr;
@@ -1974,9 +2234,29 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q_total, in
                            d, ksteps, p.qpad, p.tnq, w.qpacked, w.tau, w.carry_n, w.qcount, w.qflag,
                            w.exact.redo_count, w.exact.done, w.r_count, w.tau2, w.qcount2, w.qflag2, status,
                            q0 == 0 ? 1 : 0);
+        const int ks8 = isc_shadow_ksteps(d);
+        if (use_i8)
+            hipLaunchKernelGGL((k_prep_i8<TQ>), dim3(p.qpad / 4), dim3(256), 0, stream, qptr, ldq, q, d, ks8, p.tnq,
+                               w.qpacked8, w.qrec8);
         const FilterIO io{w.qpacked, w.tau, w.qcount, w.qflag, nullptr};
         for (int li = 0; li < p.nlevels; ++li) {
             const Level& l = p.levels[li];
+            if (use_i8 && li == p.nlevels - 1) {
+                // the last level on the shadow bank: the same segments, the int8 kernel, then the float32 re-score
+                const unsigned char* sh = static_cast<const unsigned char*>(shadow);
+                const IscShadowArgs sa{reinterpret_cast<const IscShadowRec*>(sh + isc_shadow_data_bytes(n, d)), w.qrec8};
+                for_each_segment(l, p, [&](const Level& ls) {
+                    isc_timing_begin(ISC_KERNEL_DOTS_FILTER, stream);
+                    hipLaunchKernelGGL((k_dots_filter<signed char, 256, 12, false, IscShadowArgs>),
+                                       dim3(ls.nchunks, p.qtiles), dim3(NTHREADS), 0, stream, sh, ls.r0, ls.r1,
+                                       ls.tiles_per_chunk, ls.ntiles, w.qpacked8, ks8, w.tau, p.qpad, w.seg_ent, w.qcount,
+                                       w.qlist, p.kp, p.nslots, w.qflag, status, (const int32_t*)nullptr, sa);
+                    isc_timing_end(ISC_KERNEL_DOTS_FILTER, stream);
+                });
+                hipLaunchKernelGGL(k_rescore, dim3(q), dim3(SEL_THREADS), 0, stream, bank_bytes, ksteps, w.qpacked, p.tnq,
+                                   w.tau, w.qcount, w.qlist, n);
+                continue;
+            }
             // With several query-tile workgroups per chunk, a long level runs as several launches over consecutive row
             // ranges (same thresholds, no selection in between): the partner workgroups that share a chunk's bank rows
             // through their XCD's L2 drift apart as a launch goes on, and a kernel boundary realigns them for free
@@ -2080,7 +2360,7 @@ namespace {
 int topk(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q, int64_t ldq, int k,
          int64_t index_base, const float* norm_bound, float* out_scores, int64_t* out_indices, int32_t* status,
          void* workspace, size_t workspace_bytes, const uint32_t* row_mask, void* stream,
-         const IscGroups* groups = nullptr) {
+         const IscGroups* groups = nullptr, const void* shadow = nullptr) {
     ISC_REQUIRE(bank && queries && out_scores && out_indices && status);
     ISC_REQUIRE(q_dtype == ISC_F16 || q_dtype == ISC_F32);
     const int st = check_args(dtype, N, D, Q, k);
@@ -2092,11 +2372,11 @@ int topk(const void* bank, int dtype, int64_t N, int D, const void* queries, int
     if (!workspace || workspace_bytes < need) return ISC_ERR_WORKSPACE;
 #define ISC_RUN(T_, TQ_)                                                                                             \
     return groups   ? run<T_, TQ_>(bank, N, D, queries, Q, ldq, k, index_base, norm_bound, out_scores, out_indices,    \
-                                   status, workspace, isc_stream(stream), *groups)                                     \
+                                   status, workspace, isc_stream(stream), nullptr, *groups)                                     \
            : row_mask ? run<T_, TQ_>(bank, N, D, queries, Q, ldq, k, index_base, norm_bound, out_scores, out_indices,    \
-                                   status, workspace, isc_stream(stream), row_mask)                                    \
+                                   status, workspace, isc_stream(stream), nullptr, row_mask)                                    \
                     : run<T_, TQ_>(bank, N, D, queries, Q, ldq, k, index_base, norm_bound, out_scores, out_indices,    \
-                                   status, workspace, isc_stream(stream))
+                                   status, workspace, isc_stream(stream), shadow)
     if (dtype == ISC_F16) {
         if (q_dtype == ISC_F16) ISC_RUN(_Float16, _Float16);
         ISC_RUN(_Float16, float);
@@ -2114,6 +2394,24 @@ extern "C" int isc_cosine_topk(const void* bank, int dtype, int64_t N, int D, co
                                void* stream) {
     return topk(bank, dtype, N, D, queries, q_dtype, Q, ldq, k, index_base, norm_bound, out_scores, out_indices, status,
                 workspace, workspace_bytes, nullptr, stream);
+}
+
+extern "C" int isc_cosine_topk_shadow(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,
+                                      int Q, int64_t ldq, int k, int64_t index_base, const float* norm_bound,
+                                      float* out_scores, int64_t* out_indices, int32_t* status, void* workspace,
+                                      size_t workspace_bytes, const void* shadow, void* stream) {
+    ISC_REQUIRE(dtype == ISC_F16 || shadow == nullptr);
+    if (!isc_aligned(shadow, 256)) return ISC_ERR_ALIGNMENT;
+    return topk(bank, dtype, N, D, queries, q_dtype, Q, ldq, k, index_base, norm_bound, out_scores, out_indices, status,
+                workspace, workspace_bytes, nullptr, stream, nullptr, shadow);
+}
+
+extern "C" int isc_cosine_topk_uses_shadow(int dtype, int64_t N, int D, int Q, int k, int* uses) {
+    ISC_REQUIRE(uses);
+    const int st = check_args(dtype, N, D, Q, k);
+    if (st != ISC_OK) return st;
+    *uses = dtype == ISC_F16 && plan_uses_i8(make_plan(N, Q, k), D) ? 1 : 0;
+    return ISC_OK;
 }
 
 extern "C" int isc_cosine_topk_masked(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,

@@ -238,6 +238,7 @@ class EmbeddingBank:
         presharded: bool = False,
         row_groups: Tensor | None = None,
         capacity: int | None = None,
+        shadow: bool = True,
     ) -> None:
         if not isinstance(embeddings, Tensor) or not embeddings.dtype.is_floating_point:
             raise TypeError("embeddings must be a floating point torch.Tensor")
@@ -267,6 +268,10 @@ class EmbeddingBank:
         if self.dim == 0:
             raise ValueError("embedding dimension must be positive")
         self.normalize = bool(normalize)
+        # int8 shadow of an fp16 bank (`isc_bank_quantize`, +50 % of the bank's memory): built at the first plain search
+        # whose plan uses it (more than 256 queries on a bank of millions of rows), dropped by whatever changes the image
+        self.shadow = bool(shadow)
+        self._shadow: Tensor | None = None
         if capacity is None:
             self._bank = self._store(embeddings, normalize)
         else:
@@ -458,6 +463,7 @@ class EmbeddingBank:
         self._bank, self._fill, self._capacity = packed, fill, capacity
         if self.group_labels is not None:
             self._row_codes = codes
+        self._shadow = None
         # sized by the image's row count
         self._workspaces = {}
         self._range_ws = None
@@ -471,6 +477,7 @@ class EmbeddingBank:
         if self._fill is None or capacity > self.capacity:
             self._wait_for_issued()
             self._relayout(capacity)
+        self._shadow = None
         self._revision += 1
         self._fill_filter = RowFilter(self, self._fill, None)
 
@@ -531,6 +538,7 @@ class EmbeddingBank:
         if row_origin is not None:
             self.row_origin = torch.cat([self.row_origin, row_origin.to(device=self.row_origin.device,
                                                                         dtype=self.row_origin.dtype)])
+        self._shadow = None
         self._revision += 1
         self._fill_filter = RowFilter(self, self._fill, None)
         return range(self.index_base + first, self.index_base + first + m)
@@ -757,6 +765,32 @@ class EmbeddingBank:
                 self._captured_workspaces.append(ws)
         return ws
 
+    def _shadow_for(self, nq: int, k: int) -> Tensor | None:
+        """The bank's int8 shadow if a plain search of `nq` queries uses it (`isc_cosine_topk_uses_shadow`: an fp16 bank,
+        more than 256 queries per pass, a plan with a level between the sample and the last), built on the current stream
+        the first time and kept until `append` / `reserve` change the image.  None while the stream is being captured: the
+        fp16 levels run then, with the same answer."""
+        if not self.shadow or self.dtype != torch.float16 or nq <= 256 or self._fill is not None:
+            return None
+        if torch.cuda.is_current_stream_capturing():  # (a graph would pin a buffer that `append` / `reserve` drop)
+            return None
+        if self._shadow is None:
+            lib = _lib.load()
+            uses = _lib.c_int()
+            _lib.check(lib.isc_cosine_topk_uses_shadow(_lib.ISC_F16, self.capacity, self.dim, nq, k, uses),
+                       "isc_cosine_topk_uses_shadow")
+            if not uses.value:
+                return None
+            need = _lib.c_size_t()
+            _lib.check(lib.isc_bank_shadow_bytes(self.capacity, self.dim, need), "isc_bank_shadow_bytes")
+            shadow = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                st = lib.isc_bank_quantize(self._bank.data_ptr(), self.capacity, self.dim, shadow.data_ptr(),
+                                           shadow.numel(), _lib.stream_handle(self.device))
+            _lib.check(st, "isc_bank_quantize")
+            self._shadow = shadow
+        return self._shadow
+
     def _new_out(self, nq: int, k: int) -> tuple[Tensor, Tensor, Tensor]:
         """What a local search writes when the caller gave no `out`: (scores [Q, k], indices [Q, k], status int32[4])."""
         return (torch.empty((nq, k), dtype=torch.float32, device=self.device),
@@ -794,6 +828,7 @@ class EmbeddingBank:
         nq = queries.shape[0]
         scores, indices, status = out if out is not None else self._new_out(nq, k)
         ws = self._workspace(nq, k, lane)
+        shadow = self._shadow_for(nq, k) if mask is None and groups is None else None
         if stream is not None:
             # every tensor this call touches was allocated on some other stream: tell the allocator the lane uses it, so
             # that nothing handed back early (a dropped handle, a dropped bank, a workspace bucket pushed out of the cache)
@@ -805,12 +840,20 @@ class EmbeddingBank:
             if groups is not None:
                 groups.record_stream(stream)
                 self._row_codes.record_stream(stream)
+            if shadow is not None:
+                # built on the caller's stream: the lane starts behind it
+                built = torch.cuda.Event()
+                built.record(torch.cuda.current_stream(self.device))
+                stream.wait_event(built)
+                shadow.record_stream(stream)
         args = (
             self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.capacity, self.dim, queries.data_ptr(),
             _lib.dtype_code(queries.dtype), nq, queries.stride(0), k, self.index_base, self._norm_bound.data_ptr(),
             scores.data_ptr(), indices.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
         )
-        self._row_search("isc_cosine_topk", args, mask, groups,
+        if shadow is not None:
+            args += (shadow.data_ptr(),)
+        self._row_search("isc_cosine_topk_shadow" if shadow is not None else "isc_cosine_topk", args, mask, groups,
                          stream.cuda_stream if stream is not None else _lib.stream_handle(self.device))
         self.last_status = status
         return scores, indices

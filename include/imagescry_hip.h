@@ -408,6 +408,27 @@ int isc_cosine_topk(const void* bank, int dtype, int64_t N, int D, const void* q
                     int k, int64_t index_base, const float* norm_bound, float* out_scores, int64_t* out_indices,
                     int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* int8 shadow of a packed fp16 bank: the same [tile][K step][row][128 B] scheme with 128 int8 per K step, one scale per
+ * tile of 256 rows, followed by one fp32 record per tile (scale, inverse scale, bounds of the rows' quantisation residual
+ * and quantised norm).  isc_bank_shadow_bytes: its size (data + records; about half the fp16 bank).  isc_bank_quantize:
+ * build it from the packed bank, one pass on `stream`; `shadow` 256-byte aligned.  The shadow describes the bank as it was
+ * when the call ran: build it again after isc_bank_pack / isc_bank_append / isc_bank_repack touched the bank.
+ *
+ * isc_cosine_topk_shadow: isc_cosine_topk with the shadow of `bank` (or NULL: exactly isc_cosine_topk).  Same results,
+ * bit for bit: when the call has more than 256 queries per pass and its plan has a level between the sample and the last
+ * one (isc_cosine_topk_uses_shadow tells, host only), the LAST filter level streams the int8 shadow instead of the fp16
+ * rows -- half the bytes and half the matrix-core work per row -- with a threshold loosened by a proven bound of the
+ * quantisation error, so that it keeps every row the fp16 filter keeps; the survivors are re-scored from the fp16 rows
+ * and filtered with the fp16 threshold before the exact pass sees them.  Every other call runs isc_cosine_topk's launches.
+ * Same workspace (isc_cosine_topk_workspace_bytes). */
+int isc_bank_shadow_bytes(int64_t N, int D, size_t* bytes);
+int isc_bank_quantize(const void* packed, int64_t N, int D, void* shadow, size_t shadow_bytes, void* stream);
+int isc_cosine_topk_uses_shadow(int dtype, int64_t N, int D, int Q, int k, int* uses);
+int isc_cosine_topk_shadow(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
+                           int64_t ldq, int k, int64_t index_base, const float* norm_bound, float* out_scores,
+                           int64_t* out_indices, int32_t* status, void* workspace, size_t workspace_bytes,
+                           const void* shadow, void* stream);
+
 /* isc_cosine_topk over the rows a row filter allows: the answer of isc_cosine_topk on the bank of the allowed rows alone,
  * with their indices in the whole bank, bit for bit.  Same arguments, limits and workspace (isc_cosine_topk_workspace_bytes)
  * plus
