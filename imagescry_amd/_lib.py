@@ -87,6 +87,19 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
         c_int,
         [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    "isc_bank_remove": (
+        c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    ),
+    "isc_bank_replace": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int64, c_int, c_float, c_void_p, c_int, c_void_p,
+         c_void_p, c_void_p],
+    ),
+    "isc_bank_repack_map": (
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p],
+    ),
     "isc_nchw_to_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "isc_conv2d_nhwc": (
         c_int,
@@ -175,6 +188,7 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     ),
     "isc_row_mask_words": (c_int, [c_int64, POINTER(c_size_t)]),
     "isc_row_mask_pack": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "isc_row_mask_unpack": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "isc_cosine_topk_masked": (
         c_int,
         [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p,

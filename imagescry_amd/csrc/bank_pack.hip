@@ -1,8 +1,9 @@
 // Packing of embedding rows into the tile-contiguous, row-permuted bank layout (include/imagescry_hip.h:
 // isc_bank_pack, isc_bank_unpack, isc_bank_packed_bytes, isc_bank_permutation), and of a row filter into the same row
 // order (isc_row_mask_words, isc_row_mask_pack), and of row group codes (isc_row_groups_pack); in-place append to a bank
-// packed for a reserved capacity and its growth (isc_bank_append, isc_bank_repack); the int8 shadow of an fp16 bank
-// (isc_bank_shadow_bytes, isc_bank_quantize).
+// packed for a reserved capacity and its growth (isc_bank_append, isc_bank_repack); removal, replacement and compaction of
+// such a bank (isc_bank_remove, isc_bank_replace, isc_bank_repack_map, isc_row_mask_unpack); the int8 shadow of an fp16
+// bank (isc_bank_shadow_bytes, isc_bank_quantize).
 #include "bank_layout.h"
 #include "isc_common.h"
 
@@ -129,6 +130,77 @@ __global__ __launch_bounds__(256) void k_bank_repack(const unsigned char* __rest
     }
 }
 
+// In-place removal (isc_bank_remove): one thread per index clears the row's bit in the fill bitmap -- an atomic AND: 32
+// positions share a word, and the list may name a row twice.  Only the thread whose atomic saw the bit set owns the
+// removal: it is counted (one atomic per wave), its group code becomes -2 and its group's count goes down by one.  An
+// index outside [0, n_filled) is skipped; row bytes are not touched.
+__global__ __launch_bounds__(256) void k_bank_remove(const int64_t* __restrict__ rows, int64_t n_rows, int64_t n_filled,
+                                                     IscPerm pm, uint32_t* __restrict__ fill_mask,
+                                                     int32_t* __restrict__ packed_codes,
+                                                     unsigned long long* __restrict__ group_counts,
+                                                     unsigned long long* __restrict__ removed_count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool won = false;
+    if (i < n_rows) {
+        const int64_t r = rows[i];
+        if (r >= 0 && r < n_filled) {
+            const int64_t pos = isc_perm_pos(pm, r);
+            const uint32_t bit = 1u << (pos & 31);
+            won = (atomicAnd(fill_mask + (pos >> 5), ~bit) & bit) != 0;
+            if (won && packed_codes) {
+                const int32_t c = packed_codes[pos];
+                packed_codes[pos] = -2;
+                if (group_counts && c >= 0) atomicAdd(group_counts + c, ~0ull);  // - 1 of the int64 count
+            }
+        }
+    }
+    const unsigned long long bits = __ballot(won);
+    if (removed_count && won && (threadIdx.x & 63) == __ffsll(bits) - 1)
+        atomicAdd(removed_count, (unsigned long long)__popcll(bits));
+}
+
+// In-place replacement (isc_bank_replace): k_bank_pack's row written at the position of ORIGINAL row row_index[r].  The
+// wave reads the row's fill bit first: a removed (or never filled) row stays as it is.  An index outside [0, capacity) is
+// skipped.
+template <typename TIN, typename TOUT>
+__global__ __launch_bounds__(256) void k_bank_replace(const TIN* __restrict__ x, int64_t n_rows, int d, int64_t ldx,
+                                                      const int64_t* __restrict__ row_index, IscPerm pm, int normalize,
+                                                      float eps, unsigned char* __restrict__ packed, int ks,
+                                                      unsigned* __restrict__ norm_bound,
+                                                      const uint32_t* __restrict__ fill_mask) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n_rows) return;
+    const int64_t orig = row_index[r];
+    if (orig < 0 || orig >= pm.n) return;
+    const int64_t row = isc_perm_pos(pm, orig);
+    if (fill_mask && !((fill_mask[row >> 5] >> (row & 31)) & 1u)) return;
+    isc_pack_row<TIN, TOUT>(x + r * ldx, d, row, normalize, eps, packed, ks, norm_bound, threadIdx.x & 63);
+}
+
+// Compaction of an appendable bank (isc_bank_repack_map): k_bank_repack with the destination row taken from an index map:
+// ORIGINAL row first_row + r of the source goes to ORIGINAL row new_index[first_row + r] of the destination; a negative
+// entry (a removed row) or one past the destination's rows moves nothing.
+__global__ __launch_bounds__(256) void k_bank_repack_map(const unsigned char* __restrict__ src, IscPerm spm,
+                                                         unsigned char* __restrict__ dst, IscPerm dpm, int ks,
+                                                         int64_t first_row, int64_t n_rows,
+                                                         const int32_t* __restrict__ src_codes,
+                                                         int32_t* __restrict__ dst_codes, uint32_t* __restrict__ dst_fill,
+                                                         const int64_t* __restrict__ new_index) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n_rows) return;
+    const int64_t ni = new_index[first_row + r];
+    if (ni < 0 || ni >= dpm.n) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t from = isc_perm_pos(spm, first_row + r), to = isc_perm_pos(dpm, ni);
+    for (int c = lane; c < ks * 8; c += 64)
+        *reinterpret_cast<uint4*>(dst + isc_packed_offset(to, c >> 3, ks) + (c & 7) * 16) =
+            *reinterpret_cast<const uint4*>(src + isc_packed_offset(from, c >> 3, ks) + (c & 7) * 16);
+    if (lane == 0) {
+        atomicOr(dst_fill + (to >> 5), 1u << (to & 31));
+        if (dst_codes) dst_codes[to] = src_codes[from];
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_bank_unpack(const unsigned char* __restrict__ packed, int d, int ks,
                                                      IscPerm pm, int64_t first_row, int64_t n_rows,
@@ -153,6 +225,15 @@ __global__ __launch_bounds__(256) void k_row_mask_pack(const uint8_t* __restrict
     if (lane == 0) packed_mask[p >> 5] = (uint32_t)bits;
     if (lane == 32) packed_mask[p >> 5] = (uint32_t)(bits >> 32);
     if (allowed_count && lane == 0 && bits != 0ull) atomicAdd(allowed_count, (unsigned long long)__popcll(bits));
+}
+
+// Inverse of k_row_mask_pack for the first n_rows ORIGINAL rows: one thread per row reads the bit at its packed position.
+__global__ __launch_bounds__(256) void k_row_mask_unpack(const uint32_t* __restrict__ packed_mask, IscPerm pm,
+                                                         int64_t n_rows, uint8_t* __restrict__ allow) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n_rows) return;
+    const int64_t p = isc_perm_pos(pm, r);
+    allow[r] = (uint8_t)((packed_mask[p >> 5] >> (p & 31)) & 1u);
 }
 
 // Row group codes of a grouped search: one thread per PACKED position p of the padded bank; code[orig(p)] for p < n, -2
@@ -397,6 +478,70 @@ extern "C" int isc_bank_repack(const void* src_packed, int64_t src_capacity, voi
     return isc_launch_status();
 }
 
+extern "C" int isc_bank_remove(const int64_t* rows, int64_t n_rows, int64_t n_filled, int64_t capacity,
+                               uint32_t* fill_mask, int32_t* packed_codes, int64_t* group_counts, int64_t* removed_count,
+                               void* stream) {
+    ISC_REQUIRE(rows && fill_mask && n_rows > 0 && n_filled >= 0);
+    ISC_REQUIRE(capacity > 0 && capacity >= n_filled && capacity <= 0x7ffffffe);
+    ISC_REQUIRE(!group_counts || packed_codes);
+    if (!isc_aligned(rows, 8) || !isc_aligned(fill_mask, 4) || !isc_aligned(packed_codes, 16) ||
+        !isc_aligned(group_counts, 8) || !isc_aligned(removed_count, 8))
+        return ISC_ERR_ALIGNMENT;
+    const int64_t blocks = isc_ceil_div<int64_t>(n_rows, 256);
+    if (blocks > 0x7fffffff) return ISC_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_bank_remove, dim3((unsigned)blocks), dim3(256), 0, isc_stream(stream), rows, n_rows, n_filled,
+                       isc_make_perm(capacity), fill_mask, packed_codes,
+                       reinterpret_cast<unsigned long long*>(group_counts),
+                       reinterpret_cast<unsigned long long*>(removed_count));
+    return isc_launch_status();
+}
+
+extern "C" int isc_bank_replace(const void* rows, int in_dtype, int64_t n_rows, int D, int64_t ldx,
+                                const int64_t* row_index, int64_t capacity, int normalize, float eps, void* packed,
+                                int dtype, float* norm_bound, const uint32_t* fill_mask, void* stream) {
+    ISC_REQUIRE(rows && row_index && packed && check_dtype(in_dtype) && check_dtype(dtype));
+    ISC_REQUIRE(n_rows > 0 && D > 0 && ldx >= D);
+    ISC_REQUIRE(capacity > 0 && capacity <= 0x7ffffffe);
+    if (!isc_aligned(packed, 16) || !isc_aligned(row_index, 8) || !isc_aligned(fill_mask, 4)) return ISC_ERR_ALIGNMENT;
+    const int64_t blocks = isc_ceil_div<int64_t>(n_rows, 4);
+    if (blocks > 0x7fffffff) return ISC_ERR_UNSUPPORTED;
+    const int ks = isc_ksteps(D, dtype == ISC_F16 ? 2 : 4);
+    unsigned char* out = static_cast<unsigned char*>(packed);
+    hipStream_t s = isc_stream(stream);
+    const IscPerm pm = isc_make_perm(capacity);
+    const dim3 grid((unsigned)blocks), block(256);
+#define ISC_REPLACE(TIN, TOUT)                                                                                         \
+    hipLaunchKernelGGL((k_bank_replace<TIN, TOUT>), grid, block, 0, s, static_cast<const TIN*>(rows), n_rows, D, ldx, \
+                       row_index, pm, normalize, eps, out, ks, reinterpret_cast<unsigned*>(norm_bound), fill_mask)
+    if (in_dtype == ISC_F32 && dtype == ISC_F16) ISC_REPLACE(float, _Float16);
+    else if (in_dtype == ISC_F32 && dtype == ISC_F32) ISC_REPLACE(float, float);
+    else if (in_dtype == ISC_F16 && dtype == ISC_F16) ISC_REPLACE(_Float16, _Float16);
+    else ISC_REPLACE(_Float16, float);
+#undef ISC_REPLACE
+    return isc_launch_status();
+}
+
+extern "C" int isc_bank_repack_map(const void* src_packed, int64_t src_capacity, void* dst_packed, int64_t dst_capacity,
+                                   int dtype, int D, int64_t first_row, int64_t n_rows, const int32_t* src_codes,
+                                   int32_t* dst_codes, uint32_t* dst_fill_mask, const int64_t* new_index, void* stream) {
+    ISC_REQUIRE(src_packed && dst_packed && dst_fill_mask && new_index && src_packed != dst_packed && check_dtype(dtype));
+    ISC_REQUIRE(n_rows > 0 && D > 0 && first_row >= 0);
+    ISC_REQUIRE(src_capacity >= first_row + n_rows && dst_capacity > 0);
+    ISC_REQUIRE(src_capacity <= 0x7ffffffe && dst_capacity <= 0x7ffffffe);
+    ISC_REQUIRE((src_codes == nullptr) == (dst_codes == nullptr));
+    if (!isc_aligned(src_packed, 16) || !isc_aligned(dst_packed, 16) || !isc_aligned(dst_fill_mask, 4) ||
+        !isc_aligned(src_codes, 4) || !isc_aligned(dst_codes, 16) || !isc_aligned(new_index, 8))
+        return ISC_ERR_ALIGNMENT;
+    const int64_t blocks = isc_ceil_div<int64_t>(n_rows, 4);
+    if (blocks > 0x7fffffff) return ISC_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_bank_repack_map, dim3((unsigned)blocks), dim3(256), 0, isc_stream(stream),
+                       static_cast<const unsigned char*>(src_packed), isc_make_perm(src_capacity),
+                       static_cast<unsigned char*>(dst_packed), isc_make_perm(dst_capacity),
+                       isc_ksteps(D, dtype == ISC_F16 ? 2 : 4), first_row, n_rows, src_codes, dst_codes, dst_fill_mask,
+                       new_index);
+    return isc_launch_status();
+}
+
 extern "C" int isc_bank_unpack(const void* packed, int dtype, int D, int64_t n_total, int64_t first_row,
                                int64_t n_rows, void* rows, int64_t ldy, void* stream) {
     ISC_REQUIRE(packed && rows && check_dtype(dtype) && D > 0 && n_rows > 0 && first_row >= 0 && ldy >= D);
@@ -427,6 +572,15 @@ extern "C" int isc_row_mask_pack(const uint8_t* allow, int64_t N, uint32_t* pack
     const int64_t tiles = isc_ceil_div<int64_t>(N, ISC_TILE_ROWS);
     hipLaunchKernelGGL(k_row_mask_pack, dim3((unsigned)tiles), dim3(256), 0, isc_stream(stream), allow, isc_make_perm(N),
                        packed_mask, reinterpret_cast<unsigned long long*>(allowed_count));
+    return isc_launch_status();
+}
+
+extern "C" int isc_row_mask_unpack(const uint32_t* packed_mask, int64_t N, int64_t n_rows, uint8_t* allow, void* stream) {
+    ISC_REQUIRE(packed_mask && allow && N > 0 && N <= 0x7ffffffe && n_rows > 0 && n_rows <= N);
+    if (!isc_aligned(packed_mask, 4)) return ISC_ERR_ALIGNMENT;
+    const int64_t blocks = isc_ceil_div<int64_t>(n_rows, 256);
+    hipLaunchKernelGGL(k_row_mask_unpack, dim3((unsigned)blocks), dim3(256), 0, isc_stream(stream), packed_mask,
+                       isc_make_perm(N), n_rows, allow);
     return isc_launch_status();
 }
 

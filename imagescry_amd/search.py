@@ -171,7 +171,8 @@ class RowFilter:
     """A set of allowed rows of ONE bank, made by `EmbeddingBank.row_filter`: the bitmap of this rank's rows in the bank's
     packed row order (`isc_row_mask_pack`) and the number of rows it allows (int64 [1], device).  Searches given it as
     `mask=` answer as if the bank held the allowed rows only, with their indices in the whole bank.  A filter describes
-    the bank as it was when the filter was made: after `EmbeddingBank.append` or `reserve` it is refused."""
+    the bank as it was when the filter was made: after `EmbeddingBank.append`, `reserve`, `remove`, `replace` or `compact`
+    it is refused."""
 
     __slots__ = ("packed", "allowed_count", "_bank", "_revision")
 
@@ -224,6 +225,8 @@ class EmbeddingBank:
     _fill_filter: RowFilter | None = None
     _group_counts: Tensor | None = None
     _revision = 0
+    # the rows `remove` took out and `compact` has not closed up yet: their fill bits are 0, their indices stay reserved
+    _num_removed = 0
     _GROW_BLOCK = 1 << 20  # rows per isc_bank_pack / isc_bank_append / isc_bank_repack launch
     _n_total: int | None = None  # rows of the whole sharded bank, learnt by `_global_rows`
 
@@ -437,6 +440,65 @@ class EmbeddingBank:
                 )
                 _lib.check(st, "isc_bank_repack")
 
+    def _repack_map(self, src: Tensor, src_capacity: int, src_codes: Tensor | None, dst: Tensor, dst_capacity: int,
+                    dst_codes: Tensor | None, dst_fill: Tensor, new_index: Tensor) -> None:
+        """`isc_bank_repack_map`: `_repack_rows` with row r landing at row `new_index[r]` (int64 `[len]`, device) of the
+        destination, a negative entry moving nothing.  A device hook."""
+        lib = _lib.load()
+        with torch.cuda.device(dst.device):
+            for r0 in range(0, self.num_local_rows, self._GROW_BLOCK):
+                st = lib.isc_bank_repack_map(
+                    src.data_ptr(), src_capacity, dst.data_ptr(), dst_capacity, _lib.dtype_code(self.dtype), self.dim, r0,
+                    min(self._GROW_BLOCK, self.num_local_rows - r0), _lib.ptr(src_codes), _lib.ptr(dst_codes),
+                    dst_fill.data_ptr(), new_index.data_ptr(), _lib.stream_handle(dst.device),
+                )
+                _lib.check(st, "isc_bank_repack_map")
+
+    def _remove_rows(self, index: Tensor, removed: Tensor) -> None:
+        """`isc_bank_remove` of the local rows `index` (int64 `[m]`, device, m > 0), one launch on the current stream: their
+        fill bits are cleared, their group codes become -2, `_group_counts` goes down, and the number of rows that were
+        still there is added to `removed` (int64 `[1]`, device).  A device hook."""
+        with torch.cuda.device(self.device):
+            st = _lib.load().isc_bank_remove(
+                index.data_ptr(), index.numel(), self.num_local_rows, self.capacity, self._fill.data_ptr(),
+                _lib.ptr(self._row_codes), _lib.ptr(self._group_counts if self._row_codes is not None else None),
+                removed.data_ptr(), _lib.stream_handle(self.device),
+            )
+        _lib.check(st, "isc_bank_remove")
+
+    def _replace_rows(self, embeddings: Tensor, index: Tensor, normalize: bool) -> None:
+        """`isc_bank_replace`: `embeddings[i]` is stored at local row `index[i]` (int64 `[m]`, device, distinct) unless that
+        row is removed; one launch per 2^20 rows on the current stream.  A device hook."""
+        _lib.require_device(embeddings, "rows")
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            for r0, rows in self._row_blocks(embeddings):
+                st = lib.isc_bank_replace(
+                    rows.data_ptr(), _lib.dtype_code(rows.dtype), rows.shape[0], self.dim, rows.stride(0),
+                    index[r0 : r0 + self._GROW_BLOCK].data_ptr(), self.capacity, int(normalize), 1e-12,
+                    self._bank.data_ptr(), _lib.dtype_code(self.dtype), self._norm_bound.data_ptr(), _lib.ptr(self._fill),
+                    _lib.stream_handle(self.device),
+                )
+                _lib.check(st, "isc_bank_replace")
+
+    def _unpack_mask(self, packed: Tensor, n_rows: int) -> Tensor:
+        """`isc_row_mask_unpack`: bool `[n_rows]`, the bits of the first `n_rows > 0` rows of a bitmap in this bank's packed
+        row order.  A device hook."""
+        allow = torch.empty(n_rows, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            st = _lib.load().isc_row_mask_unpack(packed.data_ptr(), self.capacity, n_rows, allow.data_ptr(),
+                                                 _lib.stream_handle(self.device))
+        _lib.check(st, "isc_row_mask_unpack")
+        return allow.view(torch.bool)
+
+    def _code_rows(self, codes: Tensor) -> Tensor:
+        """The local rows (int64, device, any order) whose stored group code is one of `codes` (int32, >= 0): tensor ops on
+        the packed codes, position p holding row `(mul * p) mod capacity`.  A device hook."""
+        mul, inv = _lib.c_int64(), _lib.c_int64()
+        _lib.check(_lib.load().isc_bank_permutation(self.capacity, mul, inv), "isc_bank_permutation")
+        pos = torch.isin(self._row_codes, codes).nonzero().squeeze(1)
+        return (pos * mul.value) % self.capacity
+
     def _wait_for_issued(self) -> None:
         """Order the caller's current stream behind everything this bank has issued elsewhere: both lane streams of
         `search_async` and the exchange stream.  An unresolved asynchronous search then never reads a half-updated image."""
@@ -450,12 +512,18 @@ class EmbeddingBank:
                 issued.record(stream)
                 cur.wait_event(issued)
 
-    def _relayout(self, capacity: int) -> None:
-        """Move the bank into a fresh image laid out for `capacity` rows (`isc_bank_repack`)."""
+    def _relayout(self, capacity: int, new_index: Tensor | None = None) -> None:
+        """Move the bank into a fresh image laid out for `capacity` rows (`isc_bank_repack`).  `new_index` (int64 `[len]`,
+        -1: the row stays behind): the rows move through it (`isc_bank_repack_map`); a bank with removed rows always moves
+        that way, so a growth neither moves nor revives them."""
         old = (self._bank, self._fill, self._row_codes)
+        if new_index is None and self._num_removed:
+            new_index = torch.where(self.live, torch.arange(self.num_local_rows, device=self.device), -1)
         packed, fill, codes = self._alloc_image(capacity, self.device, self.group_labels is not None)
-        if self.num_local_rows:
+        if self.num_local_rows and new_index is None:
             self._repack_rows(self._bank, self.capacity, self._row_codes, packed, capacity, codes, fill)
+        elif self.num_local_rows:
+            self._repack_map(self._bank, self.capacity, self._row_codes, packed, capacity, codes, fill, new_index)
         if self._captured_workspaces:
             # a graph captured before the growth still holds the old pointers: a stale replay must read stale memory,
             # never memory the allocator has handed to somebody else
@@ -543,6 +611,175 @@ class EmbeddingBank:
         self._fill_filter = RowFilter(self, self._fill, None)
         return range(self.index_base + first, self.index_base + first + m)
 
+    # ------------------------------------------------------------------ remove, replace, compact
+    def _refuse_sharded(self, what: str) -> None:
+        if self.process_group is not None:
+            raise ValueError(f"a sharded bank (process_group=) cannot {what}: its global indices are contiguous per rank "
+                             "and would shift")
+
+    def _local_index(self, index: object, name: str) -> Tensor:
+        """Global row indices (an integer tensor or a sequence of ints) as a contiguous int64 `[m]` tensor of LOCAL rows
+        on the bank's device; ValueError for one outside the bank (reads the extremes back to the host)."""
+        r = index if isinstance(index, Tensor) else torch.as_tensor(list(index), dtype=torch.int64)
+        if r.dtype.is_floating_point or r.dtype.is_complex or r.dtype == torch.bool or r.ndim != 1:
+            raise ValueError(f"{name} must be a 1-D sequence of integer row indices")
+        r = r.to(device=self.device, dtype=torch.int64) - self.index_base
+        if r.numel() and (int(r.min()) < 0 or int(r.max()) >= self.num_local_rows):
+            raise ValueError(f"{name} must lie in [{self.index_base}, {self.index_base + self.num_local_rows})")
+        return r.contiguous()
+
+    def _changed(self) -> None:
+        """What every call that changes the stored rows ends with: the shadow is stale, older `RowFilter`s are refused."""
+        self._shadow = None
+        self._revision += 1
+        self._fill_filter = None if self._fill is None else RowFilter(self, self._fill, None)
+
+    def _counts(self) -> Tensor:
+        """`_group_counts`, taken from the stored codes when nobody has kept it (a bare bank whose codes were set by hand)."""
+        if self._group_counts is None:
+            c = self._row_codes[self._row_codes >= 0].long()
+            self._group_counts = torch.bincount(c, minlength=self.group_labels.numel())
+        return self._group_counts
+
+    @property
+    def num_removed(self) -> int:
+        """Rows `remove` has taken out since the bank was built or last compacted (kept on the host)."""
+        return self._num_removed
+
+    @property
+    def live(self) -> Tensor:
+        """bool `[len]` on the bank's device: False for the rows `remove` has taken out (unpacked from the fill bitmap,
+        `isc_row_mask_unpack`)."""
+        n = self.num_local_rows
+        if not self._num_removed or n == 0:
+            return torch.ones(n, dtype=torch.bool, device=self.device)
+        return self._unpack_mask(self._fill, n)
+
+    def remove(self, *, rows: "Tensor | Sequence[int] | None" = None, image_ids: "Tensor | Sequence[int] | None" = None,
+               groups: "Tensor | Sequence[int] | None" = None) -> int:
+        """Take rows out of the bank, chosen by exactly one of
+        - `rows`: global row indices,
+        - `image_ids`: every cell of these images (needs `row_origin`, i.e. a bank from `from_database`),
+        - `groups`: every row that carries one of these `row_groups` labels (a label no row carries selects nothing),
+        and return how many rows the call actually removed: duplicates and rows removed before are tolerated and counted
+        once.  That count is one host read, like a grouped append's.  An index outside the bank raises ValueError before
+        anything is launched.
+
+        The selector becomes row indices with tensor ops; ONE launch (`isc_bank_remove`) then clears those rows' bits in the
+        fill bitmap, which is the mask of every later search: the answers are those of the bank without the rows, bit for
+        bit.  Row bytes are not touched.  Indices are stable: `len(bank)` stays the size of the index space, a removed
+        index is never returned again, `append` keeps numbering from `len`, and `k` is still validated against `len` (a
+        query with fewer than k rows left ends in score -inf, index -1 entries, as in any masked search).  `compact`
+        closes the holes.  On a grouped bank the rows' stored codes become -2 and the per-group counts go down on the
+        device; the planning figure of `search_groups` stays an upper bound until `compact`.
+
+        A bank that never reserved capacity gains a fill bitmap of all ones first (one `isc_row_mask_pack` launch, its
+        capacity is its length; the image does not move).  A `search` captured into a graph on a bank with spare capacity
+        replays over the removal -- it is the masked call, and no pointer changes.  A graph captured while the bank had
+        neither spare room nor holes holds the unmasked call: capture it again after the first `remove`.
+
+        Runs on the caller's current stream, behind everything the bank has issued on its own streams (unresolved
+        `search_async` handles see the bank as it was).  `RowFilter`s made before the call are refused afterwards.  A
+        sharded bank (`process_group=`) cannot remove."""
+        self._refuse_sharded("remove")
+        if sum(x is not None for x in (rows, image_ids, groups)) != 1:
+            raise ValueError("give exactly one of rows, image_ids or groups")
+        if rows is not None:
+            index = self._local_index(rows, "rows")
+        elif image_ids is not None:
+            if self.row_origin is None:
+                raise ValueError("image_ids needs row_origin: build the bank with EmbeddingBank.from_database")
+            if self.row_origin.shape[0] != self.num_local_rows:
+                raise ValueError("row_origin does not describe the bank's rows")
+            ids = image_ids if isinstance(image_ids, Tensor) else torch.as_tensor(list(image_ids), dtype=torch.int64)
+            origin = self.row_origin[:, 0]
+            index = torch.isin(origin, ids.to(device=origin.device, dtype=origin.dtype)).nonzero().squeeze(1).to(self.device)
+        else:
+            if self.group_labels is None:
+                raise ValueError("groups needs row groups: build the bank with row_groups= (or from_database)")
+            g = groups if isinstance(groups, Tensor) else torch.as_tensor(list(groups), dtype=torch.int64)
+            _check_labels(g, "groups", g.shape[0] if g.ndim == 1 else -1, "[m]", got=True)
+            codes = self._query_codes(g, g.shape[0])
+            index = self._code_rows(codes[codes >= 0])
+        if index.numel() == 0:
+            return 0
+        self._wait_for_issued()
+        if self._fill is None:
+            self._capacity = self.num_local_rows
+            self._fill = self._pack_filter(torch.ones(self.num_local_rows, dtype=torch.bool, device=self.device)).packed
+        if self._row_codes is not None:
+            self._counts()
+        count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._remove_rows(index, count)
+        removed = int(count.item())
+        self._num_removed += removed
+        self._changed()
+        return removed
+
+    def replace(self, indices: "Tensor | Sequence[int]", rows: Tensor, *, normalize: bool | None = None) -> None:
+        """Overwrite the stored vectors of the rows `indices` (global, distinct) with `rows` (floating `[m, D]`, on the
+        bank's device), in place: ONE launch that touches only those rows (`isc_bank_replace`), with the arithmetic of the
+        constructor and of `append` (`normalize` defaults to the bank's own setting), so the bank then equals the bank built
+        with those vectors substituted.  Group and origin of a row are kept.  A removed index is skipped: the row stays
+        removed.  Duplicate indices raise ValueError (found with one host read).  The norm bound the searches' rounding
+        guard reads can only rise, so it stays a valid upper bound.
+
+        No pointer changes: a captured masked `search` replays over the new vectors.  Stream order, stale `RowFilter`s and
+        sharded banks: as in `remove`."""
+        self._refuse_sharded("replace")
+        if not isinstance(rows, Tensor) or not rows.dtype.is_floating_point:
+            raise TypeError("rows must be a floating point torch.Tensor")
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"rows must have shape [m, {self.dim}], got {tuple(rows.shape)}")
+        if rows.device != self.device:
+            raise ValueError(f"rows are on {rows.device} but the bank is on {self.device}")
+        index = self._local_index(indices, "indices")
+        if index.shape[0] != rows.shape[0]:
+            raise ValueError(f"indices must name one row per vector: {index.shape[0]} indices for {rows.shape[0]} rows")
+        if index.numel() == 0:
+            return
+        if int(torch.unique(index).numel()) != index.numel():
+            raise ValueError("indices must be distinct")
+        self._wait_for_issued()
+        self._replace_rows(rows, index, self.normalize if normalize is None else bool(normalize))
+        self._changed()
+
+    def compact(self) -> Tensor:
+        """Close the holes `remove` left: the surviving rows move, in row order, into a fresh image of the same capacity
+        (`isc_bank_repack_map`, byte for byte; peak memory is the old image plus the new one).  Returns the int64
+        `[len_before]` map from old to new row index (local rows, on the bank's device), -1 for the removed rows.  With no
+        holes nothing happens and the identity map is returned.
+
+        Afterwards `len` is the number of surviving rows, `row_origin` holds their rows only, `group_labels` has lost the
+        labels no row carries any more (the stored codes are re-mapped) and the planning figure of `search_groups` is exact
+        again: the bank equals, in everything a caller can see, the bank built from the surviving rows with `capacity=`.
+        Graphs captured on the bank are invalidated exactly as by a growth (the old image is kept alive if a capture has
+        seen it; the cached workspaces are dropped).  Stream order, stale `RowFilter`s and sharded banks: as in `remove`."""
+        self._refuse_sharded("compact")
+        n = self.num_local_rows
+        if not self._num_removed:
+            return torch.arange(n, dtype=torch.int64, device=self.device)
+        self._wait_for_issued()
+        live = self.live
+        new_index = torch.where(live, torch.cumsum(live, 0) - 1, -1)
+        self._relayout(self.capacity, new_index)
+        self.num_local_rows = n - self._num_removed
+        self._num_removed = 0
+        if self.row_origin is not None:
+            self.row_origin = self.row_origin[live.to(self.row_origin.device)]
+        if self.group_labels is not None:
+            counts = self._counts()
+            keep = counts > 0
+            if self.group_labels.numel():
+                table = (torch.cumsum(keep, 0) - 1).to(torch.int32)
+                stored = self._row_codes
+                stored.copy_(torch.where(stored >= 0, table[stored.clamp(min=0).long()], stored))
+            self.group_labels = self.group_labels[keep]
+            self._group_counts = counts = counts[keep]
+            self._max_group_rows = int(counts.max()) if counts.numel() else 0
+        self._changed()
+        return new_index
+
     def _merge_labels(self, new: Tensor) -> Tensor:
         """The int32 codes of an append's labels after merging them into `group_labels`, which stays sorted: a code is the
         label's position in it, so labels not seen before re-map the stored codes -- in place, through the old -> new
@@ -573,7 +810,9 @@ class EmbeddingBank:
 
     @property
     def bank(self) -> Tensor:
-        """The stored rows as a row-major `[N_local, D]` tensor of the bank dtype (unpacked copy, `isc_bank_unpack`)."""
+        """The stored rows as a row-major `[N_local, D]` tensor of the bank dtype (unpacked copy, `isc_bank_unpack`): all
+        `len` slots; a removed row (`remove`) keeps the bytes it had until a growth or `reserve` moves the image: only live
+        rows move, so it reads as zeros afterwards."""
         out = torch.empty((self.num_local_rows, self.dim), dtype=self.dtype, device=self.device)
         if self.num_local_rows:
             lib = _lib.load()
@@ -611,7 +850,7 @@ class EmbeddingBank:
         - `allow`: bool `[N]` over the GLOBAL rows of the bank (True = the row may be returned),
         - `rows`: global row indices,
         - `image_ids`: the images whose cells may be returned (needs `row_origin`, i.e. a bank from `from_database`);
-        `exclude=True` allows the complement instead.  A sharded bank keeps the bits of its own rows
+        `exclude=True` allows the complement instead.  Rows `remove` has taken out are never allowed.  A sharded bank keeps the bits of its own rows
         `[index_base, index_base + len(self))`; there every rank makes the filter (the first call learns the global row
         count with a collective).  A presharded bank without a process group takes an `allow` of any length that covers
         its rows.  The filter is packed on the device in one launch and belongs to this bank."""
@@ -646,7 +885,10 @@ class EmbeddingBank:
             keep = torch.isin(origin, ids.to(device=origin.device, dtype=origin.dtype)).to(dev)
         if exclude:
             keep = ~keep
-        return self._pack_filter(keep[self.index_base : self.index_base + self.num_local_rows])
+        local = keep[self.index_base : self.index_base + self.num_local_rows]
+        if self._num_removed:  # a filter never allows a removed row, and `allowed_count` counts the rows it can return
+            local = local & self.live
+        return self._pack_filter(local)
 
     def _pack_filter(self, local: Tensor) -> RowFilter:
         """`isc_row_mask_pack` of this rank's bool `[N_local]` rows (zero-padded to the capacity the image is laid out for)."""
@@ -668,8 +910,8 @@ class EmbeddingBank:
         return RowFilter(self, packed, count)
 
     def _as_filter(self, mask: "RowFilter | Tensor | None") -> RowFilter | None:
-        if mask is None:  # a bank with spare capacity searches its filled rows: the fill bitmap is the filter
-            return self._fill_filter if self.num_local_rows < self.capacity else None
+        if mask is None:  # a bank with spare capacity or removed rows searches its live rows: the fill bitmap is the filter
+            return self._fill_filter if self.num_local_rows < self.capacity or self._num_removed else None
         if isinstance(mask, RowFilter):
             if not mask.belongs_to(self):
                 raise ValueError("this RowFilter belongs to another EmbeddingBank")

@@ -158,7 +158,8 @@ int isc_bank_unpack(const void* packed, int dtype, int D, int64_t n_total, int64
  * searched through `fill_mask` (the masked searches) answers as the bank of the filled rows alone, bit for bit, so an
  * append touches only the new rows.
  *   fill_mask     uint32 [isc_row_mask_words(capacity)], 4-byte aligned: the bit of every stored row's packed position is
- *                 set with an atomic OR (zero it before the first call)
+ *                 set with an atomic OR (zero it before the first call).  A bit of 0 means "empty or removed": a slot no
+ *                 row was stored in yet, or one whose row isc_bank_remove took out
  *   codes         optional int32 [n_rows], the new rows' group codes; written to packed_codes[position], a negative code
  *                 as -2 (isc_row_groups_pack's convention)
  *   packed_codes  int32 [ceil(capacity / 256) * 256], 16-byte aligned, filled with -2 before the first call; NULL iff
@@ -176,6 +177,37 @@ int isc_bank_repack(const void* src_packed, int64_t src_capacity, void* dst_pack
                     int64_t first_row, int64_t n_rows, const int32_t* src_codes, int32_t* dst_codes,
                     uint32_t* dst_fill_mask, void* stream);
 
+/* In-place removal from such a bank: the fill bits of the ORIGINAL rows rows[0 .. n_rows) are cleared (atomic AND), one
+ * launch, no host synchronisation; the masked searches then answer as if the rows had never been stored.  Row bytes are not
+ * touched and no index shifts.  An index outside [0, n_filled) is skipped; duplicates and rows removed before are
+ * tolerated and counted once.
+ *   rows           device int64 [n_rows], 8-byte aligned
+ *   n_filled       the rows appended so far (<= capacity)
+ *   packed_codes   optional int32 [ceil(capacity / 256) * 256], 16-byte aligned: a removed row's code becomes -2
+ *   group_counts   optional device int64 [groups], 8-byte aligned (needs packed_codes): the count at the removed row's old
+ *                  code is lowered by one
+ *   removed_count  optional device int64, 8-byte aligned: the number of rows this call removed is ADDED to it */
+int isc_bank_remove(const int64_t* rows, int64_t n_rows, int64_t n_filled, int64_t capacity, uint32_t* fill_mask,
+                    int32_t* packed_codes, int64_t* group_counts, int64_t* removed_count, void* stream);
+
+/* In-place replacement: rows[r] is stored at ORIGINAL row row_index[r] of the bank laid out for `capacity` rows, exactly as
+ * isc_bank_pack / isc_bank_append store it (one kernel body), one launch that touches only those rows.  norm_bound can only
+ * rise (atomic max), so it stays an upper bound.  The indices must be distinct; one outside [0, capacity) is skipped.
+ *   row_index      device int64 [n_rows], 8-byte aligned
+ *   fill_mask      the bank's fill bitmap, read only: a row whose bit is 0 (removed, or never filled) is left as it is.
+ *                  NULL: a bank without one (isc_bank_pack's image, capacity = its rows), every index is written */
+int isc_bank_replace(const void* rows, int in_dtype, int64_t n_rows, int D, int64_t ldx, const int64_t* row_index,
+                     int64_t capacity, int normalize, float eps, void* packed, int dtype, float* norm_bound,
+                     const uint32_t* fill_mask, void* stream);
+
+/* isc_bank_repack through an index map (compaction): ORIGINAL row first_row + r of the source image moves to ORIGINAL row
+ * new_index[first_row + r] of the destination image, byte for byte, with its code and its fill bit.  A negative entry (a
+ * removed row) moves nothing, nor does one >= dst_capacity.  The entries >= 0 must be distinct.
+ *   new_index      device int64, indexed by source row (at least first_row + n_rows entries), 8-byte aligned */
+int isc_bank_repack_map(const void* src_packed, int64_t src_capacity, void* dst_packed, int64_t dst_capacity, int dtype,
+                        int D, int64_t first_row, int64_t n_rows, const int32_t* src_codes, int32_t* dst_codes,
+                        uint32_t* dst_fill_mask, const int64_t* new_index, void* stream);
+
 /* Row filter of the masked searches (isc_cosine_topk_masked, isc_cosine_topk_exhaustive_masked, isc_cosine_range_masked):
  * a bitmap in the PACKED row order of an N-row bank.  Bit p of word p / 32 allows packed position p, i.e. ORIGINAL row
  * (mul * p) mod N (isc_bank_permutation); the bank's padding to 256-row tiles is included and its bits are 0, so one
@@ -189,6 +221,10 @@ int isc_row_mask_words(int64_t N, size_t* words);
  *   allowed_count  optional device int64: the number of allowed rows is ADDED to it (zero it first, like isc_bank_pack's
  *                  norm_bound); NULL = not counted */
 int isc_row_mask_pack(const uint8_t* allow, int64_t N, uint32_t* packed_mask, int64_t* allowed_count, void* stream);
+
+/* Inverse of isc_row_mask_pack for the first n_rows <= N ORIGINAL rows of an N-row bank, in one launch:
+ *   allow          uint8 [n_rows]: 1 where the row's bit is set, else 0 */
+int isc_row_mask_unpack(const uint32_t* packed_mask, int64_t N, int64_t n_rows, uint8_t* allow, void* stream);
 
 /* Row group codes of the grouped searches (isc_cosine_topk_grouped, isc_cosine_topk_exhaustive_grouped,
  * isc_cosine_range_grouped), in one launch (no host synchronisation):
