@@ -100,6 +100,14 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
         [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p],
     ),
+    "isc_bank_gather": (
+        c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
+    ),
+    "isc_cosine_scores": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+         c_int64, c_void_p],
+    ),
     "isc_nchw_to_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "isc_conv2d_nhwc": (
         c_int,

@@ -1,0 +1,195 @@
+// Access to the stored rows of a packed bank BY ROW INDEX (include/imagescry_hip.h: isc_bank_gather, isc_cosine_scores):
+// the stored bytes of a list of rows, and the exact float64 scores of queries against a list of rows.  Both address the
+// packed image through the bank's permutation and, when given, its fill bitmap; neither needs a workspace, a status word
+// or the host, so both are capturable.
+#include "bank_layout.h"
+#include "isc_common.h"
+#include "search_common.h"
+
+namespace {
+
+// The packed position of listed row r, or -1 for a DEAD row: one outside [0, capacity), or one whose fill bit is clear
+// (empty or removed).  A dead row is never dereferenced.
+__device__ __forceinline__ int64_t live_pos(int64_t r, const IscPerm& pm, const uint32_t* __restrict__ fill_mask) {
+    if (r < 0 || r >= pm.n) return -1;
+    const int64_t p = isc_perm_pos(pm, r);
+    if (fill_mask && !((fill_mask[p >> 5] >> (p & 31)) & 1u)) return -1;
+    return p;
+}
+
+// isc_bank_gather: one wave per listed row, a lane per 16-byte chunk of the row (8 lanes per 128-byte K-step segment, as
+// k_bank_repack reads them).  E is an unsigned integer of the element's size: the bytes move untouched.  A chunk that lies
+// inside the row goes out as one 16-byte store when the output rows are 16-byte aligned (`vec_ok`); the ragged last chunk,
+// and every chunk of an unaligned output, element by element.  A dead row is written as zeros.
+template <typename E>
+__global__ __launch_bounds__(256) void k_bank_gather(const unsigned char* __restrict__ packed, int d, int ks, IscPerm pm,
+                                                     const int64_t* __restrict__ rows, int64_t m,
+                                                     const uint32_t* __restrict__ fill_mask, E* __restrict__ out,
+                                                     int64_t ldo, int vec_ok) {
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= m) return;
+    const int lane = threadIdx.x & 63;
+    const int64_t p = live_pos(rows[i], pm, fill_mask);
+    constexpr int PER = 16 / (int)sizeof(E);
+    E* dst = out + i * ldo;
+    const int chunks = (d + PER - 1) / PER;  // <= 8 * ks
+    for (int c = lane; c < chunks; c += 64) {
+        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+        if (p >= 0) raw = *reinterpret_cast<const uint4*>(packed + isc_packed_offset(p, c >> 3, ks) + (c & 7) * 16);
+        const int e0 = c * PER;
+        if (vec_ok && e0 + PER <= d) {
+            *reinterpret_cast<uint4*>(dst + e0) = raw;
+        } else {
+            const E* v = reinterpret_cast<const E*>(&raw);
+#pragma unroll
+            for (int j = 0; j < PER; ++j)
+                if (e0 + j < d) dst[e0 + j] = v[j];
+        }
+    }
+}
+
+// isc_cosine_scores: k_exact's score of every (query, listed row) pair, without the search around it.
+//
+// A workgroup owns SC_ROWS = 64 listed rows and a group of SC_GQ = 8 queries.  As in k_exact a wave takes 8 rows (lane l:
+// row l >> 3, 16-byte chunk l & 7 of every K step), the queries sit in LDS as float64 rounded to the bank type first, and
+// every product and sum is float64: per (query, row) the lane's fma chain runs over the K steps in order and over the
+// chunk's elements in order, the 8 lanes are summed by group8_sum, the sum is divided by max(||q||, 1e-12) -- the norm
+// summed per lane over elements lane, lane + 64, ... and then over the wave, as k_exact sums it -- and cast to float32.
+// Same operations in the same order: the bits are those isc_cosine_topk_exhaustive returns for the pair.
+//
+// The queries are staged SC_KC K steps at a time (zero-padded to the K-step width): the LDS image is 8 x 8 K steps of
+// float64 = 32 KiB (fp16) or 16 KiB (fp32) whatever D, so the query-group size does not depend on D and LDS never limits
+// the four 512-thread workgroups a CU can hold; the accumulators of the wave's 8 rows x 8 queries stay in registers across
+// the stages.  The grid is (row blocks) x (query groups), the query group running fastest: the workgroups that share a
+// row block are neighbours and re-read it from the cache.
+constexpr int SC_THREADS = 512;
+constexpr int SC_WAVES = SC_THREADS / 64;
+constexpr int SC_ROWS = SC_WAVES * 8;
+constexpr int SC_GQ = 8;
+constexpr int SC_KC = 8;
+static_assert(SC_GQ == 8, "lane l & 7 of a row's 8 lanes writes query l & 7 of the group");
+static_assert(SC_GQ <= SC_WAVES, "wave g sums the norm of query g");
+
+template <typename T>
+__global__ __launch_bounds__(SC_THREADS) void k_row_scores(const unsigned char* __restrict__ bank, int ks, IscPerm pm,
+                                                           const void* __restrict__ queries, int q_f32, int64_t ldq, int d,
+                                                           int nq, int qgroups, const int64_t* __restrict__ rows, int64_t m,
+                                                           const uint32_t* __restrict__ fill_mask,
+                                                           float* __restrict__ scores, int64_t lds) {
+    constexpr int EPK = ISC_KSTEP_BYTES / (int)sizeof(T);  // elements per K step
+    constexpr int PER = Chunk16<T>::N;
+    constexpr int CE = SC_KC * EPK;  // elements per stage
+    __shared__ __attribute__((aligned(16))) double qd[SC_GQ * CE];
+    __shared__ double denom_sh[SC_GQ];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int sub = lane >> 3, ch = lane & 7;
+    const int q0 = (int)(blockIdx.x % (unsigned)qgroups) * SC_GQ;
+    const int gn = min(SC_GQ, nq - q0);
+    const int64_t j = (int64_t)(blockIdx.x / (unsigned)qgroups) * SC_ROWS + wave * 8 + sub;
+    const int64_t p = j < m ? live_pos(rows[j], pm, fill_mask) : -1;
+    const unsigned char* src = bank + (p >= 0 ? isc_packed_offset(p, 0, ks) : 0) + ch * 16;
+
+    double acc[SC_GQ];
+#pragma unroll
+    for (int g = 0; g < SC_GQ; ++g) acc[g] = 0.0;
+    double nacc = 0.0;  // wave g: this lane's part of the squared norm of query g
+    for (int s0 = 0; s0 < ks; s0 += SC_KC) {
+        const int sn = min(SC_KC, ks - s0);
+        const int e0 = s0 * EPK, en = sn * EPK;
+        if (s0 > 0) __syncthreads();  // the previous stage has been read
+        for (int g = 0; g < SC_GQ; ++g) {
+            // the caller's query elements (fp16 or float32, `q_f32`) rounded to the bank type first, as k_exact reads them
+            const float* qp32 = static_cast<const float*>(queries) + (int64_t)(q0 + g) * ldq;
+            const _Float16* qp16 = static_cast<const _Float16*>(queries) + (int64_t)(q0 + g) * ldq;
+            for (int e = tid; e < en; e += SC_THREADS) {
+                double v = 0.0;
+                if (g < gn && e0 + e < d) v = (double)(float)(T)(q_f32 ? qp32[e0 + e] : (float)qp16[e0 + e]);
+                qd[g * CE + e] = v;
+            }
+        }
+        __syncthreads();
+        if (wave < SC_GQ)  // (e0 is a multiple of 64: the lane's elements are lane, lane + 64, ... of the whole query)
+            for (int e = lane; e < en; e += 64) nacc = fma(qd[wave * CE + e], qd[wave * CE + e], nacc);
+        for (int s = 0; s < sn; ++s) {
+            double a[8];
+            if (p >= 0) {
+                Chunk16<T>::load(src + (size_t)(s0 + s) * ISC_TILE_KSTEP_BYTES, a);
+            } else {
+#pragma unroll
+                for (int e = 0; e < PER; ++e) a[e] = 0.0;
+            }
+            const double* qs = qd + s * EPK + ch * PER;
+#pragma unroll
+            for (int e = 0; e < PER; ++e)
+#pragma unroll
+                for (int g = 0; g < SC_GQ; ++g) acc[g] = fma(qs[g * CE + e], a[e], acc[g]);
+        }
+    }
+    if (wave < SC_GQ) {
+        nacc = isc_wave_sum(nacc);
+        if (lane == 0) denom_sh[wave] = fmax(sqrt(nacc), 1e-12);
+    }
+    __syncthreads();
+    // after group8_sum every one of the row's 8 lanes holds the row's sums: lane `ch` keeps, and writes, query `ch`
+    float mine = 0.f;
+#pragma unroll
+    for (int g = 0; g < SC_GQ; ++g) {
+        const float sc = (float)(group8_sum(acc[g]) / denom_sh[g]);
+        if (ch == g) mine = sc;
+    }
+    if (j < m && ch < gn) scores[(int64_t)(q0 + ch) * lds + j] = p >= 0 ? mine : -INFINITY;
+}
+
+bool rows_dtype_ok(int dtype) { return dtype == ISC_F16 || dtype == ISC_F32; }
+
+}  // namespace
+
+extern "C" int isc_bank_gather(const void* packed, int dtype, int D, int64_t capacity, const int64_t* rows, int64_t m,
+                               const uint32_t* fill_mask, void* out, int64_t ldo, void* stream) {
+    ISC_REQUIRE(rows_dtype_ok(dtype) && D > 0 && m >= 0 && ldo >= D);
+    ISC_REQUIRE(capacity > 0 && capacity <= 0x7ffffffe);
+    if (m == 0) return ISC_OK;
+    ISC_REQUIRE(packed && rows && out);
+    const int esz = dtype == ISC_F16 ? 2 : 4;
+    if (!isc_aligned(packed, 16) || !isc_aligned(rows, 8) || !isc_aligned(fill_mask, 4) || !isc_aligned(out, esz))
+        return ISC_ERR_ALIGNMENT;
+    const int64_t blocks = isc_ceil_div<int64_t>(m, 4);
+    if (blocks > 0x7fffffff) return ISC_ERR_UNSUPPORTED;
+    const int vec_ok = isc_aligned(out, 16) && (ldo * esz) % 16 == 0 ? 1 : 0;
+    const unsigned char* in = static_cast<const unsigned char*>(packed);
+    const IscPerm pm = isc_make_perm(capacity);
+    if (dtype == ISC_F16)
+        hipLaunchKernelGGL(k_bank_gather<uint16_t>, dim3((unsigned)blocks), dim3(256), 0, isc_stream(stream), in, D,
+                           isc_ksteps(D, 2), pm, rows, m, fill_mask, static_cast<uint16_t*>(out), ldo, vec_ok);
+    else
+        hipLaunchKernelGGL(k_bank_gather<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, isc_stream(stream), in, D,
+                           isc_ksteps(D, 4), pm, rows, m, fill_mask, static_cast<uint32_t*>(out), ldo, vec_ok);
+    return isc_launch_status();
+}
+
+extern "C" int isc_cosine_scores(const void* bank, int dtype, int64_t capacity, int D, const void* queries, int q_dtype,
+                                 int Q, int64_t ldq, const int64_t* rows, int64_t M, const uint32_t* fill_mask,
+                                 float* scores, int64_t lds, void* stream) {
+    ISC_REQUIRE(rows_dtype_ok(dtype) && rows_dtype_ok(q_dtype) && D > 0 && Q >= 0 && M >= 0 && ldq >= D && lds >= M);
+    ISC_REQUIRE(capacity > 0 && capacity <= 0x7ffffffe);
+    if (D > ISC_SEARCH_MAX_D || Q > ISC_SEARCH_MAX_Q) return ISC_ERR_UNSUPPORTED;
+    if (Q == 0 || M == 0) return ISC_OK;
+    ISC_REQUIRE(bank && queries && rows && scores);
+    if (!isc_aligned(bank, 16) || !isc_aligned(queries, q_dtype == ISC_F16 ? 2 : 4) || !isc_aligned(rows, 8) ||
+        !isc_aligned(fill_mask, 4) || !isc_aligned(scores, 4))
+        return ISC_ERR_ALIGNMENT;
+    const int qgroups = isc_ceil_div(Q, SC_GQ);
+    const int64_t blocks = isc_ceil_div<int64_t>(M, SC_ROWS) * qgroups;
+    if (blocks > 0x7fffffff) return ISC_ERR_UNSUPPORTED;
+    const unsigned char* in = static_cast<const unsigned char*>(bank);
+    const IscPerm pm = isc_make_perm(capacity);
+    const int qf = q_dtype == ISC_F32 ? 1 : 0;
+    if (dtype == ISC_F16)
+        hipLaunchKernelGGL(k_row_scores<_Float16>, dim3((unsigned)blocks), dim3(SC_THREADS), 0, isc_stream(stream), in,
+                           isc_ksteps(D, 2), pm, queries, qf, ldq, D, Q, qgroups, rows, M, fill_mask, scores, lds);
+    else
+        hipLaunchKernelGGL(k_row_scores<float>, dim3((unsigned)blocks), dim3(SC_THREADS), 0, isc_stream(stream), in,
+                           isc_ksteps(D, 4), pm, queries, qf, ldq, D, Q, qgroups, rows, M, fill_mask, scores, lds);
+    return isc_launch_status();
+}

@@ -151,6 +151,15 @@ struct Chunk16<float> {
     }
 };
 
+// sum over the 8 lanes that share a bank row (k_exact, k_exact_collapse, k_row_scores: lane l holds the 16-byte chunk l & 7
+// of every K step of row l >> 3), left in all 8
+__device__ __forceinline__ double group8_sum(double v) {
+    v += __shfl_xor(v, 1, 64);
+    v += __shfl_xor(v, 2, 64);
+    v += __shfl_xor(v, 4, 64);
+    return v;
+}
+
 // float64 norm of the packed query row at `qrow_base` (K step s at + s * tnq * 128 B); called by ONE wave, result in
 // every lane
 template <typename T>

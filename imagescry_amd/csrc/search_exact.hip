@@ -50,13 +50,6 @@ struct Chunk<float> {
     }
 };
 
-__device__ __forceinline__ double group8_sum(double v) {  // over the 8 lanes that share a bank row
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    return v;
-}
-
 // grid = chunks of consecutive bank tiles, 512 threads.  GQ listed queries are scored per sweep of the chunk: the
 // queries sit in LDS as float64, a wave takes 8 bank rows at a time (lane = row l >> 3, 16-byte chunk l & 7 of every K
 // step: each load instruction reads 1 KiB of contiguous HBM), every product and sum is float64.  Each wave keeps a

@@ -499,6 +499,36 @@ class EmbeddingBank:
         pos = torch.isin(self._row_codes, codes).nonzero().squeeze(1)
         return (pos * mul.value) % self.capacity
 
+    def _stored_codes(self, index: Tensor) -> Tensor:
+        """The stored int32 group codes of the local rows `index` (int64 `[m]`, device), read from the packed codes at the
+        rows' packed positions `(mul_inv * row) mod capacity`: tensor ops, no label lookup, no host read.  A device hook."""
+        mul, inv = _lib.c_int64(), _lib.c_int64()
+        _lib.check(_lib.load().isc_bank_permutation(self.capacity, mul, inv), "isc_bank_permutation")
+        return self._row_codes[(index * inv.value) % self.capacity]
+
+    def _gather_rows(self, index: Tensor, out: Tensor) -> None:
+        """`isc_bank_gather`: `out[i]` (`[m, D]` of the bank dtype, unit inner stride) receives the stored bytes of local
+        row `index[i]` (int64 `[m]`, device, m > 0), zeros for a removed row; one launch on the current stream, no host
+        read.  A device hook."""
+        with torch.cuda.device(self.device):
+            st = _lib.load().isc_bank_gather(
+                self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.dim, self.capacity, index.data_ptr(),
+                index.numel(), _lib.ptr(self._fill), out.data_ptr(), out.stride(0), _lib.stream_handle(self.device),
+            )
+        _lib.check(st, "isc_bank_gather")
+
+    def _score_rows(self, q: Tensor, index: Tensor, out: Tensor) -> None:
+        """`isc_cosine_scores`: `out[i, j]` (float32 `[Q, M]`, unit inner stride) receives the score of query `q[i]`
+        (prepared, Q > 0) against local row `index[j]` (int64 `[M]`, device, M > 0), -inf for a removed row; one launch on
+        the current stream, no host read.  A device hook."""
+        with torch.cuda.device(self.device):
+            st = _lib.load().isc_cosine_scores(
+                self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.capacity, self.dim, q.data_ptr(),
+                _lib.dtype_code(q.dtype), q.shape[0], q.stride(0), index.data_ptr(), index.numel(), _lib.ptr(self._fill),
+                out.data_ptr(), out.stride(0), _lib.stream_handle(self.device),
+            )
+        _lib.check(st, "isc_cosine_scores")
+
     def _wait_for_issued(self) -> None:
         """Order the caller's current stream behind everything this bank has issued elsewhere: both lane streams of
         `search_async` and the exchange stream.  An unresolved asynchronous search then never reads a half-updated image."""
@@ -612,10 +642,12 @@ class EmbeddingBank:
         return range(self.index_base + first, self.index_base + first + m)
 
     # ------------------------------------------------------------------ remove, replace, compact
-    def _refuse_sharded(self, what: str) -> None:
+    def _refuse_sharded(self, what: str, why: str = "its global indices are contiguous per rank and would shift") -> None:
         if self.process_group is not None:
-            raise ValueError(f"a sharded bank (process_group=) cannot {what}: its global indices are contiguous per rank "
-                             "and would shift")
+            raise ValueError(f"a sharded bank (process_group=) cannot {what}: {why}")
+
+    # why the stored-row calls (`rows`, `scores`, `similarity_map`, `search_rows`) refuse a sharded bank
+    _ROWS_ON_ONE_RANK = "a row is stored on one rank only, and every other rank would need it broadcast by its owner"
 
     def _local_index(self, index: object, name: str) -> Tensor:
         """Global row indices (an integer tensor or a sequence of ints) as a contiguous int64 `[m]` tensor of LOCAL rows
@@ -812,7 +844,7 @@ class EmbeddingBank:
     def bank(self) -> Tensor:
         """The stored rows as a row-major `[N_local, D]` tensor of the bank dtype (unpacked copy, `isc_bank_unpack`): all
         `len` slots; a removed row (`remove`) keeps the bytes it had until a growth or `reserve` moves the image: only live
-        rows move, so it reads as zeros afterwards."""
+        rows move, so it reads as zeros afterwards.  `rows(indices)` reads chosen rows without unpacking the rest."""
         out = torch.empty((self.num_local_rows, self.dim), dtype=self.dtype, device=self.device)
         if self.num_local_rows:
             lib = _lib.load()
@@ -1223,12 +1255,14 @@ class EmbeddingBank:
     _LANE_MAX_QUERIES = 128
 
     def _search(self, queries: Tensor, k: int, lanes: bool, mask: "RowFilter | Tensor | None" = None,
-                exclude_group: Tensor | None = None) -> SearchHandle:
+                exclude_group: Tensor | None = None, query_codes: Tensor | None = None) -> SearchHandle:
+        """`query_codes`: the int32 `[Q]` codes of the queries' groups themselves, in place of `exclude_group` labels
+        (`search_rows` reads them from the stored codes)."""
         rf = self._as_filter(mask)
         self._check_k(k)
         q = self._prepare_queries(queries)
         nq = q.shape[0]
-        filt = self._filter_kwargs(rf, self._query_codes(exclude_group, nq))
+        filt = self._filter_kwargs(rf, self._query_codes(exclude_group, nq) if query_codes is None else query_codes)
         # sharded: the first search learns the bank's size with a collective of every rank
         n_rows = self.num_local_rows if self.process_group is None else self._global_rows()
         if k > n_rows:
@@ -1321,6 +1355,98 @@ class EmbeddingBank:
         gathered = torch.empty(self.world_size * src.numel(), dtype=torch.uint8, device=src.device)
         dist.all_gather_into_tensor(gathered, src, group=self.process_group)
         return gathered.to(xbuf.device).view(self.world_size, src.numel())
+
+    # ------------------------------------------------------------------ stored rows
+    def rows(self, indices: "Tensor | Sequence[int]") -> Tensor:
+        """The stored vectors of the rows `indices` (global, any order, duplicates allowed): `[m, D]` of the bank dtype,
+        ONE launch that reads only those rows (`isc_bank_gather`) -- `bank.bank[indices]` bit for bit without unpacking the
+        bank.  A removed row reads as zeros.  An index outside the bank raises ValueError.  Runs on the caller's current
+        stream.  A sharded bank (`process_group=`) cannot read rows back."""
+        self._refuse_sharded("read rows back", self._ROWS_ON_ONE_RANK)
+        index = self._local_index(indices, "indices")
+        out = torch.empty((index.numel(), self.dim), dtype=self.dtype, device=self.device)
+        if index.numel():
+            self._gather_rows(index, out)
+        return out
+
+    def scores(self, queries: Tensor, rows: "Tensor | Sequence[int]") -> Tensor:
+        """The scores of `queries` (floating `[Q, D]`, as in `search`) against the rows `rows` (global, any order,
+        duplicates allowed): float32 `[Q, M]`, ONE launch that reads only those rows (`isc_cosine_scores`).  Entry
+        `[q, j]` has the bits `search_exhaustive` returns for that query and row -- re-rank a candidate list from elsewhere,
+        or check a `search` result by hand.  The column of a removed row is -inf.  `Q == 0` or `M == 0` gives an empty
+        tensor without a launch.  No host synchronisation past the index check.  A sharded bank cannot score rows."""
+        self._refuse_sharded("score rows", self._ROWS_ON_ONE_RANK)
+        q = self._prepare_queries(queries)
+        index = self._local_index(rows, "rows")
+        out = torch.empty((q.shape[0], index.numel()), dtype=torch.float32, device=self.device)
+        if out.numel():
+            self._score_rows(q, index, out)
+        return out
+
+    def similarity_map(self, queries: Tensor, image_id: int) -> Tensor:
+        """The score of every query against every cell of one image, on a bank with `row_origin` (`from_database`):
+        float32 `[Q, H, W]` with H = the image's largest h + 1 and W = its largest w + 1; cells the bank does not hold, or
+        has removed, are -inf.  An image no row of the bank belongs to raises ValueError.  Host indexing on `scores`."""
+        self._refuse_sharded("map an image", self._ROWS_ON_ONE_RANK)
+        if self.row_origin is None:
+            raise ValueError("similarity_map needs row_origin: build the bank with EmbeddingBank.from_database")
+        if self.row_origin.shape[0] != self.num_local_rows:
+            raise ValueError("row_origin does not describe the bank's rows")
+        q = self._prepare_queries(queries)
+        origin = self.row_origin
+        cells = (origin[:, 0] == int(image_id)).nonzero().squeeze(1)
+        if cells.numel() == 0:
+            raise ValueError(f"image_id {int(image_id)} is not in the bank")
+        h, w = origin[cells, 1].to(self.device), origin[cells, 2].to(self.device)
+        out = torch.full((q.shape[0], int(h.max()) + 1, int(w.max()) + 1), -math.inf, dtype=torch.float32,
+                         device=self.device)
+        out[:, h, w] = self.scores(q, cells + self.index_base)
+        return out
+
+    def search_rows(self, indices: "Tensor | Sequence[int]", k: int = 10, *, exclude_self: bool = True,
+                    mask: "RowFilter | Tensor | None" = None,
+                    exclude_group: "Tensor | str | None" = None) -> tuple[Tensor, Tensor]:
+        """`search` with the stored vectors of the rows `indices` (global) as the queries -- "more cells like this stored
+        cell".  The queries are gathered in the bank dtype (`isc_bank_gather`), so rounding them to the bank dtype is the
+        identity and the answer is `search(rows(indices), k, ...)` bit for bit.  `mask`, `exclude_group`: as in `search`;
+        in addition `exclude_group="own"` makes every query skip its own row's group ("in other images"): the query codes
+        are the rows' stored codes, read on the device, so the bank must have row groups.
+
+        `exclude_self=True` (default) keeps a query's own row out of its answer.  With `"own"` the group exclusion already
+        does.  Otherwise `k + 1` entries are searched and, per query, the entry whose index is the query's own row is
+        dropped, or the last entry when the own row is not among them (the mask or the group exclusion disallows it, or
+        `k + 1` exact copies with lower indices precede it); the order is total, so what remains is exactly the top-k of
+        the rows other than the query's own.  Then `1 <= k <= min(ISC_TOPK_MAX_K - 1, len - 1)`.
+
+        A removed row among `indices` raises ValueError (one host read, only while `num_removed > 0`).  Everything else is
+        enqueued on the caller's current stream.  A sharded bank cannot search by row."""
+        self._refuse_sharded("search by row", self._ROWS_ON_ONE_RANK)
+        index = self._local_index(indices, "indices")
+        self._check_k(k)
+        own = isinstance(exclude_group, str)
+        if own and exclude_group != "own":
+            raise ValueError(f"exclude_group must be a label tensor or 'own', got {exclude_group!r}")
+        if own and self.group_labels is None:
+            raise ValueError("exclude_group='own' needs row groups: build the bank with row_groups= (or from_database)")
+        drop = bool(exclude_self) and not own
+        if drop and k > min(_lib.ISC_TOPK_MAX_K, self.num_local_rows) - 1:
+            raise ValueError(f"k={k} must be in [1, {min(_lib.ISC_TOPK_MAX_K, self.num_local_rows) - 1}] with "
+                             "exclude_self=True: each query's own row is searched too and then dropped")
+        if self._num_removed and index.numel() and not bool(self.live[index].all()):
+            raise ValueError("indices name a removed row: it has no stored vector to search with")
+        q = torch.empty((index.numel(), self.dim), dtype=self.dtype, device=self.device)
+        if index.numel():
+            self._gather_rows(index, q)
+        codes = self._stored_codes(index) if own else None
+        scores, found = self._search(q, k + 1 if drop else k, lanes=False, mask=mask,
+                                     exclude_group=None if own else exclude_group, query_codes=codes).result()
+        if not drop:
+            return scores, found
+        hit = found == (index + self.index_base)[:, None]  # at most one entry per query: a result names a row once
+        at = torch.where(hit.any(dim=1), hit.to(torch.uint8).argmax(dim=1), k)  # the own row's position, or the last
+        cols = torch.arange(k, device=found.device)[None, :]
+        cols = cols + (cols >= at[:, None])
+        return scores.gather(1, cols), found.gather(1, cols)
 
     # ------------------------------------------------------------------ collapsed search
     def _labels_of(self, codes: Tensor) -> Tensor:

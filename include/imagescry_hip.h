@@ -208,6 +208,18 @@ int isc_bank_repack_map(const void* src_packed, int64_t src_capacity, void* dst_
                         int D, int64_t first_row, int64_t n_rows, const int32_t* src_codes, int32_t* dst_codes,
                         uint32_t* dst_fill_mask, const int64_t* new_index, void* stream);
 
+/* Read stored rows back by index, one launch, no host synchronisation (capturable): out[i, :D] receives the stored bytes of
+ * ORIGINAL row rows[i] of the image laid out for `capacity` rows (isc_bank_permutation(capacity), as isc_bank_unpack and
+ * isc_bank_replace address it), in the bank dtype, bit for bit.  The list may be in any order and name a row twice.  A DEAD
+ * row -- an index < 0 or >= capacity, or, with `fill_mask`, a row whose fill bit is 0 (empty or removed) -- is never
+ * dereferenced and reads as zeros.  Columns D .. ldo-1 of `out` are not written.  m == 0 returns ISC_OK without a launch.
+ *   rows           device int64 [m], 8-byte aligned
+ *   fill_mask      the bank's fill bitmap (isc_bank_append), or NULL: every row of [0, capacity) is stored
+ *   out            row-major [m, D] of `dtype`, leading dimension ldo >= D (elements); 16-byte stores are used when `out`
+ *                  is 16-byte aligned and ldo a multiple of 16 bytes, element stores otherwise */
+int isc_bank_gather(const void* packed, int dtype, int D, int64_t capacity, const int64_t* rows, int64_t m,
+                    const uint32_t* fill_mask, void* out, int64_t ldo, void* stream);
+
 /* Row filter of the masked searches (isc_cosine_topk_masked, isc_cosine_topk_exhaustive_masked, isc_cosine_range_masked):
  * a bitmap in the PACKED row order of an N-row bank.  Bit p of word p / 32 allows packed position p, i.e. ORIGINAL row
  * (mul * p) mod N (isc_bank_permutation); the bank's padding to 256-row tiles is included and its bits are 0, so one
@@ -515,6 +527,20 @@ int isc_cosine_topk_exhaustive_grouped(const void* bank, int dtype, int64_t N, i
                                        int64_t* out_indices, void* workspace, size_t workspace_bytes,
                                        const uint32_t* row_mask, const int32_t* row_group, const int32_t* query_group,
                                        void* stream);
+
+/* The scores of chosen rows: scores[q, j] = the score of query q against ORIGINAL row rows[j] of the image laid out for
+ * `capacity` rows, float32(dot_f64(q, b) / max(||q||_2, 1e-12)) with the query rounded to the bank dtype first -- computed
+ * with isc_cosine_topk_exhaustive's operations in its order, so the bits are the ones that call returns for the pair.  The
+ * list may be in any order and name a row twice; a DEAD row (isc_bank_gather) is never dereferenced and scores -inf.  NaN
+ * or inf in the inputs give what the arithmetic gives.  One launch for any Q, no workspace, no status word, no host
+ * synchronisation (capturable).  Q == 0 or M == 0 returns ISC_OK without a launch.  D <= ISC_SEARCH_MAX_D.
+ *   bank, dtype, D, queries, q_dtype, Q, ldq   as isc_cosine_topk
+ *   rows           device int64 [M], 8-byte aligned
+ *   fill_mask      the bank's fill bitmap (isc_bank_append), or NULL: every row of [0, capacity) is stored
+ *   scores         float [Q, M], leading dimension lds >= M */
+int isc_cosine_scores(const void* bank, int dtype, int64_t capacity, int D, const void* queries, int q_dtype, int Q,
+                      int64_t ldq, const int64_t* rows, int64_t M, const uint32_t* fill_mask, float* scores, int64_t lds,
+                      void* stream);
 
 /* Exact cosine range search: for every query, EVERY row with score(q, b) >= min_score[q], with the score of
  * isc_cosine_topk (the query rounded to the bank dtype first; float32(dot_f64(q, b) / max(||q||_2, 1e-12))).  NaN scores
