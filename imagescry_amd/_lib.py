@@ -177,6 +177,10 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "isc_bank_shadow_bytes": (c_int, [c_int64, c_int, POINTER(c_size_t)]),
     "isc_bank_quantize": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p]),
     "isc_cosine_topk_uses_shadow": (c_int, [c_int, c_int64, c_int, c_int, c_int, POINTER(c_int)]),
+    "isc_cosine_topk_plan": (
+        c_int,
+        [c_int, c_int64, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int64), POINTER(c_int)],
+    ),
     "isc_cosine_topk_shadow": (
         c_int,
         [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p,

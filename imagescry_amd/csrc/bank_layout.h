@@ -24,7 +24,7 @@ __device__ __forceinline__ T isc_packed_load(const void* bank, int64_t row, int 
     return *reinterpret_cast<const T*>(p);
 }
 
-// ---- int8 shadow of an fp16 bank (isc_bank_quantize; the last filter level of large query batches streams it) -----
+// ---- int8 shadow of an fp16 bank (isc_bank_quantize; the filter levels after the sample of large query batches stream it) -----
 // The same scheme with 128 int8 per K step: [tile of 256 rows][K step of 128 dims][row][128 B], element e of a row at
 // byte e % 128 of K step e / 128, rows in the fp16 bank's order, padding rows and columns zero.  One fp32 record per tile
 // follows the data (256-byte aligned):

@@ -48,6 +48,7 @@
 //              half times the 64-query search), the 256-query tile runs half empty; this one streams the bank once with
 //              the matrix pipe ~45 % busy.
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <type_traits>
@@ -87,6 +88,7 @@ struct Level {
     int64_t r0, r1;
     int ntiles, tiles_per_chunk, nchunks;
     int sample;  // level 0
+    int kind;    // 0 = the sample, 1 = a float filter level, 2 = an int8 filter level on the shadow bank (make_plan)
 };
 
 struct Plan {
@@ -137,6 +139,22 @@ int sample_tiles_cap() {
 constexpr int first_ratio() { return 16; }
 constexpr int sample_tiles_cap() { return 0; }
 #endif
+#ifdef ISC_ABLATION
+bool i8_first_piece_i8() {
+    static const bool v = getenv("ISC_I8_FIRST_I8") != nullptr;  // A/B aid: the int8 plan's piece next to the sample in int8 too
+    return v;
+}
+#else
+constexpr bool i8_first_piece_i8() { return false; }
+#endif
+#ifdef ISC_ABLATION
+bool i8_last_level_only() {
+    static const bool v = getenv("ISC_I8_LAST_ONLY") != nullptr;  // A/B aid: the float plan with its last level on the shadow
+    return v;
+}
+#else
+constexpr bool i8_last_level_only() { return false; }
+#endif
 
 // Collapsed search (isc_cosine_topk_collapse, group_rows = the most rows one group has, >= 1): the slot maxima of the sample
 // level bound a workgroup's kp-th best ROW, which says nothing about its kp-th best GROUP, so the sample level keeps every
@@ -147,7 +165,22 @@ constexpr int COLLAPSE_MIN_KP = 32;
 constexpr int COLLAPSE_ROWS_CAP = 64;
 constexpr int COLLAPSE_GROUPS = 4096;  // distinct groups a selection can hold (GroupHash)
 
-Plan make_plan(int64_t n, int q, int k, int group_rows = 0) {
+// The int8 levels ("The int8 level").  The loosened int8 test multiplies a level's survivors by a
+// data-dependent factor (about 8 on unit rows of 768 iid dimensions); a level runs on the shadow only if I8_INFLATION times
+// the float filter's expected survivors, kp (rows of the level / rows before it), fit the budget of the level's lists.  A
+// bank that inflates more overflows a list: the query is flagged and redone by the fp16 filter, as after any overflow.
+constexpr int I8_INFLATION = 16;
+
+// i8: the search may run on the bank's int8 shadow (run(): an fp16 bank, no mask / group / collapse, a shadow given, and
+// Dpad 127^2 < 2^24).  Without it -- and for every shape but the 256-query tile with several query tiles -- the plan is the
+// float one above.  With it every level after the sample is an int8 level of at most R8 - 1 times the rows before it,
+// R8 = 1 + budget / (kp I8_INFLATION), laid out BACKWARDS from the end of the bank (b0 = n, b(j+1) = b(j) / R8 rounded up
+// to a tile) so that the long late levels get the full ratio and the piece next to the sample takes what is left; that
+// piece runs in fp16 when other levels follow it (see below).  Every
+// level must hold its survivors in the segments of its REAL number of chunks (a piece shorter than one tile per
+// workgroup has fewer).  A shape whose layout does not fit (MAX_LEVELS, a level that fails the inequality) keeps the float
+// plan, with its last level on the shadow where that level alone satisfies the inequality (the rule before the int8 plan).
+Plan make_plan(int64_t n, int q, int k, int group_rows = 0, bool i8 = false) {
     Plan p;
     p.qb = q < QBATCH ? q : QBATCH;
     p.tnq = p.qb <= 64 ? 64 : p.qb <= SMALL_Q ? 128 : 256;
@@ -170,6 +203,7 @@ Plan make_plan(int64_t n, int q, int k, int group_rows = 0) {
         l.r0 = r0;
         l.r1 = r1;
         l.sample = sample;
+        l.kind = sample ? 0 : 1;
         l.ntiles = (int)isc_ceil_div<int64_t>(r1 - r0, TM);
         int want = sample ? l.ntiles : wgs;
         if (want > l.ntiles) want = l.ntiles;
@@ -184,6 +218,7 @@ Plan make_plan(int64_t n, int q, int k, int group_rows = 0) {
     if (stiles > ntiles_all) stiles = ntiles_all;
     int64_t seen = stiles * TM < n ? stiles * TM : n;
     add(0, seen, 1);
+    const int64_t seen0 = seen;
     while (seen < n) {
         const int64_t nseg = (int64_t)p.segs_per_chunk * wgs;
         // The level's survivors per query are ~ (ratio - 1) x G with G ~ Gamma(kp): the threshold is the kp-th best of what
@@ -211,6 +246,63 @@ Plan make_plan(int64_t n, int q, int k, int group_rows = 0) {
         add(seen, r1, 0);
         seen = r1;
     }
+    if (i8 && group_rows == 0 && p.tnq == 256 && p.qtiles > 1 && p.nlevels > 1) {
+        const Plan flt = p;
+        const int64_t list_budget = (int64_t)((double)QCAP * p.kp / (p.kp + 8.0 * sqrt((double)p.kp)));
+        auto level_budget = [&](int nchunks) {
+            const int64_t slots = (int64_t)p.segs_per_chunk * nchunks * CAP / 8;
+            return slots < list_budget ? slots : list_budget;
+        };
+        // chunks of a filter level of [r0, r1), as add() cuts it
+        auto chunks_of = [&](int64_t r0, int64_t r1) {
+            const int ntiles = (int)isc_ceil_div<int64_t>(r1 - r0, TM);
+            const int per = isc_ceil_div(ntiles, wgs < ntiles ? wgs : ntiles);
+            return isc_ceil_div(ntiles, per);
+        };
+        auto fits_i8 = [&](int64_t r0, int64_t r1) {
+            return (double)p.kp * (double)(r1 - r0) / (double)r0 * I8_INFLATION <= (double)level_budget(chunks_of(r0, r1));
+        };
+        const int64_t r8 = 1 + level_budget(wgs) / ((int64_t)p.kp * I8_INFLATION);
+        int64_t ends[MAX_LEVELS];
+        int m = 0;
+        bool ok = r8 >= 2 && !i8_last_level_only();
+        for (int64_t b = n; ok && b > seen0;) {
+            if (m == MAX_LEVELS - 1) {
+                ok = false;
+                break;
+            }
+            ends[m++] = b;
+            // the level's start: b / R8, moved up while the chunks the level really has (the tiles do not always divide
+            // into `wgs` chunks) hold fewer survivors than the full budget
+            int64_t nb = isc_ceil_div<int64_t>(isc_ceil_div<int64_t>(b, r8), TM) * TM;
+            for (int it = 0; it < 64 && nb < b && nb > seen0 && !fits_i8(nb, b); ++it) {
+                const int64_t r = 1 + level_budget(chunks_of(nb, b)) / ((int64_t)p.kp * I8_INFLATION);
+                const int64_t up = isc_ceil_div<int64_t>(isc_ceil_div<int64_t>(b, r), TM) * TM;
+                nb = up > nb ? up : nb + TM;
+            }
+            if (nb >= b) ok = false;
+            b = nb;
+        }
+        if (ok) {
+            p.nlevels = 1;
+            for (int j = m - 1; j >= 0; --j) {
+                add(p.levels[p.nlevels - 1].r1, ends[j], 0);
+                Level& l = p.levels[p.nlevels - 1];
+                if (fits_i8(l.r0, l.r1)) l.kind = 2;
+                else ok = false;
+            }
+            // The piece next to the sample runs in fp16 when longer levels follow: it is short (less than R8 - 1 times the
+            // sample), so the rows it saves cost less than its k_rescore launch (10 M x 768, Q = 1024: 7.47 -> 7.28 ms per
+            // search, LABLOG.md).  Its float survivors are a sixteenth of what the int8 test above allows for.
+            if (ok && !i8_first_piece_i8() && p.nlevels > 2) p.levels[1].kind = 1;
+        }
+        if (!ok) {
+            p = flt;
+            Level& l = p.levels[p.nlevels - 1];
+            if (p.nlevels >= 3 && (double)p.kp * (double)(l.r1 - l.r0) / (double)l.r0 * I8_INFLATION <= (double)p.budget)
+                l.kind = 2;
+        }
+    }
     // the redo of unproven queries streams the WHOLE bank as one level (run()): its chunks need segments too
     const int redo_chunks = (int)(wgs < ntiles_all ? wgs : ntiles_all);
     if (p.segs_per_chunk * redo_chunks > p.max_seg) p.max_seg = p.segs_per_chunk * redo_chunks;
@@ -235,7 +327,7 @@ struct Workspace {
     int32_t* qflag2;          // [qpad]  slot -> a candidate buffer overflowed
     unsigned char* qpacked2;  // [qtiles][ks][tnq][128 B]  packed query rows by slot
     IscExactWs exact;        // list + partial lists of k_exact (the exhaustive float64 pass, the last resort)
-    // the int8 level of an fp16 search (run(): use_i8): the pass's queries quantised, and their records
+    // the int8 levels of an fp16 search (run(): use_i8): the pass's queries quantised, and their records
     unsigned char* qpacked8;  // [qtiles][K steps of 128 dims][tnq][128 B]
     float4* qrec8;            // [qpad]  (c_q, ||Q||_2, e_q, unused)
     size_t bytes;
@@ -320,7 +412,7 @@ __global__ __launch_bounds__(256) void k_prep(const TQ* __restrict__ queries, in
     *reinterpret_cast<uint4*>(packed + (size_t)i * 16) = *reinterpret_cast<const uint4*>(v);
 }
 
-// The queries of a pass once more as int8, for the last level of a large-batch fp16 search (run(): use_i8).  One wave per
+// The queries of a pass once more as int8, for the int8 levels of a large-batch fp16 search (run(): use_i8).  One wave per
 // query row of the padded pass.  The query is first rounded to fp16 -- it is the fp16-rounded query whose dot products the
 // thresholds are about -- then quantised like a bank tile (bank_pack.hip: k_bank_quantize) with its own inverse scale
 // c_q = 127 / max |q|: Q = rint(q c_q), e_q >= ||q c_q - Q||_2 and ||Q||_2, both from float64 sums and rounded up.
@@ -455,6 +547,30 @@ struct IscShadowArgs {
     const float4* qrec;        // [qpad]: (c_q, ||Q||_2 bound, e_q bound, unused); c_q = NaN: the query passes nothing
 };
 
+// The int8 test of one (query, tile) pair: the largest integer an accumulator acc = Q.X may have while the row is proven to
+// score <= the threshold.  The caller keeps a row when acc > the returned value.  With q = (Q + dq) / c_q and
+// x = (X + dx) / c_t (Q, X the stored integers; c_q, c_t the stored floats, so both identities are exact):
+//     q.x c_q c_t = Q.X + Q.dx + dq.(X + dx),
+// and by Cauchy-Schwarz |Q.dx| <= ||Q|| e_t, |dq.(X + dx)| <= e_q (n_t + e_t).  Hence q.x > thr implies
+//     Q.X > thr c_q c_t - M,     M = ||Q|| e_t + e_q (n_t + e_t)
+// for every row of the tile: testing acc (exact in int32) against any number <= the right-hand side keeps every row whose
+// score exceeds thr.  The right-hand side is evaluated in float32 with at most two roundings in t and four in M and t - M,
+// each relative 2^-24 of |t| or M (all terms of M are non-negative): the error is below 6 * 2^-24 (|t| + M), and
+// delta = 2^-20 (|t| + M) + 1e-30 covers it (the constant: a t that underflows to zero while the true bound is a hair below
+// an integer).  acc is an integer, so acc > x <=> acc > floor(x).  t = +inf (the true bound exceeds every possible acc) and
+// a NaN (a query that takes no part: k_prep_i8) pass nothing; t = -inf passes everything; the result saturates to +-INT32.
+// A tile with a non-finite value (n_t = +inf) passes every row.
+//   thr_cq = thr * c_q (rounded once);  ct, et, nt = the tile's IscShadowRec;  qn, eq = ||Q||_2 and e_q of the query.
+// k_dots_filter's int8 epilogue calls it with the level's tau, k_rescore's second stage with tau' >= tau.
+__device__ __forceinline__ int isc_i8_threshold(float thr_cq, float ct, float et, float nt, float qn, float eq) {
+    const float t = thr_cq * ct;
+    const float mg = fmaf(qn, et, eq * (nt + et));
+    const float lo = (t - mg) - (fabsf(t) + mg) * 9.5367431640625e-7f - 1e-30f;
+    int r = !(lo <= 2.0e9f) ? INT32_MAX : lo < -2.0e9f ? INT32_MIN : (int)floorf(lo);
+    if (!(nt < INFINITY)) r = thr_cq < INFINITY ? INT32_MIN : INT32_MAX;
+    return r;
+}
+
 // LDS fragment read, hidden from the compiler: a C++ load from the staging array would make hipcc drain the
 // in-flight LDS-DMA (s_waitcnt vmcnt(0)) in front of it.  The destination is valid only after the counted
 // lgkmcnt wait that names it.
@@ -532,7 +648,7 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
                                                           Cand* __restrict__ qlist, int kp, int nslots,
                                                           int32_t* __restrict__ qflag, int32_t* __restrict__ status,
                                                           const int32_t* __restrict__ active, RowMask... row_mask) {
-    // I8: the last level of a large-batch search on the int8 shadow bank (run(): use_i8).  T = signed char, the pack holds
+    // I8: a level of a large-batch search on the int8 shadow bank (run(): a level of kind 2).  T = signed char, the pack holds
     // one IscShadowArgs, the accumulators are integers and the threshold test at a tile's end is the one derived there.
     constexpr bool I8 = std::is_same<T, signed char>::value;
     typedef typename Mma<T>::Acc Acc;
@@ -1212,27 +1328,10 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
             }
             if constexpr (GROUP && !DEFER) apply_codes(MBE_C{}, tile_codes);
             if constexpr (I8) {
-                // ---- int8 test.  With q = (Q + dq) / c_q and x = (X + dx) / c_t (Q, X the stored integers; c_q, c_t the
-                // stored floats, so both identities are exact):   q.x c_q c_t = Q.X + Q.dx + dq.(X + dx),   and by
-                // Cauchy-Schwarz |Q.dx| <= ||Q|| e_t, |dq.(X + dx)| <= e_q (n_t + e_t).  Hence q.x > tau implies
-                //     Q.X > tau c_q c_t - M,     M = ||Q|| e_t + e_q (n_t + e_t)
-                // for every row of the tile: testing acc = Q.X (exact in int32) against any number <= the right-hand
-                // side keeps every row the fp16 filter could keep.  The right-hand side is evaluated in float32 with at
-                // most two roundings in t and four in M and t - M, each relative 2^-24 of |t| or M (all terms of M are
-                // non-negative): the error is below 6 * 2^-24 (|t| + M), and delta = 2^-20 (|t| + M) + 1e-30 covers it
-                // (the constant: a t that underflows to zero while the true bound is a hair below an integer).  acc is
-                // an integer, so acc > x <=> acc > floor(x).  t = +inf (the true bound exceeds every possible acc) and a
-                // NaN (a query that takes no part: k_prep_i8) pass nothing; t = -inf passes everything.
+                // ---- int8 test (isc_i8_threshold: the derivation): a row is kept when acc = Q.X > thr_i
                 int thr_i[4];
 #pragma unroll
-                for (int n = 0; n < 4; ++n) {
-                    const float t = thr[n] * tile_ct;
-                    const float mg = fmaf(qn8[n], tile_et, eq8[n] * (tile_nt + tile_et));
-                    const float lo = (t - mg) - (fabsf(t) + mg) * 9.5367431640625e-7f - 1e-30f;
-                    thr_i[n] = !(lo <= 2.0e9f) ? INT32_MAX : lo < -2.0e9f ? INT32_MIN : (int)floorf(lo);
-                    // a tile with a non-finite value (n_t = +inf): every row passes
-                    if (!(tile_nt < INFINITY)) thr_i[n] = thr[n] < INFINITY ? INT32_MIN : INT32_MAX;
-                }
+                for (int n = 0; n < 4; ++n) thr_i[n] = isc_i8_threshold(thr[n], tile_ct, tile_et, tile_nt, qn8[n], eq8[n]);
                 if (r0 + (int64_t)(tile_begin + tile + 1) * TM > r1) {  // rows past the end: below every threshold
 #pragma unroll
                     for (int m = 0; m < MBE; ++m)
@@ -1689,74 +1788,183 @@ __global__ __launch_bounds__(SEL_THREADS, 4) void k_select(int32_t* __restrict__
     }
 }
 
-// After the int8 level: one workgroup per query gives every entry of the query's list its float32 score -- the dot of the
-// packed fp16 row and the packed fp16 query; products of two halves are exact in float32, and k_final's eps bounds the
-// accumulation error of ANY order -- and keeps the entries with score > tau, the float filter's strict test, compacted in
-// place; qcount becomes their number.  What the list holds afterwards is what an fp16 level could have put there.
-// One wave per entry, four entries of a wave in flight; lane l covers 16-byte chunks l and l + 64 of the row (ks <= 16).
-__global__ __launch_bounds__(SEL_THREADS, 2) void k_rescore(const unsigned char* __restrict__ bank, int ks,
-                                                            const unsigned char* __restrict__ qpacked, int tnq,
-                                                            const float* __restrict__ tau, int32_t* __restrict__ qcount,
-                                                            Cand* __restrict__ qlist, int64_t nrows) {
-    __shared__ float score[QCAP];
-    __shared__ int kept;
-    const int q = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+// After an int8 level: one workgroup per query turns the query's list of int8 survivors, entries ((float)acc, packed row),
+// into what an fp16 level could have put there: entries (float32 score, row) with score > tau, the float filter's strict
+// test, compacted in place; qcount becomes their number.  A float32 score is the dot of the packed fp16 row and the packed
+// fp16 query: products of two halves are exact in float32, and k_final's eps bounds the accumulation error of ANY order.
+// Six or seven of eight entries are false positives of the Cauchy-Schwarz bound, so the rows are fetched in two stages
+// ("The int8 level": the proof):
+//   A. the P = 2 kp entries with the best approximate score acc / (c_q c_t) are fetched and scored;
+//      tau' = max(tau, the kp-th largest of the carried scores and these P scores), tau' = tau with fewer than kp scores;
+//   B. every other entry is fetched only if acc > isc_i8_threshold(tau' ...), the int8 epilogue's own test with tau' in
+//      the place of tau: an entry that fails it is proven to score <= tau', which the next selection's kp-th score is at
+//      least.  Nothing depends on the approximate scores being good: they only decide how many rows stage B fetches.
+// One wave per row, eight rows of a wave in flight in stage B (four in stage A, which has P / 8 rows per wave and the
+// entries' registers still live), their indices in LDS before the first bank load; lane l covers 16-byte chunks l and
+// l + 64 of the row (ks <= 16).
+#ifdef ISC_ABLATION
+// ablation builds: per k_rescore workgroup (query and level) the list entries, the rows stage A fetched, the rows stage B
+// fetched, and the workgroups counted; run() prints and clears them when ISC_RESCORE_COUNT is set (LABLOG.md section 5)
+__device__ unsigned long long g_abl_rescore[4];
+#endif
+constexpr int RS_PMAX = ISC_TOPK_MAX_K + 8;  // what SelShared::topk holds: P = min(2 kp, this), i.e. 2 kp up to kp = 64
+
+// float32 scores of rows prow[0 .. np) against the query held in qv; store(i, row, score) is called by lane 0 of the wave
+// that owns entry i
+template <int RS_ROWS, typename Store>
+__device__ __forceinline__ void rescore_rows(const unsigned char* __restrict__ bank, int ks, const float (&qv)[2][8],
+                                             const int* prow, int np, int64_t nrows, Store store) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int NW = SEL_THREADS / 64;
-    const int n = min(qcount[q], QCAP);
-    Cand* list = qlist + (size_t)q * QCAP;
-    const unsigned char* qrow_base = qpacked + ((size_t)(q / tnq) * ks * tnq + (q % tnq)) * ISC_KSTEP_BYTES;
     const int nch = ks * 8;
-    float qv[2][8];
+    for (int c0 = wave; c0 < np; c0 += RS_ROWS * NW) {
+        int row[RS_ROWS];
+        uint4 raw[RS_ROWS][2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int ch = lane + 64 * h;
-        uint4 raw = make_uint4(0u, 0u, 0u, 0u);
-        if (ch < nch) raw = *reinterpret_cast<const uint4*>(qrow_base + (size_t)(ch >> 3) * tnq * ISC_KSTEP_BYTES + (ch & 7) * 16);
-        const _Float16* hv = reinterpret_cast<const _Float16*>(&raw);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) qv[h][j] = (float)hv[j];
-    }
-    if (tid == 0) kept = 0;
-    for (int c0 = wave; c0 < n; c0 += 4 * NW) {
-        float acc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < RS_ROWS; ++u) {
             const int c = c0 + u * NW;
-            int row = c < n ? list[c].row : 0;
-            if ((unsigned)row >= (unsigned)nrows) row = 0;  // cannot happen; k_final refuses such an entry
-            acc[u] = 0.f;
+            row[u] = c < np ? prow[c] : 0;
+            if ((unsigned)row[u] >= (unsigned)nrows) row[u] = 0;  // cannot happen; k_final refuses such an entry
+        }
+#pragma unroll
+        for (int u = 0; u < RS_ROWS; ++u)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int ch = lane + 64 * h;
-                if (ch < nch) {
-                    const uint4 raw = *reinterpret_cast<const uint4*>(bank + isc_packed_offset(row, ch >> 3, ks) + (ch & 7) * 16);
-                    const _Float16* hv = reinterpret_cast<const _Float16*>(&raw);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[u] = fmaf((float)hv[j], qv[h][j], acc[u]);
-                }
+                raw[u][h] = make_uint4(0u, 0u, 0u, 0u);
+                if (ch < nch && c0 + u * NW < np)  // (wave-uniform in u)
+                    raw[u][h] = *reinterpret_cast<const uint4*>(bank + isc_packed_offset(row[u], ch >> 3, ks) + (ch & 7) * 16);
             }
-        }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float tot = isc_wave_sum(acc[u]);
-            if (lane == 0 && c0 + u * NW < n) score[c0 + u * NW] = tot;
+        for (int u = 0; u < RS_ROWS; ++u) {
+            float acc = 0.f;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const _Float16* hv = reinterpret_cast<const _Float16*>(&raw[u][h]);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc = fmaf((float)hv[j], qv[h][j], acc);
+            }
+            const float tot = isc_wave_sum(acc);
+            if (lane == 0 && c0 + u * NW < np) store(c0 + u * NW, row[u], tot);
         }
     }
-    __syncthreads();
-    // every entry is read before any is written: the compaction is in place
+}
+
+// (two waves per SIMD: at four the entries' registers spill to scratch, 7.28 -> 7.65 ms per search at the headline shape)
+__global__ __launch_bounds__(SEL_THREADS, 2) void k_rescore(const unsigned char* __restrict__ bank, int ks,
+                                                            const unsigned char* __restrict__ qpacked, int tnq, int kp,
+                                                            const float* __restrict__ tau,
+                                                            const float* __restrict__ carry_s,
+                                                            const int32_t* __restrict__ carry_n, IscShadowArgs sa,
+                                                            int32_t* __restrict__ qcount, Cand* __restrict__ qlist,
+                                                            int64_t nrows) {
+    __shared__ SelShared sh;
+    __shared__ int prow[QCAP];                // rows to fetch: stage A's P, then stage B's
+    __shared__ float vals[RS_PMAX + ISC_TOPK_MAX_K + 8];  // stage A: the P float32 scores, then the carried ones
+    __shared__ float tau2_sh;
+    __shared__ int kept, npend;
+    const int q = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int n = min(qcount[q], QCAP);
+    if (n == 0) return;  // (workgroup-uniform; qcount stays 0)
+    Cand* list = qlist + (size_t)q * QCAP;
     const float t = tau[q];
-    int rows[SEL_PER];
-#pragma unroll
-    for (int j = 0; j < SEL_PER; ++j) rows[j] = tid + SEL_THREADS * j < n ? list[tid + SEL_THREADS * j].row : 0;
-    __syncthreads();
+    const float4 qr = sa.qrec[q];
+    const int nc = min(carry_n[q], kp);
+    const int ptarget = min(2 * kp, RS_PMAX);
+
+    // every entry into registers (the compaction below is in place: nothing is read from the list after this), with its
+    // tile's record; key = (approximate score, row)
+    int eacc[SEL_PER];
+    unsigned long long key[SEL_PER + 1];
 #pragma unroll
     for (int j = 0; j < SEL_PER; ++j) {
         const int i = tid + SEL_THREADS * j;
-        if (i < n && score[i] > t) list[atomicAdd(&kept, 1)] = Cand{score[i], rows[j]};
+        Cand e{0.f, 0};
+        if (i < n) e = list[i];
+        if ((unsigned)e.row >= (unsigned)nrows) e.row = 0;  // cannot happen
+        eacc[j] = (int)e.s;  // exact: |acc| <= Dpad 127^2 < 2^24
+        IscShadowRec r{1.f, 1.f, 0.f, 0.f};
+        if (i < n) r = sa.recs[e.row >> 8];
+        const float approx = e.s / (qr.x * r.inv_scale);
+        // the rows of a tile with a non-finite value all pass the filter and say nothing: they rank last
+        key[j] = i < n ? isc_make_key(approx == approx && r.qnorm < INFINITY ? approx : -INFINITY, e.row) : 0ull;
+    }
+    key[SEL_PER] = 0ull;
+    float qv[2][8];
+    {
+        const unsigned char* qrow_base = qpacked + ((size_t)(q / tnq) * ks * tnq + (q % tnq)) * ISC_KSTEP_BYTES;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int ch = lane + 64 * h;
+            uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+            if (ch < ks * 8) raw = *reinterpret_cast<const uint4*>(qrow_base + (size_t)(ch >> 3) * tnq * ISC_KSTEP_BYTES + (ch & 7) * 16);
+            const _Float16* hv = reinterpret_cast<const _Float16*>(&raw);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) qv[h][j] = (float)hv[j];
+        }
+    }
+    if (tid == 0) {
+        kept = 0;
+        npend = 0;
+    }
+
+    // ---- stage A: the best P by approximate score (an adversarial list order overflows the ranking buffer: no stage A,
+    // tau' = tau, stage B fetches every entry, as the one-stage form did)
+    const int nsel = wg_select_keys(sh, key, ptarget);
+    const int np = nsel < 0 ? 0 : nsel;
+    const unsigned long long pkey = np > 0 ? sh.topk[np - 1] : ~0ull;  // entries with key >= pkey are the P (keys are distinct)
+    if (tid < np) prow[tid] = isc_key_row(sh.topk[tid]);
+    if (tid < nc) vals[RS_PMAX + tid] = carry_s[(size_t)q * kp + tid];
+    __syncthreads();
+    rescore_rows<4>(bank, ks, qv, prow, np, nrows, [&](int i, int row, float s) {
+        vals[i] = s;
+        if (s > t) list[atomicAdd(&kept, 1)] = Cand{s, row};
+    });
+    __syncthreads();
+    // tau': the kp-th largest of the np + nc scores (a NaN counts as -inf), by counting
+    const int nv = np + nc;
+    if (tid == 0) tau2_sh = t;
+    __syncthreads();
+    if (nv >= kp && tid < nv) {
+        auto val = [&](int i) {
+            const float v = vals[i < np ? i : RS_PMAX + (i - np)];
+            return v == v ? v : -INFINITY;
+        };
+        const float mine = val(tid);
+        int rank = 0;
+        for (int j = 0; j < nv; ++j) {
+            const float o = val(j);
+            rank += (o > mine || (o == mine && j < tid)) ? 1 : 0;
+        }
+        if (rank == kp - 1) tau2_sh = fmaxf(t, mine);  // exactly one thread has this rank
     }
     __syncthreads();
+    const float t2 = tau2_sh;
+
+    // ---- stage B: the entries outside the P that the int8 test with tau' cannot drop
+    const float t2c = t2 * qr.x;
+#pragma unroll
+    for (int j = 0; j < SEL_PER; ++j) {
+        if (key[j] == 0ull || key[j] >= pkey) continue;
+        const int row = isc_key_row(key[j]);
+        const IscShadowRec r = sa.recs[row >> 8];
+        if (eacc[j] > isc_i8_threshold(t2c, r.inv_scale, r.resid, r.qnorm, qr.y, qr.z)) prow[atomicAdd(&npend, 1)] = row;
+    }
+    __syncthreads();
+    rescore_rows<8>(bank, ks, qv, prow, npend, nrows, [&](int, int row, float s) {
+        if (s > t) list[atomicAdd(&kept, 1)] = Cand{s, row};
+    });
+    __syncthreads();
     if (tid == 0) qcount[q] = kept;
+#ifdef ISC_ABLATION
+    if (tid == 0) {
+        atomicAdd(&g_abl_rescore[0], (unsigned long long)n);
+        atomicAdd(&g_abl_rescore[1], (unsigned long long)np);
+        atomicAdd(&g_abl_rescore[2], (unsigned long long)npend);
+        atomicAdd(&g_abl_rescore[3], 1ull);
+    }
+#endif
 }
 
 // Exact float64 dots of `nc` candidates with one query: one wave per candidate, a lane covers the 16-byte chunk `ch` of
@@ -2191,19 +2399,13 @@ __host__ inline IscGroups pass_filter(IscGroups g, int q0, int q, const int32_t*
 // RowMask: empty, or the row filter of isc_cosine_topk_masked (const uint32_t*), handed to every filter launch and k_exact;
 // or the IscGroups of isc_cosine_topk_grouped.  k_final and k_final2 are the masked ones in both cases: neither reads the
 // filter, and the short-list proof of k_final holds for any per-(row, query) predicate.
-// The int8 level ("The int8 level"): an fp16 search with several 256-query tiles runs its LAST level on
-// the bank's int8 shadow when the plan has a level between the sample and the last one -- the last level is where the time is
-// and the only one whose threshold is strong enough to absorb what the loosened int8 test lets through.  The loosening
-// multiplies the survivors by a data-dependent factor (about 8 on unit rows of 768 iid dimensions); the level is taken
-// only if I8_INFLATION times the float filter's expected survivors, kp (rows of the level / rows before it), still fit the
-// budget the level's lists are sized for.  A bank that inflates more overflows a list: the query is flagged and redone by
-// the fp16 filter, as after any overflow.  Dpad 127^2 < 2^24 keeps an accumulator exactly convertible to float32.
-constexpr int I8_INFLATION = 16;
-bool plan_uses_i8(const Plan& p, int d) {
-    if (p.tnq != 256 || p.qtiles <= 1 || p.nlevels < 3) return false;
-    if ((int64_t)isc_shadow_ksteps(d) * ISC_SHADOW_KSTEP_DIMS * 127 * 127 >= (1 << 24)) return false;
-    const Level& l = p.levels[p.nlevels - 1];
-    return (double)p.kp * (double)(l.r1 - l.r0) / (double)l.r0 * I8_INFLATION <= (double)p.budget;
+// The int8 levels (make_plan; DESIGN.md section 2, "The int8 level") take accumulators that convert to float32 exactly:
+// Dpad 127^2 < 2^24.
+bool i8_dims_ok(int d) { return (int64_t)isc_shadow_ksteps(d) * ISC_SHADOW_KSTEP_DIMS * 127 * 127 < (1 << 24); }
+bool plan_has_i8(const Plan& p) {
+    for (int li = 0; li < p.nlevels; ++li)
+        if (p.levels[li].kind == 2) return true;
+    return false;
 }
 
 template <typename T, typename TQ, typename... RowMask>
@@ -2211,8 +2413,8 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q_total, in
         const float* norm_bound, float* out_s, int64_t* out_i, int32_t* status, void* ws_base, hipStream_t stream,
         const void* shadow, RowMask... rm) {
     constexpr bool MASK = sizeof...(RowMask) > 0;
-    const Plan p = make_plan(n, q_total, k);
-    const bool use_i8 = std::is_same<T, _Float16>::value && !MASK && shadow != nullptr && plan_uses_i8(p, d);
+    const Plan p = make_plan(n, q_total, k, 0, std::is_same<T, _Float16>::value && !MASK && shadow != nullptr && i8_dims_ok(d));
+    const bool use_i8 = plan_has_i8(p);
 #ifdef ISC_ABLATION
     static const bool thr_inf_set = [] {
         const int v = getenv("ISC_THR_INF") != nullptr;
@@ -2241,8 +2443,8 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q_total, in
         const FilterIO io{w.qpacked, w.tau, w.qcount, w.qflag, nullptr};
         for (int li = 0; li < p.nlevels; ++li) {
             const Level& l = p.levels[li];
-            if (use_i8 && li == p.nlevels - 1) {
-                // the last level on the shadow bank: the same segments, the int8 kernel, then the float32 re-score
+            if (l.kind == 2) {
+                // a level on the shadow bank: the same segments, the int8 kernel, then the two-stage float32 re-score
                 const unsigned char* sh = static_cast<const unsigned char*>(shadow);
                 const IscShadowArgs sa{reinterpret_cast<const IscShadowRec*>(sh + isc_shadow_data_bytes(n, d)), w.qrec8};
                 for_each_segment(l, p, [&](const Level& ls) {
@@ -2254,27 +2456,27 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q_total, in
                     isc_timing_end(ISC_KERNEL_DOTS_FILTER, stream);
                 });
                 hipLaunchKernelGGL(k_rescore, dim3(q), dim3(SEL_THREADS), 0, stream, bank_bytes, ksteps, w.qpacked, p.tnq,
-                                   w.tau, w.qcount, w.qlist, n);
-                continue;
+                                   p.kp, w.tau, w.carry_s, w.carry_n, sa, w.qcount, w.qlist, n);
+            } else {
+                // With several query-tile workgroups per chunk, a long level runs as several launches over consecutive row
+                // ranges (same thresholds, no selection in between): the partner workgroups that share a chunk's bank rows
+                // through their XCD's L2 drift apart as a launch goes on, and a kernel boundary realigns them for free
+                // (measured L2 -> fabric reads per search: 1.9 x the algorithmic bytes with 594 tiles per chunk and launch,
+                // 1.3 x with 127 / 483).
+                for_each_segment(l, p, [&](const Level& ls) {
+                    isc_timing_begin(ISC_KERNEL_DOTS_FILTER, stream);
+                    if (p.tnq == 256)
+                        launch_filter<T, 256>(ls, p, w, io, bank_bytes, ksteps, status, stream,
+                                              pass_filter(rm, q0, q, nullptr)...);
+                    else if (p.tnq == 128)
+                        launch_filter<T, 128>(ls, p, w, io, bank_bytes, ksteps, status, stream,
+                                              pass_filter(rm, q0, q, nullptr)...);
+                    else
+                        launch_filter<T, 64>(ls, p, w, io, bank_bytes, ksteps, status, stream,
+                                             pass_filter(rm, q0, q, nullptr)...);
+                    isc_timing_end(ISC_KERNEL_DOTS_FILTER, stream);
+                });
             }
-            // With several query-tile workgroups per chunk, a long level runs as several launches over consecutive row
-            // ranges (same thresholds, no selection in between): the partner workgroups that share a chunk's bank rows
-            // through their XCD's L2 drift apart as a launch goes on, and a kernel boundary realigns them for free
-            // (measured L2 -> fabric reads per search: 1.9 x the algorithmic bytes with 594 tiles per chunk and launch,
-            // 1.3 x with 127 / 483).
-            for_each_segment(l, p, [&](const Level& ls) {
-                isc_timing_begin(ISC_KERNEL_DOTS_FILTER, stream);
-                if (p.tnq == 256)
-                    launch_filter<T, 256>(ls, p, w, io, bank_bytes, ksteps, status, stream,
-                                          pass_filter(rm, q0, q, nullptr)...);
-                else if (p.tnq == 128)
-                    launch_filter<T, 128>(ls, p, w, io, bank_bytes, ksteps, status, stream,
-                                          pass_filter(rm, q0, q, nullptr)...);
-                else
-                    launch_filter<T, 64>(ls, p, w, io, bank_bytes, ksteps, status, stream,
-                                         pass_filter(rm, q0, q, nullptr)...);
-                isc_timing_end(ISC_KERNEL_DOTS_FILTER, stream);
-            });
             if (li + 1 < p.nlevels) {
                 if (spec_all)
                     hipLaunchKernelGGL(k_select<SEL_PER>, dim3(q), dim3(SEL_THREADS), 0, stream, w.qcount, w.qlist, p.kp,
@@ -2332,6 +2534,17 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q_total, in
                                   isc_row_mask_ptr(rm...), stream);
         if (st != ISC_OK) return st;
     }
+#ifdef ISC_ABLATION
+    if (use_i8 && getenv("ISC_RESCORE_COUNT")) {  // synchronises: a counting run is not a timing run
+        unsigned long long c[4] = {0, 0, 0, 0};
+        const unsigned long long zero[4] = {0, 0, 0, 0};
+        if (hipStreamSynchronize(stream) == hipSuccess &&
+            hipMemcpyFromSymbol(c, HIP_SYMBOL(g_abl_rescore), sizeof(c)) == hipSuccess && c[3] > 0)
+            fprintf(stderr, "k_rescore per query and level: %.1f entries, %.1f rows fetched in stage A, %.1f in stage B (%llu)\n",
+                    (double)c[0] / c[3], (double)c[1] / c[3], (double)c[2] / c[3], c[3]);
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_abl_rescore), zero, sizeof(zero));
+    }
+#endif
     return isc_launch_status();
 }
 
@@ -2410,7 +2623,22 @@ extern "C" int isc_cosine_topk_uses_shadow(int dtype, int64_t N, int D, int Q, i
     ISC_REQUIRE(uses);
     const int st = check_args(dtype, N, D, Q, k);
     if (st != ISC_OK) return st;
-    *uses = dtype == ISC_F16 && plan_uses_i8(make_plan(N, Q, k), D) ? 1 : 0;
+    *uses = plan_has_i8(make_plan(N, Q, k, 0, dtype == ISC_F16 && i8_dims_ok(D))) ? 1 : 0;
+    return ISC_OK;
+}
+
+extern "C" int isc_cosine_topk_plan(int dtype, int64_t N, int D, int Q, int k, int shadow, int max_levels, int* nlevels,
+                                    int64_t* row_end, int* kind) {
+    ISC_REQUIRE(nlevels && row_end && kind && max_levels >= 0);
+    const int st = check_args(dtype, N, D, Q, k);
+    if (st != ISC_OK) return st;
+    const Plan p = make_plan(N, Q, k, 0, shadow != 0 && dtype == ISC_F16 && i8_dims_ok(D));
+    *nlevels = p.nlevels;
+    if (p.nlevels > max_levels) return ISC_ERR_INVALID_ARG;
+    for (int li = 0; li < p.nlevels; ++li) {
+        row_end[li] = p.levels[li].r1;
+        kind[li] = p.levels[li].kind;
+    }
     return ISC_OK;
 }
 

@@ -1041,7 +1041,7 @@ class EmbeddingBank:
 
     def _shadow_for(self, nq: int, k: int) -> Tensor | None:
         """The bank's int8 shadow if a plain search of `nq` queries uses it (`isc_cosine_topk_uses_shadow`: an fp16 bank,
-        more than 256 queries per pass, a plan with a level between the sample and the last), built on the current stream
+        more than 256 queries per pass, a plan with an int8 level -- `isc_cosine_topk_plan`), built on the current stream
         the first time and kept until `append` / `reserve` change the image.  None while the stream is being captured: the
         fp16 levels run then, with the same answer."""
         if not self.shadow or self.dtype != torch.float16 or nq <= 256 or self._fill is not None:

@@ -463,15 +463,24 @@ int isc_cosine_topk(const void* bank, int dtype, int64_t N, int D, const void* q
  * when the call ran: build it again after isc_bank_pack / isc_bank_append / isc_bank_repack touched the bank.
  *
  * isc_cosine_topk_shadow: isc_cosine_topk with the shadow of `bank` (or NULL: exactly isc_cosine_topk).  Same results,
- * bit for bit: when the call has more than 256 queries per pass and its plan has a level between the sample and the last
- * one (isc_cosine_topk_uses_shadow tells, host only), the LAST filter level streams the int8 shadow instead of the fp16
- * rows -- half the bytes and half the matrix-core work per row -- with a threshold loosened by a proven bound of the
- * quantisation error, so that it keeps every row the fp16 filter keeps; the survivors are re-scored from the fp16 rows
- * and filtered with the fp16 threshold before the exact pass sees them.  Every other call runs isc_cosine_topk's launches.
- * Same workspace (isc_cosine_topk_workspace_bytes). */
+ * bit for bit: when the call has more than 256 queries per pass (isc_cosine_topk_uses_shadow tells, host only), the
+ * filter levels after the sample stream the int8 shadow instead of the fp16 rows -- half the bytes and half the
+ * matrix-core work per row -- with a threshold loosened by a proven bound of the quantisation error, so that they keep
+ * every row the fp16 filter keeps; the survivors that the same bound cannot drop against the threshold of the best of
+ * them are re-scored from the fp16 rows and filtered with the fp16 threshold before the next selection sees them.  Every
+ * other call runs isc_cosine_topk's launches.  Same workspace (isc_cosine_topk_workspace_bytes).
+ *
+ * isc_cosine_topk_plan (host only): the filter levels of such a call.  Level i covers packed rows
+ * [row_end[i - 1], row_end[i]) (level 0 from row 0; the last ends at N), every boundary but N a multiple of 256;
+ * kind[i] = 0 the sample level, 1 a float filter level, 2 an int8 filter level on the shadow.  shadow = 0: the plan of
+ * isc_cosine_topk and of every masked / grouped call; shadow != 0: the plan of isc_cosine_topk_shadow with a shadow given.
+ * *nlevels is always set; with max_levels < *nlevels nothing else is written and ISC_ERR_INVALID_ARG returned (16 is
+ * enough for every shape).  isc_cosine_topk_uses_shadow = "the shadow != 0 plan holds a level of kind 2". */
 int isc_bank_shadow_bytes(int64_t N, int D, size_t* bytes);
 int isc_bank_quantize(const void* packed, int64_t N, int D, void* shadow, size_t shadow_bytes, void* stream);
 int isc_cosine_topk_uses_shadow(int dtype, int64_t N, int D, int Q, int k, int* uses);
+int isc_cosine_topk_plan(int dtype, int64_t N, int D, int Q, int k, int shadow, int max_levels, int* nlevels,
+                         int64_t* row_end, int* kind);
 int isc_cosine_topk_shadow(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
                            int64_t ldq, int k, int64_t index_base, const float* norm_bound, float* out_scores,
                            int64_t* out_indices, int32_t* status, void* workspace, size_t workspace_bytes,
