@@ -17,7 +17,7 @@ PyTorch is used for device memory, streams and `torch.distributed` only.
 
 from imagescry_amd.batching import ImageTensorDataset, SimilarShapeBatcher
 from imagescry_amd.data import EmbeddingBatch, ImageBatch
-from imagescry_amd.decomposition import PCA
+from imagescry_amd.decomposition import PCA, KMeans
 from imagescry_amd.embedding import (
     EfficientNetEmbedder,
     EmbeddingModule,
@@ -38,6 +38,7 @@ __all__ = [
     "EmbedSearchPipeline",
     "SearchHandle",
     "SearchResult",
+    "KMeans",
     "PCA",
     "RangeResult",
     "RowFilter",

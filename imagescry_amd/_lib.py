@@ -254,6 +254,23 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
         [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
          c_void_p, c_void_p],
     ),
+    "isc_bank_assign_workspace_bytes": (c_int, [c_int, c_int64, c_int, c_int, POINTER(c_size_t)]),
+    "isc_bank_assign": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "isc_bank_assign_exhaustive": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_size_t, c_void_p],
+    ),
+    "isc_bank_group_sums_workspace_bytes": (c_int, [c_int, c_int64, c_int, POINTER(c_size_t)]),
+    "isc_bank_group_sums": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+         c_void_p, c_size_t, c_void_p],
+    ),
 }
 
 _lib: ctypes.CDLL | None = None

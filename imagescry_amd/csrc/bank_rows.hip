@@ -8,15 +8,6 @@
 
 namespace {
 
-// The packed position of listed row r, or -1 for a DEAD row: one outside [0, capacity), or one whose fill bit is clear
-// (empty or removed).  A dead row is never dereferenced.
-__device__ __forceinline__ int64_t live_pos(int64_t r, const IscPerm& pm, const uint32_t* __restrict__ fill_mask) {
-    if (r < 0 || r >= pm.n) return -1;
-    const int64_t p = isc_perm_pos(pm, r);
-    if (fill_mask && !((fill_mask[p >> 5] >> (p & 31)) & 1u)) return -1;
-    return p;
-}
-
 // isc_bank_gather: one wave per listed row, a lane per 16-byte chunk of the row (8 lanes per 128-byte K-step segment, as
 // k_bank_repack reads them).  E is an unsigned integer of the element's size: the bytes move untouched.  A chunk that lies
 // inside the row goes out as one 16-byte store when the output rows are 16-byte aligned (`vec_ok`); the ragged last chunk,
@@ -29,7 +20,7 @@ __global__ __launch_bounds__(256) void k_bank_gather(const unsigned char* __rest
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= m) return;
     const int lane = threadIdx.x & 63;
-    const int64_t p = live_pos(rows[i], pm, fill_mask);
+    const int64_t p = isc_live_pos(rows[i], pm, fill_mask);
     constexpr int PER = 16 / (int)sizeof(E);
     E* dst = out + i * ldo;
     const int chunks = (d + PER - 1) / PER;  // <= 8 * ks
@@ -87,7 +78,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_row_scores(const unsigned char* 
     const int q0 = (int)(blockIdx.x % (unsigned)qgroups) * SC_GQ;
     const int gn = min(SC_GQ, nq - q0);
     const int64_t j = (int64_t)(blockIdx.x / (unsigned)qgroups) * SC_ROWS + wave * 8 + sub;
-    const int64_t p = j < m ? live_pos(rows[j], pm, fill_mask) : -1;
+    const int64_t p = j < m ? isc_live_pos(rows[j], pm, fill_mask) : -1;
     const unsigned char* src = bank + (p >= 0 ? isc_packed_offset(p, 0, ks) : 0) + ch * 16;
 
     double acc[SC_GQ];

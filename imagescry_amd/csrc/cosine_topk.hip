@@ -367,9 +367,7 @@ Workspace carve(const Plan& p, int ks, int64_t n, int k, void* base) {
 
 // Per-query state reset and query packing in one launch.
 // queries row-major [q][ldq] -> packed [qtile][K step][tnq rows][128 B]; rows >= q and columns >= d are zero.
-// One thread per 16-byte chunk; the first qpad threads also reset the per-query words.
-// TQ = element type of the caller's queries: they are rounded to the bank type T while they are packed (float32 -> fp16:
-// v_cvt_f16_f32, round to nearest even = `Tensor.to(float16)`; fp16 -> float32 is exact), so no cast kernel runs in front.
+// One thread per 16-byte chunk (isc_pack_query_chunk, search_common.h); the first qpad threads also reset the per-query words.
 template <typename T, typename TQ>
 __global__ __launch_bounds__(256) void k_prep(const TQ* __restrict__ queries, int64_t ldq, int q, int d, int ks, int qpad,
                                               int tnq, unsigned char* __restrict__ packed, float* __restrict__ tau,
@@ -379,7 +377,6 @@ __global__ __launch_bounds__(256) void k_prep(const TQ* __restrict__ queries, in
                                               float* __restrict__ tau2, int32_t* __restrict__ qcount2,
                                               int32_t* __restrict__ qflag2, int32_t* __restrict__ status,
                                               int zero_status) {
-    constexpr int PER = 16 / (int)sizeof(T);
     const int total = qpad * ks * 8;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < qpad) {
@@ -398,18 +395,7 @@ __global__ __launch_bounds__(256) void k_prep(const TQ* __restrict__ queries, in
     }
     if (zero_status && i < 4) status[i] = 0;
     if (i >= total) return;
-    const int c = i & 7;
-    const int row = (i >> 3) % tnq;
-    const int blk = (i >> 3) / tnq;  // qtile * ks + kstep
-    const int kstep = blk % ks;
-    const int qrow = (blk / ks) * tnq + row;
-    T v[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int e = (kstep * 8 + c) * PER + j;
-        v[j] = (qrow < q && e < d) ? (T)queries[(int64_t)qrow * ldq + e] : (T)0.f;
-    }
-    *reinterpret_cast<uint4*>(packed + (size_t)i * 16) = *reinterpret_cast<const uint4*>(v);
+    isc_pack_query_chunk<T, TQ>(queries, ldq, q, d, ks, tnq, i, packed);
 }
 
 // The queries of a pass once more as int8, for the int8 levels of a large-batch fp16 search (run(): use_i8).  One wave per

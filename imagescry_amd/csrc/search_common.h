@@ -160,6 +160,38 @@ __device__ __forceinline__ double group8_sum(double v) {
     return v;
 }
 
+// ---- the packed image of a call's queries (k_prep of the searches, k_assign_prep of isc_bank_assign) ----------------
+// queries row-major [q][ldq] -> packed [qtile][K step][tnq rows][128 B]; rows >= q and columns >= d are zero.  Thread i
+// of the launch writes 16-byte chunk i of the image (i < padded queries * ks * 8).
+// TQ = element type of the caller's queries: they are rounded to the bank type T while they are packed (float32 -> fp16:
+// v_cvt_f16_f32, round to nearest even = `Tensor.to(float16)`; fp16 -> float32 is exact), so no cast kernel runs in front.
+template <typename T, typename TQ>
+__device__ __forceinline__ void isc_pack_query_chunk(const TQ* __restrict__ queries, int64_t ldq, int q, int d, int ks,
+                                                     int tnq, int i, unsigned char* __restrict__ packed) {
+    constexpr int PER = 16 / (int)sizeof(T);
+    const int c = i & 7;
+    const int row = (i >> 3) % tnq;
+    const int blk = (i >> 3) / tnq;  // qtile * ks + kstep
+    const int kstep = blk % ks;
+    const int qrow = (blk / ks) * tnq + row;
+    T v[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int e = (kstep * 8 + c) * PER + j;
+        v[j] = (qrow < q && e < d) ? (T)queries[(int64_t)qrow * ldq + e] : (T)0.f;
+    }
+    *reinterpret_cast<uint4*>(packed + (size_t)i * 16) = *reinterpret_cast<const uint4*>(v);
+}
+
+// The packed position of listed row r, or -1 for a DEAD row: one outside [0, capacity), or one whose fill bit is clear
+// (empty or removed).  A dead row is never dereferenced.
+__device__ __forceinline__ int64_t isc_live_pos(int64_t r, const IscPerm& pm, const uint32_t* __restrict__ fill_mask) {
+    if (r < 0 || r >= pm.n) return -1;
+    const int64_t p = isc_perm_pos(pm, r);
+    if (fill_mask && !((fill_mask[p >> 5] >> (p & 31)) & 1u)) return -1;
+    return p;
+}
+
 // float64 norm of the packed query row at `qrow_base` (K step s at + s * tnq * 128 B); called by ONE wave, result in
 // every lane
 template <typename T>

@@ -1,4 +1,4 @@
-"""Principal component analysis on MI355X: fit and projection.
+"""Principal component analysis and spherical k-means on MI355X.
 
 Same constructor arguments, attributes and behaviour as the reference `PCA`
 (src/imagescry/models/decomposition.py:11-180).  `fit` keeps everything sample-sized on the GPU -- float64 feature sums,
@@ -7,6 +7,9 @@ symmetric eigenproblem, where the reference runs an SVD of the whole `[N, F]` ma
 `forward` -- the step the reference applies to every embedding batch right after the hot path
 (src/imagescry/models/pipelines.py:76-84) -- runs in the HIP kernel behind `isc_linear_centered`:
 `(x - feature_means) @ component_vectors` with the centring done before the product.
+
+`KMeans` clusters the rows of an `EmbeddingBank` by cosine similarity without unpacking it: every iteration is one
+`EmbeddingBank.assign` (labels only) and one `EmbeddingBank.group_sums`.
 """
 
 from __future__ import annotations
@@ -16,7 +19,7 @@ from torch import Tensor
 
 from imagescry_amd import _lib
 
-__all__ = ["PCA"]
+__all__ = ["PCA", "KMeans"]
 
 
 class PCA:
@@ -234,3 +237,107 @@ class PCA:
     @property
     def num_components(self) -> int:
         return self._num_components
+
+
+class KMeans:
+    """Spherical k-means over the rows of an `EmbeddingBank`: clusters by cosine similarity, centroids of unit length.
+
+    Args:
+        num_clusters: C >= 1.
+        max_iter: most iterations (assignments) `fit` runs; the last one does not move the centroids.
+        tol: `fit` stops when an update raises the objective by less than this.
+        init: `"sample"` (C distinct live rows, drawn with a CPU generator seeded by `seed`) or a `[C, D]` tensor that is
+            used as given.
+        seed: seed of the `"sample"` draw.
+
+    After `fit`: `cluster_centers` (`[C, D]` float32 on the bank's device), `labels` (int32 `[len]`, -1 for removed or
+    masked rows), `counts` (int64 `[C]`), `objective` (one float per iteration: the mean over the live rows of the winning
+    score, before that iteration's update) and `num_iter`.
+    """
+
+    def __init__(self, num_clusters: int, *, max_iter: int = 25, tol: float = 1e-4,
+                 init: "str | Tensor" = "sample", seed: int = 0) -> None:
+        if isinstance(num_clusters, bool) or not isinstance(num_clusters, int) or num_clusters < 1:
+            raise ValueError(f"num_clusters must be a positive int, got {num_clusters!r}")
+        if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
+            raise ValueError(f"max_iter must be a positive int, got {max_iter!r}")
+        if not tol >= 0.0:
+            raise ValueError(f"tol must be >= 0, got {tol!r}")
+        if isinstance(init, str):
+            if init != "sample":
+                raise ValueError(f"init must be 'sample' or a [num_clusters, D] tensor, got {init!r}")
+        elif not (isinstance(init, Tensor) and init.dtype.is_floating_point and init.ndim == 2
+                  and init.shape[0] == num_clusters):
+            raise ValueError(f"init must be 'sample' or a floating [{num_clusters}, D] tensor")
+        self.num_clusters = num_clusters
+        self.max_iter = max_iter
+        self.tol = float(tol)
+        self.init = init
+        self.seed = int(seed)
+        self.cluster_centers: Tensor | None = None
+        self.labels: Tensor | None = None
+        self.counts: Tensor | None = None
+        self.objective: list[float] = []
+        self.num_iter = 0
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}(num_clusters={self.num_clusters}, num_iter={self.num_iter})"
+
+    def _initial_centers(self, bank, live: Tensor, num_live: int) -> Tensor:
+        c = self.num_clusters
+        if isinstance(self.init, Tensor):
+            if self.init.shape[1] != bank.dim:
+                raise ValueError(f"init must have shape [{c}, {bank.dim}], got {tuple(self.init.shape)}")
+            return self.init.detach().to(device=bank.device, dtype=torch.float32).clone()
+        gen = torch.Generator().manual_seed(self.seed)
+        pick = torch.randperm(num_live, generator=gen)[:c]  # distinct positions among the live rows
+        rows = live.nonzero().squeeze(1).cpu()[pick] + bank.index_base
+        return bank.rows(rows).float()
+
+    def fit(self, bank, mask=None) -> "KMeans":
+        """Cluster the live rows of `bank` (those `mask` allows, when given).  Per iteration: `assign` (labels only),
+        `group_sums`, centroid = sum / ||sum|| in float64 (an empty cluster keeps its centroid), and the objective taken
+        from the sums -- the winning score of a row is row . q_c / ||q_c||, so its sum over a cluster is sum_c . q_c /
+        ||q_c|| -- with ONE host read.  Stops when no label changed, when the objective rose by less than `tol`, or after
+        `max_iter` iterations.  ValueError for fewer live rows than clusters and for a sharded bank."""
+        if bank.process_group is not None:
+            raise ValueError("a sharded bank (process_group=) cannot be clustered: " + bank._ROWS_ON_ONE_RANK)
+        rf = bank._as_filter(mask)
+        c = self.num_clusters
+        live = bank.live if rf is None or rf.packed is bank._fill else bank._unpack_mask(rf.packed, len(bank))
+        num_live = int(live.sum())
+        if num_live < c:
+            raise ValueError(f"{c} clusters need at least {c} live rows, the bank has {num_live}")
+        centers = self._initial_centers(bank, live, num_live)
+        self.objective = []
+        labels = None
+        for it in range(self.max_iter):
+            new_labels, _ = bank.assign(centers, mask=rf, return_scores=False)
+            sums, counts = bank.group_sums(new_labels, c)
+            q = centers.to(bank.dtype).double()  # the centroids as `assign` scored them
+            qn = q.norm(dim=1).clamp_min(1e-12)
+            obj = ((sums * q).sum(dim=1) / qn).sum() / num_live
+            changed = (new_labels != labels).any() if labels is not None else torch.ones((), dtype=torch.bool,
+                                                                                          device=new_labels.device)
+            obj_host, changed_host = torch.stack([obj, changed.double()]).tolist()  # the iteration's one host read
+            labels = new_labels
+            self.labels, self.counts = labels, counts
+            self.objective.append(obj_host)
+            self.num_iter = it + 1
+            if not changed_host:
+                break
+            if it > 0 and obj_host - self.objective[-2] < self.tol:
+                break
+            if it + 1 == self.max_iter:  # no update without an assignment behind it: `labels` belong to `cluster_centers`
+                break
+            norm = sums.norm(dim=1, keepdim=True)
+            keep = (counts == 0)[:, None] | ~(norm > 0)
+            centers = torch.where(keep, centers.double(), sums / norm.clamp_min(1e-300)).float()
+        self.cluster_centers = centers
+        return self
+
+    def predict(self, bank) -> Tensor:
+        """The label of every row of `bank` under the fitted centroids: `bank.assign(cluster_centers)` labels."""
+        if self.cluster_centers is None:
+            raise RuntimeError("KMeans model not fitted")
+        return bank.assign(self.cluster_centers, return_scores=False)[0]

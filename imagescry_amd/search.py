@@ -1383,6 +1383,126 @@ class EmbeddingBank:
             self._score_rows(q, index, out)
         return out
 
+    # ------------------------------------------------------------------ nearest centroid, sums per group
+    def _assign_rows(self, q: Tensor, mask: RowFilter | None, labels: Tensor, scores: Tensor | None,
+                     exhaustive: bool) -> None:
+        """`isc_bank_assign` (`exhaustive`: `isc_bank_assign_exhaustive`): `labels` (int32 `[capacity]`) and, unless None,
+        `scores` (float32 `[capacity]`) receive the best centroid of `q` (prepared, C > 0) for every row of the image in
+        ORIGINAL row order, (-1, -inf) for a row `mask` (None: the fill bitmap, if the bank has one) does not allow.  On the
+        current stream, no host read; the status words are left in `last_assign_status`.  A device hook."""
+        lib = _lib.load()
+        dev = self.device
+        n = self.capacity
+        code = _lib.dtype_code(self.dtype)
+        status = torch.empty(4, dtype=torch.int32, device=dev)
+        rm = _lib.ptr(mask.packed) if mask is not None else _lib.ptr(self._fill)
+        ws = None
+        if not exhaustive:
+            need = _lib.c_size_t()
+            _lib.check(lib.isc_bank_assign_workspace_bytes(code, n, self.dim, q.shape[0], need),
+                       "isc_bank_assign_workspace_bytes")
+            if self._assign_ws is None or self._assign_ws.numel() < need.value:
+                self._assign_ws = None
+                self._assign_ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+            ws = self._assign_ws
+        with torch.cuda.device(dev):
+            head = (self._bank.data_ptr(), code, n, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), q.shape[0],
+                    q.stride(0))
+            tail = (rm, labels.data_ptr(), _lib.ptr(scores), status.data_ptr(), _lib.ptr(ws),
+                    0 if ws is None else ws.numel(), _lib.stream_handle(dev))
+            if exhaustive:
+                st = lib.isc_bank_assign_exhaustive(*head, *tail)
+            else:
+                st = lib.isc_bank_assign(*head, self._norm_bound.data_ptr(), *tail)
+        _lib.check(st, "isc_bank_assign_exhaustive" if exhaustive else "isc_bank_assign")
+        self.last_assign_status = status
+
+    def _group_sums(self, rows: Tensor, offsets: Tensor, sums: Tensor, counts: Tensor) -> None:
+        """`isc_bank_group_sums`: `sums[g]` (float64 `[G, D]`) and `counts[g]` (int64 `[G]`) receive the sum and the number
+        of the live rows among `rows[offsets[g]:offsets[g + 1]]` (int64, device; entries past `offsets[G]` are ignored).
+        On the current stream, no host read.  A device hook."""
+        lib = _lib.load()
+        dev = self.device
+        code = _lib.dtype_code(self.dtype)
+        need = _lib.c_size_t()
+        _lib.check(lib.isc_bank_group_sums_workspace_bytes(code, rows.numel(), self.dim, need),
+                   "isc_bank_group_sums_workspace_bytes")
+        if self._sums_ws is None or self._sums_ws.numel() < need.value:
+            self._sums_ws = None
+            self._sums_ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        ws = self._sums_ws
+        with torch.cuda.device(dev):
+            st = lib.isc_bank_group_sums(
+                self._bank.data_ptr(), code, self.capacity, self.dim, rows.data_ptr(), rows.numel(), offsets.data_ptr(),
+                counts.numel(), _lib.ptr(self._fill), sums.data_ptr(), sums.stride(0), counts.data_ptr(), ws.data_ptr(),
+                ws.numel(), _lib.stream_handle(dev),
+            )
+        _lib.check(st, "isc_bank_group_sums")
+
+    _assign_ws: Tensor | None = None  # the workspaces of `assign` and `group_sums`, grown on demand like `_range_ws`
+    _sums_ws: Tensor | None = None
+    last_assign_status: Tensor | None = None
+
+    def _assign(self, centroids: Tensor, mask: "RowFilter | Tensor | None", return_scores: bool,
+                exhaustive: bool) -> tuple[Tensor, Tensor | None]:
+        self._refuse_sharded("assign rows to centroids", self._ROWS_ON_ONE_RANK)
+        q = self._prepare_queries(centroids)
+        if q.shape[0] == 0:
+            raise ValueError("centroids must hold at least one vector")
+        if q.shape[0] > 1 << 24:
+            raise ValueError(f"at most {1 << 24} centroids, got {q.shape[0]}")
+        rf = self._as_filter(mask)
+        n = self.num_local_rows
+        labels = torch.empty(self.capacity, dtype=torch.int32, device=self.device)
+        scores = torch.empty(self.capacity, dtype=torch.float32, device=self.device) if return_scores else None
+        if n:
+            self._assign_rows(q, rf, labels, scores, exhaustive)
+        return labels[:n], None if scores is None else scores[:n]
+
+    def assign(self, centroids: Tensor, *, mask: "RowFilter | Tensor | None" = None,
+               return_scores: bool = True) -> tuple[Tensor, Tensor | None]:
+        """For EVERY stored row the nearest of `centroids` (floating `[C, D]`, C >= 1, as the queries of `search`): labels
+        int32 `[len]` and, with `return_scores`, the winning scores float32 `[len]` (else None), in row order.  The score
+        of a centroid against a row is the score `search` gives the centroid as a query (`scores(centroids, [r])` bit for
+        bit); the best is by score descending, NaN last, ties to the lower centroid.  A removed row, and a row `mask`
+        (`RowFilter` or bool `[N]`) does not allow, gets label -1 and score -inf.  The packed bank is streamed once per 64
+        centroids on the matrix cores and finished exactly (`isc_bank_assign`; `last_assign_status` holds its status
+        words); labels alone are cheaper than labels with scores.  Runs on the caller's current stream with no host read.
+        A sharded bank cannot assign."""
+        return self._assign(centroids, mask, return_scores, False)
+
+    def assign_exhaustive(self, centroids: Tensor, *, mask: "RowFilter | Tensor | None" = None,
+                          return_scores: bool = True) -> tuple[Tensor, Tensor | None]:
+        """`assign` answered by the data-independent float64 kernel (`isc_bank_assign_exhaustive`): slow, the reference
+        `assign` is tested against, bit for bit."""
+        return self._assign(centroids, mask, return_scores, True)
+
+    def group_sums(self, labels: Tensor, num_groups: int) -> tuple[Tensor, Tensor]:
+        """Float64 sums of the stored rows per label: `sums` `[G, D]` float64 and `counts` `[G]` int64 with G =
+        `num_groups`, from `labels` (integer `[len]`, e.g. the labels of `assign`).  Rows whose label is outside `[0, G)`
+        and removed rows are ignored.  A stable sort of the labels lists the rows group by group; `isc_bank_group_sums`
+        adds them in that order without floating-point atomics, so the same labels give the same bits.  No host read.
+        A sharded bank cannot sum rows."""
+        self._refuse_sharded("sum rows per group", self._ROWS_ON_ONE_RANK)
+        n = self.num_local_rows
+        ok = isinstance(labels, Tensor) and labels.ndim == 1 and labels.shape[0] == n
+        if not ok or labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+            raise ValueError(f"labels must be an integer tensor of shape [{n}] (one label per row)")
+        if isinstance(num_groups, bool) or not isinstance(num_groups, int) or num_groups < 0:
+            raise ValueError(f"num_groups must be a non-negative int, got {num_groups!r}")
+        g = num_groups
+        dev = self.device
+        sums = torch.zeros((g, self.dim), dtype=torch.float64, device=dev)
+        counts = torch.zeros(g, dtype=torch.int64, device=dev)
+        if g == 0 or n == 0:
+            return sums, counts
+        lab = labels.to(device=dev, dtype=torch.int64)
+        key = torch.where((lab >= 0) & (lab < g), lab, g)  # the rows without a group sort behind every group
+        skey, order = torch.sort(key, stable=True)
+        offsets = torch.searchsorted(skey, torch.arange(g + 1, dtype=torch.int64, device=dev)).to(torch.int64)
+        self._group_sums(order.contiguous(), offsets.contiguous(), sums, counts)
+        return sums, counts
+
     def similarity_map(self, queries: Tensor, image_id: int) -> Tensor:
         """The score of every query against every cell of one image, on a bank with `row_origin` (`from_database`):
         float32 `[Q, H, W]` with H = the image's largest h + 1 and W = its largest w + 1; cells the bank does not hold, or

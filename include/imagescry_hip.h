@@ -641,6 +641,50 @@ int isc_topk_merge_groups(const float* scores, const int64_t* indices, const int
                           int kout, int64_t stride_g_scores, int64_t stride_g_indices, int64_t stride_g_labels,
                           float* out_scores, int64_t* out_indices, int64_t* out_labels, void* stream);
 
+/* Nearest-centroid assignment, the ROW-major question: for every row of the image laid out for N rows, the centroid with
+ * the best key isc_cosine_topk would give it as a query -- score float32(dot_f64(q_c, b_r) / max(||q_c||_2, 1e-12)) with
+ * the centroid rounded to the bank dtype first (isc_cosine_scores' operations in its order: its bits), score descending,
+ * NaN below every number, -0.0 equal to +0.0, ties to the lower centroid.  A row whose scores are all NaN gets label 0 and
+ * score NaN.  A DEAD row -- row_mask clear; the mask is the bank's fill bitmap or a packed row filter (isc_row_mask_pack),
+ * NULL: every row of [0, N) is live -- gets label -1 and score -inf and its vector is never scored.  Outputs are in
+ * ORIGINAL row order.  One float32 matrix-core pass over the bank per 64 centroids, an exact float64 finish and a proof per
+ * row that the filter lost nothing; rows without a proof are answered by the float64 kernel of
+ * isc_bank_assign_exhaustive.  No host synchronisation (capturable); the workspace's contents on entry do not matter.
+ * C == 0 or N == 0 returns ISC_OK without a launch.  D <= ISC_SEARCH_MAX_D, C <= ISC_SEARCH_MAX_Q; C >
+ * ISC_SEARCH_PASS_QUERIES runs as passes of 1024 centroids merged by key.
+ *   bank, dtype, N, D      as isc_cosine_topk (N = the capacity of the image)
+ *   centroids, c_dtype, C, ldc   row-major [C, D] of ISC_F16 / ISC_F32, leading dimension ldc >= D
+ *   norm_bound   device float [1]: upper bound of the stored rows' norms (isc_bank_pack), NULL = 1.001
+ *   out_labels   int32_t [N]
+ *   out_scores   float [N], or NULL: labels only (rows with one surviving candidate are then never re-scored)
+ *   status       int32_t [4] device words: [0] = rows re-scored against more than one candidate, [1] = rows answered by the
+ *                float64 kernel, [2] = float bits of max |filter score - exact score| / bound over the re-scored candidates
+ *                (must stay < 1), [3] = 0
+ * The workspace depends on (dtype, N, D, min(C, 1024)). */
+int isc_bank_assign_workspace_bytes(int dtype, int64_t N, int D, int C, size_t* bytes);
+int isc_bank_assign(const void* bank, int dtype, int64_t N, int D, const void* centroids, int c_dtype, int C, int64_t ldc,
+                    const float* norm_bound, const uint32_t* row_mask, int32_t* out_labels, float* out_scores,
+                    int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same answer from the data-independent float64 kernel: slow, the on-device reference of isc_bank_assign and what
+ * answers its unproven rows.  status[1] = the live rows, the other words 0.  The workspace is not used (NULL is fine). */
+int isc_bank_assign_exhaustive(const void* bank, int dtype, int64_t N, int D, const void* centroids, int c_dtype, int C,
+                               int64_t ldc, const uint32_t* row_mask, int32_t* out_labels, float* out_scores,
+                               int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Float64 sums of stored rows per group: sums[g] = the sum of the live rows among rows[offsets[g] .. offsets[g + 1]) and
+ * counts[g] = how many of them were live (a dead row: outside [0, N) or fill bit clear; never dereferenced).  `rows` is the
+ * row list sorted by group, offsets[0] = 0 and offsets[G] = M.  Partial sums over fixed chunks of 1024 list entries go to
+ * the workspace and are added in chunk order: no floating-point atomics, two calls on the same inputs give the same bits.
+ * No host synchronisation (capturable).  G == 0 returns ISC_OK without a launch.
+ *   rows      device int64_t [M], 8-byte aligned        offsets   device int64_t [G + 1]
+ *   sums      double [G, ld], ld >= D                    counts    int64_t [G]
+ * The workspace depends on (M, D). */
+int isc_bank_group_sums_workspace_bytes(int dtype, int64_t M, int D, size_t* bytes);
+int isc_bank_group_sums(const void* bank, int dtype, int64_t N, int D, const int64_t* rows, int64_t M,
+                        const int64_t* offsets, int64_t G, const uint32_t* fill_mask, double* sums, int64_t ld,
+                        int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
