@@ -162,6 +162,8 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
         [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int64, c_int, c_void_p],
     ),
     "isc_attention_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "isc_attention_f16_stream": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "isc_attention_stream_geometry": (c_int, [POINTER(c_int), POINTER(c_int)]),
     "isc_patchify_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "isc_vit_assemble": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "isc_vit_pos_resample": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

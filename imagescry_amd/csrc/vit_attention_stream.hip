@@ -1,0 +1,239 @@
+// Multi-head self-attention for sequences of any length (head size 64): isc_attention_f16_stream.  The keys and values
+// are STREAMED through LDS in chunks and the softmax is kept online (running maximum and sum per query, flash style),
+// so neither a head's keys nor a query's score row has to fit anywhere.  isc_attention_f16 (vit.hip) holds both whole
+// and stops at T = 224; this kernel is what vit._encode calls above that.  Operands, layouts and the result are
+// those of isc_attention_f16.
+//
+// A workgroup of eight waves owns (image, head, block of AS_QB = 128 queries), a wave 16 of those queries, and all
+// eight walk the keys in chunks of AS_KC = 64:
+//   S^T[key][query] = K . Q^T / 8      4 key blocks x 2 MFMAs (mfma_f32_16x16x32_f16); a lane holds ONE query (lane & 15)
+//                                       and 4 keys of every 16-key block -- the lane mapping of att_query_block
+//   m' = max(m, chunk maximum), alpha = exp2((m - m') log2 e)          float32; the first chunk has no rescale, so
+//   p  = exp2(fma(s, log2 e, -m' log2 e))                              -inf - (-inf) never occurs
+//   l  = l alpha + sum p               per LANE (a query's four lanes see the same alpha); the lanes are added once, at
+//                                       the end
+//   O^T[d][query] = O^T alpha + V^T . P^T    the SAME alpha value as l; P rounded to fp16 stays in registers as the
+//                                       P^T operand (slot (g, j) <-> key 32 ks + 4 g + j / 32 ks + 16 + 4 g + (j - 4)),
+//                                       V stays row-major in LDS and is read transposed (ds_read_b64_tr_b16)
+// The chunks are double-buffered and register-staged: the global loads of chunk c + 1 are issued before the arithmetic
+// of chunk c and written to the other LDS buffer behind it, one barrier per chunk.  Key rows at or past T are staged
+// as zeros (they may not exist -- row-major -- or hold anything -- packed padding) and their scores set to -inf behind
+// the MFMA: 0 probability times 0 value.  Only the last chunk can hold such keys, and only it pays for the masks
+// (as_chunk<true>), where it also skips the 16-key blocks that lie wholly past T.
+//
+// Workgroups of one (image, head) re-read the same keys and values, so they are placed on ONE XCD (workgroup i runs
+// on XCD i % 8): the heads are dealt to the XCDs round robin and the query blocks of a head follow each other there.
+#include "isc_common.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+typedef short tr4 __attribute__((__vector_size__(4 * sizeof(short))));  // what ds_read_b64_tr_b16 returns
+typedef short tr8 __attribute__((__vector_size__(8 * sizeof(short))));
+
+constexpr int AS_QB = 128;      // queries per workgroup (16 per wave)
+constexpr int AS_KC = 64;       // keys per chunk; a multiple of 32 (the P V slot mapping pairs keys in 32s)
+constexpr int AS_THREADS = 512;
+constexpr int AS_STRIDE = 72;   // halves per staged key / value row (64 + 8 pad, as in vit.hip)
+constexpr int AS_NKB = AS_KC / 16;
+constexpr int AS_XCDS = 8;
+static_assert(AS_KC % 32 == 0 && AS_QB == AS_THREADS / 64 * 16 && AS_KC * 8 == AS_THREADS, "geometry");
+
+// element (row, col) of a packed matrix of `cols` columns (the layout of include/imagescry_hip.h, pk_offset of vit.hip)
+__device__ __forceinline__ size_t as_pk_offset(long long row, int col, int cols) {
+    return (((size_t)(row >> 8) * (size_t)(cols >> 6) + (size_t)(col >> 6)) * 256 + (size_t)(row & 255)) * 64 + (size_t)(col & 63);
+}
+
+// One chunk of AS_KC staged keys / values against a wave's 16 queries.  qf: the lane's two query fragments, scaled by
+// 1/8; left = T - (first key of the chunk) > 0, only looked at when TAIL (left < AS_KC); first: chunk 0, no rescale.
+template <bool TAIL>
+__device__ __forceinline__ void as_chunk(const _Float16* __restrict__ Ks, const _Float16* __restrict__ Vs,
+                                         const half8 (&qf)[2], int left, bool first, int qi, int g, float& m, float& l,
+                                         f32x4 (&o)[4]) {
+    constexpr float LOG2E = 1.4426950408889634f;
+    f32x4 s[AS_NKB];
+#pragma unroll
+    for (int kb = 0; kb < AS_NKB; ++kb) {
+        f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (!TAIL || kb * 16 < left) {  // (wave-uniform) a block wholly past T is not computed
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                const half8 kf = *reinterpret_cast<const half8*>(&Ks[(kb * 16 + qi) * AS_STRIDE + (kk * 4 + g) * 8]);
+                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[kk], a, 0, 0, 0);
+            }
+        }
+        if (TAIL) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (kb * 16 + g * 4 + r >= left) a[r] = -INFINITY;
+        }
+        s[kb] = a;
+    }
+    float cm = -INFINITY;
+#pragma unroll
+    for (int kb = 0; kb < AS_NKB; ++kb) cm = fmaxf(cm, fmaxf(fmaxf(s[kb][0], s[kb][1]), fmaxf(s[kb][2], s[kb][3])));
+    cm = fmaxf(cm, __shfl_xor(cm, 16, 64));
+    cm = fmaxf(cm, __shfl_xor(cm, 32, 64));  // finite: every chunk holds at least one key below T
+    if (first) {
+        m = cm;
+    } else {
+        const float mn = fmaxf(m, cm);
+        const float alpha = __builtin_amdgcn_exp2f((m - mn) * LOG2E);  // <= 1; ONE value for l and O
+        m = mn;
+        l *= alpha;
+#pragma unroll
+        for (int db = 0; db < 4; ++db) o[db] *= alpha;
+    }
+    const float mxl = -m * LOG2E;
+#pragma unroll
+    for (int kb = 0; kb < AS_NKB; ++kb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float e = __builtin_amdgcn_exp2f(fmaf(s[kb][r], LOG2E, mxl));  // masked keys: exp2(-inf) = 0
+            s[kb][r] = e;
+            l += e;
+        }
+#pragma unroll
+    for (int ks = 0; ks < AS_NKB / 2; ++ks) {
+        if (TAIL && ks * 32 >= left) break;  // (wave-uniform) every probability of this step is 0
+        half8 pf;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            pf[r] = (_Float16)s[2 * ks][r];
+            pf[4 + r] = (_Float16)s[2 * ks + 1][r];
+        }
+#pragma unroll
+        for (int db = 0; db < 4; ++db) {
+            // V^T fragment: slot j of lane group g is key 32 ks + 4 g + j (j < 4) / 32 ks + 16 + 4 g + (j - 4), of value
+            // column 16 db + qi; lane 4 q + p of a 16-lane group supplies the address of row q, columns 4 p .. 4 p + 3
+            // (EXEC is all ones here: the branches around this code are wave-uniform).
+            const _Float16* vb = &Vs[(ks * 32 + g * 4 + (qi >> 2)) * AS_STRIDE + db * 16 + (qi & 3) * 4];
+            const tr4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr4*)vb);
+            const tr4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr4*)(vb + 16 * AS_STRIDE));
+            const half8 vf = __builtin_bit_cast(half8, tr8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
+            o[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf, o[db], 0, 0, 0);
+        }
+    }
+}
+
+// pairs = B * heads, nqb = query blocks per pair; the grid is ceil(pairs / 8) * 8 * nqb workgroups
+template <bool PACKED>
+__global__ __launch_bounds__(AS_THREADS) void k_attention_f16_stream(const _Float16* __restrict__ qkv, int T, int heads,
+                                                                       int pairs, int nqb, _Float16* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) _Float16 Kb[2][AS_KC * AS_STRIDE];
+    __shared__ __attribute__((aligned(16))) _Float16 Vb[2][AS_KC * AS_STRIDE];
+    // workgroup -> (pair, query block): XCD blockIdx.x % 8 takes the pairs xcd, xcd + 8, ..., a pair's blocks in a row
+    const int xcd = blockIdx.x % AS_XCDS;
+    const int slot = blockIdx.x / AS_XCDS;
+    const int pair = (slot / nqb) * AS_XCDS + xcd;
+    if (pair >= pairs) return;  // the whole workgroup: no barrier is left behind
+    const int q0 = (slot % nqb) * AS_QB;
+    const int b = pair / heads;
+    const int h = pair - b * heads;
+    const int D = heads * 64;
+    const long long row0 = (long long)b * T;
+    const int tid = threadIdx.x;
+    // element address of (token t of this image, part 0/1/2 = q/k/v, 8-half chunk c of this head); 64-bit throughout
+    auto qkv_at = [&](int t, int part, int c) -> const _Float16* {
+        if (PACKED) return qkv + as_pk_offset(row0 + t, part * D + h * 64, 3 * D) + c * 8;
+        return qkv + (size_t)(row0 + t) * ((size_t)3 * D) + (size_t)(part * D + h * 64 + c * 8);
+    };
+
+    // staging: thread tid holds 16 bytes of key row tid >> 3 of the chunk and the same of the value row
+    const int st = tid >> 3, sc = tid & 7;
+    half8 kreg, vreg;
+    auto stage_load = [&](int k0) {
+        kreg = half8{0, 0, 0, 0, 0, 0, 0, 0};
+        vreg = kreg;
+        if (k0 + st < T) {  // rows at or past T are never read: they are staged as zeros
+            kreg = *reinterpret_cast<const half8*>(qkv_at(k0 + st, 1, sc));
+            vreg = *reinterpret_cast<const half8*>(qkv_at(k0 + st, 2, sc));
+        }
+    };
+    auto stage_store = [&](int buf) {
+        *reinterpret_cast<half8*>(&Kb[buf][st * AS_STRIDE + sc * 8]) = kreg;
+        *reinterpret_cast<half8*>(&Vb[buf][st * AS_STRIDE + sc * 8]) = vreg;
+    };
+
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int qi = lane & 15;
+    const int g = lane >> 4;
+    const int tq = q0 + wave * 16 + qi;
+    const bool active = q0 + wave * 16 < T;  // (wave-uniform) a wave without queries only stages
+    stage_load(0);
+    half8 qf[2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        qf[kk] = *reinterpret_cast<const half8*>(qkv_at(min(tq, T - 1), 0, kk * 4 + g));
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qf[kk][j] = qf[kk][j] * (_Float16)0.125f;  // 1/sqrt(64): exact scaling
+    }
+    stage_store(0);
+    __syncthreads();
+
+    float m = -INFINITY, l = 0.f;
+    f32x4 o[4];
+#pragma unroll
+    for (int db = 0; db < 4; ++db) o[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int chunks = (T + AS_KC - 1) / AS_KC;
+    for (int c = 0; c < chunks; ++c) {
+        const int k0 = c * AS_KC;
+        const bool more = c + 1 < chunks;
+        if (more) stage_load(k0 + AS_KC);  // in flight under this chunk's arithmetic
+        if (active) {
+            const int left = T - k0;
+            if (left >= AS_KC) as_chunk<false>(Kb[c & 1], Vb[c & 1], qf, left, c == 0, qi, g, m, l, o);
+            else as_chunk<true>(Kb[c & 1], Vb[c & 1], qf, left, c == 0, qi, g, m, l, o);
+        }
+        if (!more) break;
+        stage_store((c + 1) & 1);  // the buffer chunk c - 1 was read from: every wave is past that chunk's barrier
+        __syncthreads();
+    }
+    if (!active) return;
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    const float inv = 1.f / l;
+    if (tq < T) {  // rows behind the output and packed padding rows are not written
+        _Float16* orow = PACKED ? out + as_pk_offset(row0 + tq, h * 64, D) : out + (size_t)(row0 + tq) * (size_t)D + h * 64;
+#pragma unroll
+        for (int db = 0; db < 4; ++db) {
+            half4 hv;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) hv[r] = (_Float16)(o[db][r] * inv);
+            *reinterpret_cast<half4*>(orow + db * 16 + g * 4) = hv;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int isc_attention_stream_geometry(int* query_block, int* key_chunk) {
+    ISC_REQUIRE(query_block && key_chunk);
+    *query_block = AS_QB;
+    *key_chunk = AS_KC;
+    return ISC_OK;
+}
+
+extern "C" int isc_attention_f16_stream(const void* qkv, int B, int T, int heads, int head_dim, void* out, int packed,
+                                        void* stream) {
+    ISC_REQUIRE(qkv && out && B > 0 && T > 0 && heads > 0);
+    if (head_dim != 64) return ISC_ERR_UNSUPPORTED;
+    if (!isc_aligned(qkv, 16) || !isc_aligned(out, 16)) return ISC_ERR_ALIGNMENT;
+    if ((long long)B * T > 0x7fffffffLL || heads > 0x7fffffff / 192) return ISC_ERR_UNSUPPORTED;
+    const long long pairs = (long long)B * heads;
+    const int nqb = (T + AS_QB - 1) / AS_QB;
+    const long long grid = (pairs + AS_XCDS - 1) / AS_XCDS * AS_XCDS * nqb;
+    if (pairs > 0x7fffffffLL || grid > 0x7fffffffLL) return ISC_ERR_UNSUPPORTED;
+    if (packed)
+        hipLaunchKernelGGL(k_attention_f16_stream<true>, dim3((unsigned)grid), dim3(AS_THREADS), 0, isc_stream(stream),
+                           reinterpret_cast<const _Float16*>(qkv), T, heads, (int)pairs, nqb,
+                           reinterpret_cast<_Float16*>(out));
+    else
+        hipLaunchKernelGGL(k_attention_f16_stream<false>, dim3((unsigned)grid), dim3(AS_THREADS), 0, isc_stream(stream),
+                           reinterpret_cast<const _Float16*>(qkv), T, heads, (int)pairs, nqb,
+                           reinterpret_cast<_Float16*>(out));
+    return isc_launch_status();
+}

@@ -410,6 +410,11 @@ class ViTB16Embedder(EmbeddingModule):
     resized image.  `grid="aspect"` keeps the aspect ratio: a `[B, 3, H, W]` batch is resized to `(16 h, 16 w)` with
     `(h, w) = vit.token_grid(H, W, config.grid ** 2)` and the position embeddings are resampled bicubically to that
     grid (`vit.position_table`); `forward` then takes any `[B, 3, 16 h, 16 w]` with `h w <= config.grid ** 2`.
+
+    `max_patches` (with `grid="aspect"`, 1 .. `vit.MAX_PATCHES`) replaces `config.grid ** 2` in both places: 400 gives
+    a 20 x 20 map of a square image, 1024 a 32 x 32 one.  Sequences of more than 224 tokens run on the streaming
+    attention kernel (`isc_attention_f16_stream`) and in passes of fewer images (`vit.images_per_pass`).  A config whose
+    own grid is larger than 14 x 14 needs no `max_patches`.
     """
 
     def __init__(
@@ -421,6 +426,7 @@ class ViTB16Embedder(EmbeddingModule):
         max_images_per_pass: int = 1024,
         output: str = "cls",
         grid: str = "fixed",
+        max_patches: int | None = None,
     ) -> None:
         super().__init__()
         if max_images_per_pass <= 0:
@@ -429,13 +435,21 @@ class ViTB16Embedder(EmbeddingModule):
             raise ValueError(f'output must be "cls" or "patches", got {output!r}')
         if grid not in ("fixed", "aspect"):
             raise ValueError(f'grid must be "fixed" or "aspect", got {grid!r}')
+        if max_patches is not None:
+            if grid == "fixed":
+                raise ValueError('max_patches needs grid="aspect": a fixed grid is the config\'s')
+            if not 1 <= max_patches <= vit.MAX_PATCHES:
+                raise ValueError(f"max_patches must be in 1 .. {vit.MAX_PATCHES}, got {max_patches}")
         self.config = config
+        self.max_patches = max_patches
         self.max_images_per_pass = max_images_per_pass
         self.output = output
         self.grid = grid
         self.hparams = {"image_size": config.image_size, "patch_size": config.patch_size, "depth": config.depth}
         if (output, grid) != ("cls", "fixed"):
             self.hparams.update(output=output, grid=grid)
+        if max_patches is not None:
+            self.hparams.update(max_patches=max_patches)
         # the patch-token head applies F.normalize itself when predict_step asks for it (isc_vit_tokens_out)
         self._head_normalizes = output == "patches"
         sd = state_dict if state_dict is not None else vit.make_state_dict(config, seed=seed)
@@ -448,13 +462,18 @@ class ViTB16Embedder(EmbeddingModule):
     def embedding_dim(self) -> int:
         return self.config.dim
 
+    @property
+    def _patch_cap(self) -> int:
+        """The most patches an aspect grid may hold."""
+        return self.config.grid**2 if self.max_patches is None else self.max_patches
+
     def preprocess(self, images: Tensor) -> Tensor:
         if not isinstance(images, Tensor) or images.dtype != torch.uint8:
             raise TypeError("images must be a uint8 tensor")
         if images.ndim != 4:
             raise ValueError(f"images must have shape [B, C, H, W], got {tuple(images.shape)}")
         if self.grid == "aspect":
-            h, w = vit.token_grid(images.shape[-2], images.shape[-1], self.config.grid**2)
+            h, w = vit.token_grid(images.shape[-2], images.shape[-1], self._patch_cap)
             size = (h * self.config.patch_size, w * self.config.patch_size)
         else:
             size = (self.config.image_size, self.config.image_size)
@@ -470,8 +489,8 @@ class ViTB16Embedder(EmbeddingModule):
                 raise ValueError(f"x must have shape [B, 3, {s}, {s}], got {tuple(x.shape)}")
             return self.config.grid, self.config.grid
         ok = x.ndim == 4 and x.shape[1] == 3 and x.shape[2] > 0 and x.shape[3] > 0 and x.shape[2] % p == 0 and x.shape[3] % p == 0
-        if not ok or (x.shape[2] // p) * (x.shape[3] // p) > self.config.grid**2:
-            raise ValueError(f"x must have shape [B, 3, {p} h, {p} w] with h w <= {self.config.grid ** 2}, "
+        if not ok or (x.shape[2] // p) * (x.shape[3] // p) > self._patch_cap:
+            raise ValueError(f"x must have shape [B, 3, {p} h, {p} w] with h w <= {self._patch_cap}, "
                              f"got {tuple(x.shape)}")
         return x.shape[2] // p, x.shape[3] // p
 
@@ -487,17 +506,19 @@ class ViTB16Embedder(EmbeddingModule):
             raise ValueError(f"module is on {self.device} but the input is on {x.device}; call .to() first")
         x = x.contiguous()
         b = x.shape[0]
-        step = self.max_images_per_pass
+        step = vit.images_per_pass(grid[0] * grid[1] + 1, self.max_images_per_pass)
+        cap = self._patch_cap if self.grid == "aspect" else None
         if self.output == "patches":
             out = torch.empty((b, self.config.dim, *grid), dtype=torch.float32, device=x.device)
             with torch.cuda.device(x.device):
                 for b0 in range(0, b, step):
-                    vit.forward_tokens(self._net, x[b0 : b0 + step], grid, normalize=normalized, out=out[b0 : b0 + step])
+                    vit.forward_tokens(self._net, x[b0 : b0 + step], grid, normalize=normalized, out=out[b0 : b0 + step],
+                                       max_patches=cap)
             return out
         out = torch.empty((b, self.config.dim), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             for b0 in range(0, b, step):
-                out[b0 : b0 + step] = vit.forward_cls(self._net, x[b0 : b0 + step], grid)
+                out[b0 : b0 + step] = vit.forward_cls(self._net, x[b0 : b0 + step], grid, max_patches=cap)
         return out[:, :, None, None]
 
     def predict_step(self, batch: ImageBatch) -> EmbeddingBatch:

@@ -41,6 +41,18 @@ class ViTConfig:
 
 
 VIT_B16 = ViTConfig()
+MAX_PATCHES = 4096  # the largest token grid an embedder may ask for: 64 x 64 patches, 1024 x 1024 pixels
+ONE_SHOT_TOKENS = 224  # isc_attention_f16 holds a head's keys whole up to here; longer sequences stream them
+PASS_ROWS = 1024 * 197  # token rows of the default configuration's largest pass (1024 images x 197 tokens)
+
+
+def images_per_pass(tokens: int, max_images: int) -> int:
+    """Images one pass of the encoder takes at `tokens` tokens an image: `max_images` on the native grids (up to 224
+    tokens), above that as many as keep a pass within the 1024 x 197 token rows the default configuration sends, at
+    least one."""
+    if tokens <= ONE_SHOT_TOKENS:
+        return max_images
+    return max(1, min(max_images, PASS_ROWS // tokens))
 
 
 def token_grid(height: int, width: int, max_patches: int = VIT_B16.grid**2) -> tuple[int, int]:
@@ -282,8 +294,12 @@ def _encode(net: PreparedViT, x: Tensor, grid: tuple[int, int]) -> Tensor:
     for blk in net.blocks:
         _layernorm_packed(xa, m, blk.norm1, cfg.ln_eps, hbuf, stream)
         _gemm(hbuf, m, blk.qkv, qkv, stream=stream)
-        _lib.check(lib.isc_attention_f16(qkv.data_ptr(), b, t, cfg.heads, d // cfg.heads, att.data_ptr(), 1, stream),
-                   "isc_attention_f16")
+        if t <= ONE_SHOT_TOKENS:
+            _lib.check(lib.isc_attention_f16(qkv.data_ptr(), b, t, cfg.heads, d // cfg.heads, att.data_ptr(), 1, stream),
+                       "isc_attention_f16")
+        else:  # the keys of a head no longer fit in LDS: the streaming kernel
+            _lib.check(lib.isc_attention_f16_stream(qkv.data_ptr(), b, t, cfg.heads, d // cfg.heads, att.data_ptr(), 1,
+                                                    stream), "isc_attention_f16_stream")
         _gemm(att, m, blk.proj, xb, residual=xa, stream=stream)
         _layernorm_packed(xb, m, blk.norm2, cfg.ln_eps, hbuf, stream)
         _gemm(hbuf, m, blk.fc1, mlp, act=_lib.ISC_ACT_GELU, stream=stream)
@@ -291,21 +307,24 @@ def _encode(net: PreparedViT, x: Tensor, grid: tuple[int, int]) -> Tensor:
     return xa
 
 
-def _check_grid(net: PreparedViT, x: Tensor, grid: tuple[int, int]) -> None:
+def _check_grid(net: PreparedViT, x: Tensor, grid: tuple[int, int], max_patches: int | None = None) -> None:
     h, w = grid
     p = net.cfg.patch_size
-    if h < 1 or w < 1 or h * w > net.cfg.grid**2:
-        raise ValueError(f"a token grid holds 1 .. {net.cfg.grid ** 2} patches, got {h} x {w}")
+    top = net.cfg.grid**2 if max_patches is None else max_patches
+    if h < 1 or w < 1 or h * w > top:
+        raise ValueError(f"a token grid holds 1 .. {top} patches, got {h} x {w}")
     if x.ndim != 4 or tuple(x.shape[1:]) != (3, h * p, w * p):
         raise ValueError(f"x must have shape [B, 3, {h * p}, {w * p}] for a {h} x {w} grid, got {tuple(x.shape)}")
 
 
-def forward_cls(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = None) -> Tensor:
+def forward_cls(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = None,
+                max_patches: int | None = None) -> Tensor:
     """float32 `[B, 3, P h, P w]` (already preprocessed; `grid = (h, w)`, the native square grid by default) on a HIP
-    device -> float32 `[B, D]` class-token features."""
+    device -> float32 `[B, D]` class-token features.  `max_patches`: the most patches `grid` may hold, the native
+    grid's count by default."""
     cfg = net.cfg
     grid = (cfg.grid, cfg.grid) if grid is None else grid
-    _check_grid(net, x, grid)
+    _check_grid(net, x, grid, max_patches)
     b, d, t = x.shape[0], cfg.dim, grid[0] * grid[1] + 1
     xa = _encode(net, x, grid)
     out = torch.empty((b, d), dtype=torch.float32, device=x.device)
@@ -317,14 +336,15 @@ def forward_cls(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = None
 
 
 def forward_tokens(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = None, normalize: bool = False,
-                   out: Tensor | None = None) -> Tensor:
+                   out: Tensor | None = None, max_patches: int | None = None) -> Tensor:
     """float32 `[B, 3, P h, P w]` -> the float32 patch-token map `[B, D, h, w]`: cell `(i, j)` is token `1 + i w + j`
     after the final LayerNorm, L2-normalised per cell (`F.normalize`, eps 1e-12) when `normalize` -- LayerNorm,
     normalisation and the transposition into the channels-first map are one kernel (`isc_vit_tokens_out`).  `out`: a
-    contiguous `[B, D, h, w]` tensor to write into."""
+    contiguous `[B, D, h, w]` tensor to write into.  `max_patches`: the most patches `grid` may hold, the native grid's
+    count by default."""
     cfg = net.cfg
     grid = (cfg.grid, cfg.grid) if grid is None else grid
-    _check_grid(net, x, grid)
+    _check_grid(net, x, grid, max_patches)
     h, w = grid
     b, d, t = x.shape[0], cfg.dim, h * w + 1
     if out is None:
@@ -338,5 +358,5 @@ def forward_tokens(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = N
     return out
 
 
-__all__ = ["VIT_B16", "ViTConfig", "forward_cls", "forward_tokens", "gemm_flops", "make_state_dict", "pack_rows",
-           "position_table", "prepare", "token_grid", "unpack_rows"]
+__all__ = ["MAX_PATCHES", "VIT_B16", "ViTConfig", "forward_cls", "forward_tokens", "gemm_flops", "images_per_pass",
+           "make_state_dict", "pack_rows", "position_table", "prepare", "token_grid", "unpack_rows"]

@@ -370,6 +370,17 @@ int isc_layernorm(const float* x, int64_t rows, int D, int64_t ldx, const float*
  * both row-major (packed == 0) or both packed.  head_dim == 64, T <= 224. */
 int isc_attention_f16(const void* qkv, int B, int T, int heads, int head_dim, void* out, int packed, void* stream);
 
+/* The same product for ANY T >= 1 (B * T < 2^31): the keys are streamed in chunks under an online softmax (running
+ * maximum and sum per query, float32), so the result agrees with isc_attention_f16 to rounding, not bit for bit.
+ * Same operands, layouts and alignment; head_dim == 64.  No workspace, no host synchronisation, capturable.  Slower
+ * than isc_attention_f16 where that one applies (T <= 224). */
+int isc_attention_f16_stream(const void* qkv, int B, int T, int heads, int head_dim, void* out, int packed,
+                             void* stream);
+
+/* The two constants of isc_attention_f16_stream: a workgroup owns `query_block` queries of one (image, head) and walks
+ * the keys in chunks of `key_chunk` (a multiple of 32) -- the sequence lengths at which its code paths change. */
+int isc_attention_stream_geometry(int* query_block, int* key_chunk);
+
 /* non-overlapping patches of an NCHW float32 image batch as fp16 GEMM rows (row-major or packed):
  * patches[(b, ph, pw)][c * P * P + r * P + s] = x[b][c][ph * P + r][pw * P + s]   (torch Conv2d(kernel=stride=P) weight
  * order).  P % 8 == 0, H % P == 0, W % P == 0. */
