@@ -273,6 +273,17 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
         [c_void_p, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
          c_void_p, c_size_t, c_void_p],
     ),
+    "isc_bank_gram_chunk_rows": (c_int, []),
+    "isc_bank_gram_workspace_bytes": (c_int, [c_int, c_int64, c_int, POINTER(c_size_t)]),
+    "isc_bank_gram": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "isc_bank_project": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+         c_int, c_float, c_void_p, c_void_p],
+    ),
 }
 
 _lib: ctypes.CDLL | None = None

@@ -7,6 +7,8 @@ symmetric eigenproblem, where the reference runs an SVD of the whole `[N, F]` ma
 `forward` -- the step the reference applies to every embedding batch right after the hot path
 (src/imagescry/models/pipelines.py:76-84) -- runs in the HIP kernel behind `isc_linear_centered`:
 `(x - feature_means) @ component_vectors` with the centring done before the product.
+`fit_bank` fits on the rows of an `EmbeddingBank` without unpacking it (`isc_bank_gram`), and `EmbeddingBank.project`
+compresses the bank the same way (`isc_bank_project`).
 
 `KMeans` clusters the rows of an `EmbeddingBank` by cosine similarity without unpacking it: every iteration is one
 `EmbeddingBank.assign` (labels only) and one `EmbeddingBank.group_sums`.
@@ -127,7 +129,12 @@ class PCA:
                                                     fpad, ldn, stream), "isc_center_transpose")
                 _lib.check(lib.isc_gram_rows(xt.data_ptr(), fpad, ldn, gram_chunk.data_ptr(), stream), "isc_gram_rows")
                 gram += gram_chunk.double()
-        g = gram[:f, :f].cpu()
+        return self._finish_fit(gram[:f, :f].cpu(), n, f, mean, dev)
+
+    def _finish_fit(self, g: Tensor, n: int, f: int, mean: Tensor, dev: torch.device) -> "PCA":
+        """The host tail of `fit` and `fit_bank`: `g` is the float64 `[F, F]` Gram matrix of the `n` centred samples (host),
+        `mean` the float32 `[F]` mean on `dev`.  Symmetrise, `eigh`, descending order, the sign convention, the float32
+        explained variance and the choice of the component count."""
         g = (g + g.T) * 0.5
         evals, evecs = torch.linalg.eigh(g)  # ascending; float64
         evals = torch.flip(evals, dims=(0,)).clamp_min(0.0)
@@ -157,6 +164,32 @@ class PCA:
         self._device = dev
         self._packed = None
         return self
+
+    def fit_bank(self, bank, *, mask=None) -> "PCA":
+        """`fit` on the live rows of an `EmbeddingBank` (those `mask` -- a `RowFilter` or bool `[N]` -- allows, when given)
+        without unpacking it: the rows are read from the packed image as stored (float16 or float32) and nothing row-sized
+        is allocated.  The mean comes from `bank.group_sums` with one group -- float64 sums in a fixed order, then
+        `(sums / n).float()` as in `fit` --, the centred Gram matrix from one `isc_bank_gram` (float32 partials per chunk of
+        packed rows on the f32 matrix cores, added in float64 in chunk order: the same bank gives the same bits), and the
+        host tail is `fit`'s.  `n` is the number of live, allowed rows (one host read); fewer than 2 raise ValueError, and
+        so does a sharded bank."""
+        if bank.process_group is not None:
+            raise ValueError("a sharded bank (process_group=) cannot be fitted: " + bank._ROWS_ON_ONE_RANK)
+        rf = bank._as_filter(mask)
+        rows, f = len(bank), bank.dim
+        dev = bank.device
+        if rows == 0:
+            raise ValueError("num_samples must be at least 2, got 0")
+        live = bank.live if rf is None or rf.packed is bank._fill else bank._unpack_mask(rf.packed, rows)
+        sums, counts = bank.group_sums(torch.where(live, 0, -1), 1)
+        n = int(counts[0])
+        if n < 2:
+            raise ValueError(f"num_samples must be at least 2, got {n} live rows")
+        mean = (sums[0] / n).float()  # what the reference subtracts: a float32 mean
+        gram = torch.zeros((f, f), dtype=torch.float64, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        bank._gram_rows(mean, rf, gram, count)
+        return self._finish_fit(gram.cpu(), n, f, mean, dev)
 
     # ------------------------------------------------------------------ device placement
     def to(self, device: str | torch.device) -> "PCA":

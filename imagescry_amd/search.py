@@ -1503,6 +1503,118 @@ class EmbeddingBank:
         self._group_sums(order.contiguous(), offsets.contiguous(), sums, counts)
         return sums, counts
 
+    # ------------------------------------------------------------------ PCA on the packed image
+    _gram_ws: Tensor | None = None  # the workspace of `_gram_rows`, grown on demand
+
+    def _gram_rows(self, mean: Tensor, mask: RowFilter | None, gram: Tensor, count: Tensor) -> None:
+        """`isc_bank_gram`: `gram` (float64 `[D, D]`, zeroed) receives the sum over the rows `mask` allows (None: the fill
+        bitmap, if the bank has one) of `(row - mean) (row - mean)^T` with `mean` float32 `[D]`, and `count` (int64 `[1]`,
+        zeroed) the number of those rows.  On the current stream, no host read.  A device hook."""
+        lib = _lib.load()
+        dev = self.device
+        code = _lib.dtype_code(self.dtype)
+        need = _lib.c_size_t()
+        _lib.check(lib.isc_bank_gram_workspace_bytes(code, self.capacity, self.dim, need), "isc_bank_gram_workspace_bytes")
+        if self._gram_ws is None or self._gram_ws.numel() < need.value:
+            self._gram_ws = None
+            self._gram_ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        ws = self._gram_ws
+        rm = _lib.ptr(mask.packed) if mask is not None else _lib.ptr(self._fill)
+        with torch.cuda.device(dev):
+            st = lib.isc_bank_gram(
+                self._bank.data_ptr(), code, self.capacity, self.dim, mean.data_ptr(), rm, gram.data_ptr(), gram.stride(0),
+                count.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_handle(dev),
+            )
+        _lib.check(st, "isc_bank_gram")
+
+    def _project_rows(self, mean: Tensor, w: Tensor, mask: RowFilter | None, out_rows: Tensor | None,
+                      out_bank: "EmbeddingBank | None") -> None:
+        """`isc_bank_project`: every row `mask` allows (None: the fill bitmap, if the bank has one) is projected once,
+        `(row - mean) @ w` with `mean` float32 `[D]` and `w` float32 `[D, K]`, and goes to `out_rows` (float32
+        `[capacity, K]`, zeros for the other rows) and / or into the packed image of `out_bank` (a K-wide bank laid out for
+        the same capacity, image zeroed) with `out_bank`'s dtype, `normalize` and norm bound.  One launch on the current
+        stream, no host read.  A device hook."""
+        dev = self.device
+        with torch.cuda.device(dev):
+            st = _lib.load().isc_bank_project(
+                self._bank.data_ptr(), _lib.dtype_code(self.dtype), self.capacity, self.dim, mean.data_ptr(), w.data_ptr(),
+                w.shape[1], w.stride(0), _lib.ptr(mask.packed) if mask is not None else _lib.ptr(self._fill),
+                _lib.ptr(out_rows), 0 if out_rows is None else out_rows.stride(0),
+                None if out_bank is None else out_bank._bank.data_ptr(),
+                _lib.dtype_code(self.dtype if out_bank is None else out_bank.dtype),
+                0 if out_bank is None else int(out_bank.normalize), 1e-12,
+                None if out_bank is None else out_bank._norm_bound.data_ptr(), _lib.stream_handle(dev),
+            )
+        _lib.check(st, "isc_bank_project")
+
+    def _pca_operands(self, pca: object, what: str) -> tuple[Tensor, Tensor]:
+        """(`feature_means` as float32 `[D]`, `component_vectors` as float32 `[D, K]`, unit inner stride) of a fitted PCA
+        on this bank's device whose `num_features` is the bank's `dim`; ValueError otherwise."""
+        self._refuse_sharded(what, self._ROWS_ON_ONE_RANK)
+        if not getattr(pca, "fitted", False):
+            raise ValueError("the PCA is not fitted")
+        if pca.num_features != self.dim:
+            raise ValueError(f"the PCA was fitted on {pca.num_features} features, the bank holds {self.dim}")
+        mean, w = pca.feature_means, pca.component_vectors
+        if mean.device != self.device or w.device != self.device:
+            raise ValueError(f"the PCA is on {w.device} but the bank is on {self.device}; call pca.to() first")
+        return mean.reshape(-1).float().contiguous(), w.float().contiguous()
+
+    def projected_rows(self, pca: object) -> Tensor:
+        """`pca.transform` of every stored row, float32 `[len, K]` in row order, read from the packed image
+        (`isc_bank_project`): no unpacked copy of the bank is made.  A removed row comes back as zeros.  The centred row is
+        formed in float32 from the stored value and multiplied on the f32 matrix cores.  `pca` is a fitted `PCA` on the
+        bank's device with `num_features == dim` (ValueError otherwise).  Runs on the caller's current stream with no host
+        read.  A sharded bank cannot project its rows."""
+        mean, w = self._pca_operands(pca, "project its rows")
+        n = self.num_local_rows
+        out = torch.zeros((self.capacity, w.shape[1]), dtype=torch.float32, device=self.device)
+        if n:
+            self._project_rows(mean, w, self._as_filter(None), out, None)
+        return out[:n]
+
+    def project(self, pca: object, *, dtype: torch.dtype | None = None, normalize: bool = True) -> "EmbeddingBank":
+        """The bank of the PCA-compressed rows: a new `EmbeddingBank` with `dim = pca.num_components` and `dtype` (default:
+        this bank's) whose row i is `pca.transform` of this bank's row i, stored as `EmbeddingBank(rows, dtype=...,
+        normalize=...)` would store it -- bit for bit: the projection kernel ends in the pack kernels' row function.  One
+        launch reads the packed rows and writes the packed image of the new bank (`isc_bank_project`); neither an `[N, D]`
+        nor an `[N, K]` row-major tensor exists at any time.
+
+        The new bank has the same `len`, capacity, fill bitmap (a copy: removed rows stay removed, `num_removed` is kept),
+        `row_origin`, row groups and `index_base` 0, so an index means the same row in both banks and every call works on
+        it: `search`, `search_groups`, `exclude_group=`, `similarity_map`, `append`, `remove`, ...  Runs on the caller's
+        current stream, behind everything this bank has issued on its own streams.  `pca`: as in `projected_rows`.  A
+        sharded bank cannot be projected."""
+        mean, w = self._pca_operands(pca, "be projected")
+        dtype = self.dtype if dtype is None else dtype
+        if dtype not in (torch.float16, torch.float32):
+            raise ValueError(f"bank dtype must be float16 or float32, got {dtype}")
+        k = w.shape[1]
+        n = self.num_local_rows
+        empty = torch.empty((0, k), dtype=torch.float32, device=self.device)
+        if self.capacity == 0:
+            return type(self)(empty, dtype=dtype, normalize=normalize, shadow=self.shadow)
+        self._wait_for_issued()
+        out = type(self)(empty, dtype=dtype, normalize=normalize, capacity=self.capacity, shadow=self.shadow)
+        out.num_local_rows = n
+        out._num_removed = self._num_removed
+        if self._fill is None:  # nothing reserved, nothing removed: the new bank is searched without a mask too
+            out._capacity = out._fill = out._fill_filter = None
+        else:
+            out._capacity = self._capacity
+            out._fill = self._fill.clone()
+            out._fill_filter = RowFilter(out, out._fill, None)
+        if self.row_origin is not None:
+            out.row_origin = self.row_origin.clone()
+        if self.group_labels is not None:
+            out.group_labels = self.group_labels.clone()
+            out._row_codes = self._row_codes.clone()
+            out._group_counts = None if self._group_counts is None else self._group_counts.clone()
+            out._max_group_rows = self._max_group_rows
+        if n:
+            self._project_rows(mean, w, self._as_filter(None), None, out)
+        return out
+
     def similarity_map(self, queries: Tensor, image_id: int) -> Tensor:
         """The score of every query against every cell of one image, on a bank with `row_origin` (`from_database`):
         float32 `[Q, H, W]` with H = the image's largest h + 1 and W = its largest w + 1; cells the bank does not hold, or

@@ -696,6 +696,41 @@ int isc_bank_group_sums(const void* bank, int dtype, int64_t N, int D, const int
                         const int64_t* offsets, int64_t G, const uint32_t* fill_mask, double* sums, int64_t ld,
                         int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* PCA on a packed bank.  In both calls the centred row is a_r = float32(b_r) - mean: the stored value widened exactly, then
+ * one float32 subtraction; a row is LIVE iff its bit in row_mask is set -- the bank's fill bitmap or a packed row filter
+ * (isc_row_mask_pack), NULL: every row of [0, N) -- and a dead row is never dereferenced.  The products run on the f32
+ * matrix cores (v_mfma_f32_16x16x4_f32: a float32 fma chain).  No host synchronisation (capturable).  D <= 2048
+ * (ISC_ERR_UNSUPPORTED above).
+ *
+ * isc_bank_gram: gram[i][j] = sum over the live rows of a_r[i] * a_r[j] (double [D, ld], ld >= D) and count[0] = the number
+ * of live rows.  Every chunk of isc_bank_gram_chunk_rows() packed positions (live or dead; a multiple of 256, host only)
+ * leaves one float32 partial Gram in the workspace, summed in packed row order; a second kernel adds the partials in chunk
+ * order in float64.  No floating-point atomics: two calls on the same inputs give the same bits.  Only the upper triangle
+ * of 128 x 128 tiles is computed and gram[j][i] is a copy of gram[i][j]: the same bits.  A dead row contributes nothing --
+ * neither a padding row's zeros nor a removed row's old vector is centred.  N == 0 returns ISC_OK without a launch and
+ * writes nothing: the caller passes gram and count zeroed.
+ *   mean   device float [D]        gram   device double, 8-byte aligned        count   device int64_t [1]
+ * The workspace holds ceil(ceil(N / 256) * 256 / chunk) partials of Dpad * Dpad floats, Dpad = D rounded up to a multiple of
+ * 128, followed by one int64_t per chunk (the chunk's live rows) rounded up to 256 bytes; its contents on entry do not
+ * matter.
+ *
+ * isc_bank_project: p_r = a_r . w for every live row, w float [D, K] with leading dimension ldw >= K, K <= D, float32
+ * accumulation along the features.  The row is projected once and both outputs, of which at least one is required, come
+ * from that p_r:
+ *   out_rows     float [N, ldo], ldo >= K, or NULL: p_r at ORIGINAL row r; a dead row of [0, N) is written as K zeros
+ *   out_packed   the image of a K-wide bank of out_dtype laid out for the same N, or NULL.  Packed position p of the source
+ *                is position p of the destination (the permutation depends on N only).  A live row holds exactly what
+ *                isc_bank_pack / isc_bank_append store for p_r -- their row function: normalize, eps, the rounding, the
+ *                atomic max into norm_bound (float [1], may be NULL) -- and a dead row is left as the caller filled it.
+ * No workspace.  N == 0 returns ISC_OK without a launch. */
+int isc_bank_gram_chunk_rows(void);
+int isc_bank_gram_workspace_bytes(int dtype, int64_t N, int D, size_t* bytes);
+int isc_bank_gram(const void* bank, int dtype, int64_t N, int D, const float* mean, const uint32_t* row_mask, double* gram,
+                  int64_t ld, int64_t* count, void* workspace, size_t workspace_bytes, void* stream);
+int isc_bank_project(const void* bank, int dtype, int64_t N, int D, const float* mean, const float* w, int K, int64_t ldw,
+                     const uint32_t* row_mask, float* out_rows, int64_t ldo, void* out_packed, int out_dtype, int normalize,
+                     float eps, float* norm_bound, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
