@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "isc_common.h"
+#include "packed_matrix.h"
 
 namespace {
 
@@ -86,11 +87,6 @@ __device__ __forceinline__ float gs_gelu(float v) {
     poly = fmaf(poly, t, 0.254829592f);
     const float e = 1.f - poly * t * __expf(-x * x);
     return 0.5f * v + 0.5f * fabsf(v) * e;
-}
-
-__device__ __forceinline__ size_t gs_pk_offset(long long row, int col, int cols) {
-    return (((size_t)(row >> 8) * (size_t)(cols >> 6) + (size_t)(col >> 6)) * 256 + (size_t)(row & 255)) * 64 +
-           (size_t)(col & 63);
 }
 
 // 16 row blocks x 8 MFMAs; the weight fragment (b_[n]) is the MFMA "A" operand, the token fragment (a_) the "B" operand
@@ -276,7 +272,7 @@ __global__ __launch_bounds__(GTHREADS) void k_gemm_f16_stream(const StreamGemmPa
             // stores are issued unconditionally; row-major output has no such rows
             if (p.out_packed || token < p.M) {
                 _Float16* dst = reinterpret_cast<_Float16*>(p.out) +
-                                (p.out_packed ? gs_pk_offset(token, nb, p.N) : (size_t)token * p.N + nb);
+                                (p.out_packed ? pk_offset(token, nb, p.N) : (size_t)token * p.N + nb);
                 if constexpr (DBG == 5) {  // timing aid: the same bytes, but every store instruction one contiguous KiB
                     const long long blk = ((token >> 4) * (p.N >> 6) + (nb >> 6)) * 2;
                     dst = reinterpret_cast<_Float16*>(p.out) + (blk * 64 + lane) * 8;

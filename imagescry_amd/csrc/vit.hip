@@ -7,14 +7,13 @@
 #include <stdlib.h>
 
 #include "isc_common.h"
+#include "packed_matrix.h"
+#include "vit_attention.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 // Direct global -> LDS copy (LDS-DMA): lane l of the wave writes 16 bytes at lds_wave_base + 16 * l.
 __device__ __forceinline__ void g2_dma16(const unsigned char* gsrc, unsigned char* lds_wave_base) {
@@ -51,18 +50,9 @@ struct GemmParams {
     void* out;
     long long M;
     int N, K, ksteps, act, out_f32;
-    int a_packed, w_packed, out_packed;  // operand / fp16 output in the K-step-major tile layout (see pk_offset)
+    int a_packed, w_packed, out_packed;  // operand / fp16 output in the K-step-major tile layout (pk_offset, packed_matrix.h)
 };
 
-// The PACKED fp16 matrix layout (the embedding bank's layout, bank_layout.h): rows in tiles of 256, columns in K steps of
-// 64 halves, stored [tile][K step][row][64 halves].  The 256 x 128 B block one K step of one tile needs is 32 KiB of
-// contiguous memory and every 1 KiB LDS-DMA instruction reads one contiguous KiB; a head's 64 q / k / v values of a token
-// are exactly one 128-byte segment, consecutive tokens 128 bytes apart, which is what the attention kernel reads.
-// (Measured on the ViT-B shapes: the GEMMs run at the same speed from row-major operands -- their cost is the
-// epilogue traffic and the staging volume, not the access pattern.)
-__host__ __device__ __forceinline__ size_t pk_offset(long long row, int col, int cols) {
-    return (((size_t)(row >> 8) * (size_t)(cols >> 6) + (size_t)(col >> 6)) * 256 + (size_t)(row & 255)) * 64 + (size_t)(col & 63);
-}
 // byte offset of the first K step of `row`, and the byte distance between consecutive K steps of a row
 __device__ __forceinline__ size_t operand_row_bytes(long long row, int K, int packed) {
     return packed ? pk_offset(row, 0, K) * 2 : (size_t)row * (size_t)K * 2;
@@ -562,21 +552,14 @@ void launch_layernorm(int nv, dim3 grid, hipStream_t s, const float* x, long lon
 // qkv [B, T, 3 * D] fp16 with D = heads * 64: query / key / value of head h at columns h*64, D + h*64, 2D + h*64.
 // out [B, T, D] fp16.
 //
-// Keys (row-major) and values (TRANSPOSED) of the head sit in LDS.  Each wave takes 16 queries at a time:
+// Keys and values of the head sit in LDS, both row-major.  Each wave takes 16 queries at a time (the pieces are those of
+// vit_attention.h, shared with the streaming kernel):
 //   S^T[key][query] = K . Q^T / 8      14 key blocks x 2 MFMAs; a lane then holds ONE query (lane & 15) and 56 keys
 //   softmax over keys                   registers + two cross-lane steps; statistics in float32
-//   O^T[d][query]  = V^T . P^T         the contraction runs over keys, and the order in which a lane's 8 k-slots map
-//                                       to keys is free as long as both operands agree: slot (g, j) <-> key
-//                                       32 ks + 4 g + j (j < 4) or 32 ks + 16 + 4 g + (j - 4).  With that mapping the
-//                                       P^T operand is exactly what the lane already holds after the softmax, so the
-//                                       probabilities never leave registers; the values stay row-major in LDS and the
-//                                       V^T fragments come out of two transposed reads (ds_read_b64_tr_b16) each.
+//   O^T[d][query]  = V^T . P^T         the probabilities never leave registers and the V^T fragments come out of
+//                                       transposed LDS reads: the slot mapping at att_pv_step
 constexpr int ATT_TMAX = 224;
-constexpr int ATT_KSTRIDE = 72;   // halves per key row (64 + 8 pad)
-constexpr int ATT_VSTRIDE = 72;   // halves per value row (row-major, like the keys; read transposed by ds_read_b64_tr_b16)
 constexpr int ATT_THREADS = 512;
-typedef short tr4 __attribute__((__vector_size__(4 * sizeof(short))));  // what ds_read_b64_tr_b16 returns: four 16-bit values
-typedef short tr8 __attribute__((__vector_size__(8 * sizeof(short))));
 
 // NKB = key blocks of 16 the kernel computes (T <= 16 NKB).  TAIL: T > 16 (NKB - 1), so only the LAST key block holds
 // keys past T and only it is masked -- the shape of every ViT launch (T = 197: NKB = 13, the fourteenth block, which is
@@ -589,21 +572,18 @@ typedef short tr8 __attribute__((__vector_size__(8 * sizeof(short))));
 // of ~390 (28 K-fragment reads, 26 + 28 MFMAs).
 // One block of 16 queries against the staged keys / values of a head: scores, softmax, P V, output row.  qf = this lane's two
 // query fragments, already scaled by 1/8; orow = where query tq's 64 outputs go (tq < T), qi / g = lane & 15 / lane >> 4.
+// Ks, Vs and orow are NOT __restrict__: k_attention_f16 calls this in a loop over query blocks, the K-fragment reads do
+// not depend on the block, and once the output stores provably cannot alias them all 28 reads are hoisted out of that
+// loop -- 201 - 227 VGPRs instead of 90 - 98, one workgroup per CU instead of the two its 63 KiB of LDS are sized for.
 template <int NKB, bool TAIL>
-__device__ __forceinline__ void att_query_block(const _Float16* __restrict__ Ks, const _Float16* __restrict__ Vs,
-                                                const half8 (&qf)[2], int T, int tq, int qi, int g,
-                                                _Float16* __restrict__ orow) {
+__device__ __forceinline__ void att_query_block(const _Float16* Ks, const _Float16* Vs, const half8 (&qf)[2], int T, int tq,
+                                                int qi, int g, _Float16* orow) {
     constexpr float LOG2E = 1.4426950408889634f;
     f32x4 s[NKB];
     float mx = -INFINITY;
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
-        f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const half8 kf = *reinterpret_cast<const half8*>(&Ks[(kb * 16 + qi) * ATT_KSTRIDE + (kk * 4 + g) * 8]);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[kk], a, 0, 0, 0);
-        }
+        f32x4 a = att_score_block(Ks, kb, qf, qi, g);
         if (!TAIL || kb == NKB - 1) {  // (compile-time) the block(s) that can hold keys past T
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -615,9 +595,14 @@ __device__ __forceinline__ void att_query_block(const _Float16* __restrict__ Ks,
     // The row maximum, v_max3_f32 by hand: through fmaxf the compiler first canonicalises every matrix-core result (one
     // v_max_f32 x, x each -- 52 more instructions per query block than the 26 maxima themselves).  hipcc pads no
     // hazards for an asm statement (cdna_hip_programming.md 5.7), and a vector instruction that reads a register a
-    // matrix-core instruction has just written needs its wait states: so the maxima run in ONE block behind the whole
-    // score loop, fenced from it by a scheduling barrier, and the block opens with those wait states itself (12 >= the 11
-    // an 8-pass MFMA result needs; the last MFMA's result is read by the mask code in between at the earliest).
+    // matrix-core instruction has just written needs its wait states.  The invariant this block rests on (the only
+    // hand-written asm of the attention kernels):
+    //   * EVERY score MFMA is issued before the scheduling barrier below: the maxima run in ONE block behind the whole
+    //     score loop, never interleaved with it;
+    //   * the block opens with 12 wait states (s_nop 7; s_nop 3) inside its first statement, against the 11 an 8-pass
+    //     MFMA result needs (the last MFMA's result is read by the mask code in between at the earliest);
+    //   * the later statements carry no nops of their own: they rely on statement order (asm volatile) plus the two
+    //     barriers, which keep any MFMA from being scheduled between or behind them.
     __builtin_amdgcn_sched_barrier(0);
     // six score blocks (twelve v_max3_f32) per statement: 25 register operands, under the limit of 30
 #define ISC_ATT_MAX6(k_, PRE_)                                                                                         \
@@ -664,35 +649,53 @@ asm volatile("v_max3_f32 %0, %0, %1, %2\n\tv_max3_f32 %0, %0, %3, %4"           
     for (int db = 0; db < 4; ++db) o[db] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < (NKB + 1) / 2; ++ks) {
-        half8 pf;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            pf[r] = (_Float16)s[2 * ks][r];
-            pf[4 + r] = 2 * ks + 1 < NKB ? (_Float16)s[2 * ks + 1 < NKB ? 2 * ks + 1 : 0][r] : (_Float16)0.f;
-        }
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-            // V^T fragment: slot j of lane group g is key 32 ks + 4 g + j (j < 4) / 32 ks + 16 + 4 g + (j - 4), of value
-            // column 16 db + qi.  One transposed read hands every lane of a 16-lane group ITS column of a 4-row block;
-            // lane 4 q + p of the group supplies the address of row q, columns 4 p .. 4 p + 3 (EXEC is all ones here).
-            const _Float16* vb = &Vs[(ks * 32 + g * 4 + (qi >> 2)) * ATT_VSTRIDE + db * 16 + (qi & 3) * 4];
-            const tr4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr4*)vb);
-            const tr4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr4*)(vb + 16 * ATT_VSTRIDE));
-            const half8 vf = __builtin_bit_cast(half8, tr8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
-            o[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf, o[db], 0, 0, 0);
-        }
+        // odd NKB: the upper half of the last step has no key block; its probabilities are zero (the value rows are staged)
+        att_pv_step(Vs, ks, s[2 * ks], 2 * ks + 1 < NKB ? s[2 * ks + 1 < NKB ? 2 * ks + 1 : 0] : f32x4{0.f, 0.f, 0.f, 0.f}, qi, g, o);
         __builtin_amdgcn_sched_barrier(0);
     }
-    if (tq < T) {
+    if (tq < T) att_store_row(orow, o, inv, g);
+}
+
+// Staging of a head's keys and values by a workgroup of THREADS threads: ALL of a thread's key / value chunks are requested
+// into registers before the first one is waited for (as a rolled loop the compiler waits for each pair of loads before it
+// issues the next: four dependent HBM round trips per workgroup), and stored to an LDS image later -- at once in
+// k_attention_f16, behind the previous head's arithmetic in k_attention_f16_p.
+template <int NKB, int THREADS>
+struct AttStaged {
+    static constexpr int TROWS = NKB * 16 < ATT_TMAX ? (NKB + (NKB & 1)) * 16 : ATT_TMAX;  // key rows staged (whole MFMA k-steps of 32)
+    static constexpr int ROUNDS = (TROWS * 8 + THREADS - 1) / THREADS;
+    half8 k[ROUNDS], v[ROUNDS];
+
+    // rows [row0, row0 + T) of head h; token rows at or past T are never read: they are staged as zeros
+    template <bool PACKED>
+    __device__ __forceinline__ void load(const _Float16* qkv, long long row0, int T, int D, int h, int tid) {
 #pragma unroll
-        for (int db = 0; db < 4; ++db) {
-            half4 hv;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) hv[r] = (_Float16)(o[db][r] * inv);
-            *reinterpret_cast<half4*>(orow + db * 16 + g * 4) = hv;
+        for (int r = 0; r < ROUNDS; ++r) {
+            const int i = tid + r * THREADS;
+            const int t = i >> 3, c = i & 7;
+            k[r] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+            v[r] = k[r];
+            if (t < T) {
+                k[r] = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row0 + t, D, h, 1, c));
+                v[r] = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row0 + t, D, h, 2, c));
+            }
         }
     }
-}
+    // Values stay ROW-major, one 16-byte LDS store per chunk like the keys: the transposition the V^T operand needs is done
+    // by the reads (ds_read_b64_tr_b16).  Round 3 scattered eight 2-byte stores per chunk into a transposed image -- with
+    // any 16-byte-aligned row stride all eight land in ONE bank (8 rows x stride = 0 mod 32 dwords).
+    __device__ __forceinline__ void store(_Float16* Ks, _Float16* Vs, int tid) const {
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r) {
+            const int i = tid + r * THREADS;
+            const int t = i >> 3, c = i & 7;
+            if (i < TROWS * 8) {
+                *reinterpret_cast<half8*>(&Ks[t * ATT_STRIDE + c * 8]) = k[r];
+                *reinterpret_cast<half8*>(&Vs[t * ATT_STRIDE + c * 8]) = v[r];
+            }
+        }
+    }
+};
 
 #ifdef ISC_ABLATION
 __device__ int g_att_abl = 0;  // ISC_ATT_ABL (timing aid, wrong results): 1 = stage keys / values only, 2 = no staging loads
@@ -701,53 +704,20 @@ template <bool PACKED, int NKB, bool TAIL>
 __global__ __launch_bounds__(ATT_THREADS) void k_attention_f16(const _Float16* __restrict__ qkv, int T, int heads,
                                                                 _Float16* __restrict__ out) {
     static_assert(NKB >= 1 && NKB <= ATT_TMAX / 16, "key blocks");
-    __shared__ __attribute__((aligned(16))) _Float16 Ks[ATT_TMAX * ATT_KSTRIDE];
-    __shared__ __attribute__((aligned(16))) _Float16 Vs[ATT_TMAX * ATT_VSTRIDE];
+    __shared__ __attribute__((aligned(16))) _Float16 Ks[ATT_TMAX * ATT_STRIDE];
+    __shared__ __attribute__((aligned(16))) _Float16 Vs[ATT_TMAX * ATT_STRIDE];
     const int b = blockIdx.x / heads;
     const int h = blockIdx.x - b * heads;
     const int D = heads * 64;
-    const size_t row_stride = (size_t)3 * D;
-    const _Float16* base = qkv + (size_t)b * T * row_stride + h * 64;
+    const long long row0 = (long long)b * T;
     const int tid = threadIdx.x;
-    // element address of (token t of this image, part 0/1/2 = q/k/v, 8-half chunk c of this head).  In the packed
-    // layout a head's 64 values are exactly one 128-byte K-step segment of the token's row.
-    auto qkv_at = [&](int t, int part, int c) -> const _Float16* {
-        if (PACKED) return qkv + pk_offset((long long)b * T + t, part * D + h * 64, 3 * D) + c * 8;
-        return base + (size_t)t * row_stride + part * D + c * 8;
-    };
-
-    constexpr int TROWS = NKB * 16 < ATT_TMAX ? (NKB + (NKB & 1)) * 16 : ATT_TMAX;  // key rows staged (whole MFMA k-steps of 32)
-    // staging: ALL of a thread's key / value chunks are requested before the first one is waited for (as a rolled loop the
-    // compiler waits for each pair of loads before it issues the next: four dependent HBM round trips per workgroup)
-    constexpr int SROUNDS = (TROWS * 8 + ATT_THREADS - 1) / ATT_THREADS;
-    half8 kreg[SROUNDS], vreg[SROUNDS];
-#pragma unroll
-    for (int r = 0; r < SROUNDS; ++r) {
-        const int i = tid + r * ATT_THREADS;
-        const int t = i >> 3, c = i & 7;
-        kreg[r] = half8{0, 0, 0, 0, 0, 0, 0, 0};
-        vreg[r] = kreg[r];
+    AttStaged<NKB, ATT_THREADS> staged;
 #ifdef ISC_ABLATION
-        if (t < T && !(g_att_abl & 2)) {
+    staged.template load<PACKED>(qkv, row0, (g_att_abl & 2) ? 0 : T, D, h, tid);
 #else
-        if (t < T) {
+    staged.template load<PACKED>(qkv, row0, T, D, h, tid);
 #endif
-            kreg[r] = *reinterpret_cast<const half8*>(qkv_at(t, 1, c));
-            vreg[r] = *reinterpret_cast<const half8*>(qkv_at(t, 2, c));
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < SROUNDS; ++r) {
-        const int i = tid + r * ATT_THREADS;
-        const int t = i >> 3, c = i & 7;
-        if (i < TROWS * 8) {
-            *reinterpret_cast<half8*>(&Ks[t * ATT_KSTRIDE + c * 8]) = kreg[r];
-            // values stay ROW-major, one 16-byte LDS store per chunk like the keys: the transposition the V^T operand needs
-            // is done by the reads (ds_read_b64_tr_b16).  Round 3 scattered eight 2-byte stores per chunk into a transposed
-            // image -- with any 16-byte-aligned row stride all eight land in ONE bank (8 rows x stride = 0 mod 32 dwords).
-            *reinterpret_cast<half8*>(&Vs[t * ATT_VSTRIDE + c * 8]) = vreg[r];
-        }
-    }
+    staged.store(Ks, Vs, tid);
     __syncthreads();
 #ifdef ISC_ABLATION
     if (g_att_abl & 1) return;
@@ -758,116 +728,13 @@ __global__ __launch_bounds__(ATT_THREADS) void k_attention_f16(const _Float16* _
     const int qi = lane & 15;
     const int g = lane >> 4;
     const int nqb = (T + 15) >> 4;
-    constexpr float LOG2E = 1.4426950408889634f;
     for (int qb = wave; qb < nqb; qb += ATT_THREADS / 64) {
         const int tq = qb * 16 + qi;
+        const long long row = row0 + min(tq, T - 1);
         half8 qf[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            qf[kk] = *reinterpret_cast<const half8*>(qkv_at(min(tq, T - 1), 0, kk * 4 + g));
-#pragma unroll
-            for (int j = 0; j < 8; ++j) qf[kk][j] = qf[kk][j] * (_Float16)0.125f;  // 1/sqrt(64): exact scaling
-        }
-        f32x4 s[NKB];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-            f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const half8 kf = *reinterpret_cast<const half8*>(&Ks[(kb * 16 + qi) * ATT_KSTRIDE + (kk * 4 + g) * 8]);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[kk], a, 0, 0, 0);
-            }
-            if (!TAIL || kb == NKB - 1) {  // (compile-time) the block(s) that can hold keys past T
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (kb * 16 + g * 4 + r >= T) a[r] = -INFINITY;
-            }
-            s[kb] = a;
-            __builtin_amdgcn_sched_barrier(0);  // keep the fragment loads of later key blocks from piling up in VGPRs
-        }
-        // The row maximum, v_max3_f32 by hand: through fmaxf the compiler first canonicalises every matrix-core result (one
-        // v_max_f32 x, x each -- 52 more instructions per query block than the 26 maxima themselves).  hipcc pads no
-        // hazards for an asm statement (cdna_hip_programming.md 5.7), and a vector instruction that reads a register a
-        // matrix-core instruction has just written needs its wait states: so the maxima run in ONE block behind the whole
-        // score loop, fenced from it by a scheduling barrier, and the block opens with those wait states itself (12 >= the 11
-        // an 8-pass MFMA result needs; the last MFMA's result is read by the mask code in between at the earliest).
-        __builtin_amdgcn_sched_barrier(0);
-        // six score blocks (twelve v_max3_f32) per statement: 25 register operands, under the limit of 30
-#define ISC_ATT_MAX6(k_, PRE_)                                                                                         \
-    asm volatile(PRE_ "v_max3_f32 %0, %0, %1, %2\n\tv_max3_f32 %0, %0, %3, %4\n\tv_max3_f32 %0, %0, %5, %6\n\t"         \
-                 "v_max3_f32 %0, %0, %7, %8\n\tv_max3_f32 %0, %0, %9, %10\n\tv_max3_f32 %0, %0, %11, %12\n\t"           \
-                 "v_max3_f32 %0, %0, %13, %14\n\tv_max3_f32 %0, %0, %15, %16\n\tv_max3_f32 %0, %0, %17, %18\n\t"        \
-                 "v_max3_f32 %0, %0, %19, %20\n\tv_max3_f32 %0, %0, %21, %22\n\tv_max3_f32 %0, %0, %23, %24"             \
-                 : "+v"(mx)                                                                                            \
-                 : "v"(s[k_][0]), "v"(s[k_][1]), "v"(s[k_][2]), "v"(s[k_][3]), "v"(s[k_ + 1][0]), "v"(s[k_ + 1][1]),   \
-                   "v"(s[k_ + 1][2]), "v"(s[k_ + 1][3]), "v"(s[k_ + 2][0]), "v"(s[k_ + 2][1]), "v"(s[k_ + 2][2]),      \
-                   "v"(s[k_ + 2][3]), "v"(s[k_ + 3][0]), "v"(s[k_ + 3][1]), "v"(s[k_ + 3][2]), "v"(s[k_ + 3][3]),      \
-                   "v"(s[k_ + 4][0]), "v"(s[k_ + 4][1]), "v"(s[k_ + 4][2]), "v"(s[k_ + 4][3]), "v"(s[k_ + 5][0]),      \
-                   "v"(s[k_ + 5][1]), "v"(s[k_ + 5][2]), "v"(s[k_ + 5][3]))
-#define ISC_ATT_MAX1(k_)                                                                  \
-    asm volatile("v_max3_f32 %0, %0, %1, %2\n\tv_max3_f32 %0, %0, %3, %4"                  \
-                 : "+v"(mx)                                                               \
-                 : "v"(s[k_][0]), "v"(s[k_][1]), "v"(s[k_][2]), "v"(s[k_][3]))
-        static_assert(NKB == 13 || NKB == 14, "the maxima are written out for thirteen or fourteen key blocks");
-        ISC_ATT_MAX6(0, "s_nop 7\n\ts_nop 3\n\t");  // the wait states of the matrix-core results, inside the statement
-        ISC_ATT_MAX6(6, "");
-        ISC_ATT_MAX1(12);
-        if constexpr (NKB == 14) ISC_ATT_MAX1(NKB - 1);
-#undef ISC_ATT_MAX6
-#undef ISC_ATT_MAX1
-        __builtin_amdgcn_sched_barrier(0);
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float mxl = -mx * LOG2E;  // T >= 1: every query has a finite maximum
-        float sum = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = __builtin_amdgcn_exp2f(fmaf(s[kb][r], LOG2E, mxl));  // masked keys: exp2(-inf) = 0
-                s[kb][r] = e;
-                sum += e;
-            }
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        const float inv = 1.f / sum;
-
-        f32x4 o[4];
-#pragma unroll
-        for (int db = 0; db < 4; ++db) o[db] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < (NKB + 1) / 2; ++ks) {
-            half8 pf;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                pf[r] = (_Float16)s[2 * ks][r];
-                pf[4 + r] = 2 * ks + 1 < NKB ? (_Float16)s[2 * ks + 1 < NKB ? 2 * ks + 1 : 0][r] : (_Float16)0.f;
-            }
-#pragma unroll
-            for (int db = 0; db < 4; ++db) {
-                // V^T fragment: slot j of lane group g is key 32 ks + 4 g + j (j < 4) / 32 ks + 16 + 4 g + (j - 4), of value
-                // column 16 db + qi.  One transposed read hands every lane of a 16-lane group ITS column of a 4-row block;
-                // lane 4 q + p of the group supplies the address of row q, columns 4 p .. 4 p + 3 (EXEC is all ones here).
-                const _Float16* vb = &Vs[(ks * 32 + g * 4 + (qi >> 2)) * ATT_VSTRIDE + db * 16 + (qi & 3) * 4];
-                const tr4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr4*)vb);
-                const tr4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr4*)(vb + 16 * ATT_VSTRIDE));
-                const half8 vf = __builtin_bit_cast(half8, tr8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
-                o[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf, o[db], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (tq < T) {
-            _Float16* orow = PACKED ? out + pk_offset((long long)b * T + tq, h * 64, D)
-                                    : out + ((size_t)b * T + tq) * D + h * 64;
-#pragma unroll
-            for (int db = 0; db < 4; ++db) {
-                half4 hv;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) hv[r] = (_Float16)(o[db][r] * inv);
-                *reinterpret_cast<half4*>(orow + db * 16 + g * 4) = hv;
-            }
-        }
+        att_load_query<PACKED>(qf, qkv, row, D, h, g);
+        att_scale_query(qf, qf);
+        att_query_block<NKB, TAIL>(Ks, Vs, qf, T, tq, qi, g, att_out_row<PACKED>(out, row, D, h));
     }
 }
 
@@ -875,18 +742,17 @@ __global__ __launch_bounds__(ATT_THREADS) void k_attention_f16(const _Float16* _
 // + gridDim.x, ...  A head's thirteen (fourteen) query blocks run as ONE round, a wave each, and the keys / values of
 // the NEXT head are requested into registers before that round starts and written into the other LDS image after it --
 // in k_attention_f16 a workgroup loads, then computes, and the second workgroup of the CU does not fill the gap: the
-// two phases add up (staging alone 49 us of a 178 us layer).  Same staging layout, same query-block
-// arithmetic (att_query_block), bit-identical results.
+// two phases add up (staging alone 49 us of a 178 us layer).  Same staging (AttStaged), same query-block
+// arithmetic (att_query_block): bit-identical results (tests/test_gpu_vit_exact.py).
 constexpr int ATT_P_THREADS = 1024;
-constexpr int ATT_P_LDS_BYTES = 2 * ATT_TMAX * (ATT_KSTRIDE + ATT_VSTRIDE) * 2;  // two (K, V) images: 126 KiB
+constexpr int ATT_P_LDS_BYTES = 2 * ATT_TMAX * 2 * ATT_STRIDE * 2;  // two (K, V) images: 126 KiB
 template <bool PACKED, int NKB, bool TAIL>
 __global__ __launch_bounds__(ATT_P_THREADS) void k_attention_f16_p(const _Float16* __restrict__ qkv, int T, int heads,
                                                                     _Float16* __restrict__ out, int total) {
     extern __shared__ __attribute__((aligned(16))) unsigned char att_lds[];
-    constexpr int IMG = ATT_TMAX * (ATT_KSTRIDE + ATT_VSTRIDE);  // halves per (K, V) image
+    constexpr int IMG = ATT_TMAX * 2 * ATT_STRIDE;  // halves per (K, V) image
     _Float16* const kv = reinterpret_cast<_Float16*>(att_lds);
     const int D = heads * 64;
-    const size_t row_stride = (size_t)3 * D;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -894,53 +760,20 @@ __global__ __launch_bounds__(ATT_P_THREADS) void k_attention_f16_p(const _Float1
     const int g = lane >> 4;
     const int nqb = (T + 15) >> 4;  // <= 14 waves have a query block
     const int tq = wave * 16 + qi;
-    auto qkv_at = [&](int b, int h, int t, int part, int c) -> const _Float16* {
-        if (PACKED) return qkv + pk_offset((long long)b * T + t, part * D + h * 64, 3 * D) + c * 8;
-        return qkv + ((size_t)b * T + t) * row_stride + part * D + h * 64 + c * 8;
-    };
-    constexpr int TROWS = NKB * 16 < ATT_TMAX ? (NKB + (NKB & 1)) * 16 : ATT_TMAX;
-    constexpr int SROUNDS = (TROWS * 8 + ATT_P_THREADS - 1) / ATT_P_THREADS;
-    half8 kreg[SROUNDS], vreg[SROUNDS], qn[2];
+    AttStaged<NKB, ATT_P_THREADS> staged;
+    half8 qn[2];
     auto load_item = [&](int item) {
         const int b = item / heads, h = item - b * heads;
-#pragma unroll
-        for (int r = 0; r < SROUNDS; ++r) {
-            const int i = tid + r * ATT_P_THREADS;
-            const int t = i >> 3, c = i & 7;
-            kreg[r] = half8{0, 0, 0, 0, 0, 0, 0, 0};
-            vreg[r] = kreg[r];
-            if (t < T) {
-                kreg[r] = *reinterpret_cast<const half8*>(qkv_at(b, h, t, 1, c));
-                vreg[r] = *reinterpret_cast<const half8*>(qkv_at(b, h, t, 2, c));
-            }
-        }
-        if (wave < nqb) {
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) qn[kk] = *reinterpret_cast<const half8*>(qkv_at(b, h, min(tq, T - 1), 0, kk * 4 + g));
-        }
+        staged.template load<PACKED>(qkv, (long long)b * T, T, D, h, tid);
+        if (wave < nqb) att_load_query<PACKED>(qn, qkv, (long long)b * T + min(tq, T - 1), D, h, g);
     };
-    auto store_item = [&](int buf) {
-        _Float16* Ks = kv + buf * IMG;
-        _Float16* Vs = Ks + ATT_TMAX * ATT_KSTRIDE;
-#pragma unroll
-        for (int r = 0; r < SROUNDS; ++r) {
-            const int i = tid + r * ATT_P_THREADS;
-            const int t = i >> 3, c = i & 7;
-            if (i < TROWS * 8) {
-                *reinterpret_cast<half8*>(&Ks[t * ATT_KSTRIDE + c * 8]) = kreg[r];
-                *reinterpret_cast<half8*>(&Vs[t * ATT_VSTRIDE + c * 8]) = vreg[r];
-            }
-        }
-    };
+    auto store_item = [&](int buf) { staged.store(kv + buf * IMG, kv + buf * IMG + ATT_TMAX * ATT_STRIDE, tid); };
     int item = blockIdx.x;
     if (item >= total) return;
     load_item(item);
     store_item(0);
     half8 qf[2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) qf[kk][j] = qn[kk][j] * (_Float16)0.125f;  // 1/sqrt(64): exact scaling
+    att_scale_query(qf, qn);
     __syncthreads();
     for (int it = 0;; ++it) {
         const int next = item + (int)gridDim.x;
@@ -949,16 +782,12 @@ __global__ __launch_bounds__(ATT_P_THREADS) void k_attention_f16_p(const _Float1
         if (wave < nqb) {
             const int b = item / heads, h = item - b * heads;
             const _Float16* Ks = kv + (it & 1) * IMG;
-            _Float16* orow = PACKED ? out + pk_offset((long long)b * T + min(tq, T - 1), h * 64, D)
-                                    : out + ((size_t)b * T + min(tq, T - 1)) * D + h * 64;
-            att_query_block<NKB, TAIL>(Ks, Ks + ATT_TMAX * ATT_KSTRIDE, qf, T, tq, qi, g, orow);
+            att_query_block<NKB, TAIL>(Ks, Ks + ATT_TMAX * ATT_STRIDE, qf, T, tq, qi, g,
+                                       att_out_row<PACKED>(out, (long long)b * T + min(tq, T - 1), D, h));
         }
         if (!more) break;
         store_item((it + 1) & 1);  // the image the PREVIOUS head was read from: every wave is past that round's barrier
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) qf[kk][j] = qn[kk][j] * (_Float16)0.125f;
+        att_scale_query(qf, qn);
         __syncthreads();
         item = next;
     }

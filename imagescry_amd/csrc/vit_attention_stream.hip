@@ -7,14 +7,15 @@
 // A workgroup of eight waves owns (image, head, block of AS_QB = 128 queries), a wave 16 of those queries, and all
 // eight walk the keys in chunks of AS_KC = 64:
 //   S^T[key][query] = K . Q^T / 8      4 key blocks x 2 MFMAs (mfma_f32_16x16x32_f16); a lane holds ONE query (lane & 15)
-//                                       and 4 keys of every 16-key block -- the lane mapping of att_query_block
+//                                       and 4 keys of every 16-key block (att_score_block, vit_attention.h, as every
+//                                       piece shared with isc_attention_f16)
 //   m' = max(m, chunk maximum), alpha = exp2((m - m') log2 e)          float32; the first chunk has no rescale, so
 //   p  = exp2(fma(s, log2 e, -m' log2 e))                              -inf - (-inf) never occurs
 //   l  = l alpha + sum p               per LANE (a query's four lanes see the same alpha); the lanes are added once, at
 //                                       the end
 //   O^T[d][query] = O^T alpha + V^T . P^T    the SAME alpha value as l; P rounded to fp16 stays in registers as the
-//                                       P^T operand (slot (g, j) <-> key 32 ks + 4 g + j / 32 ks + 16 + 4 g + (j - 4)),
-//                                       V stays row-major in LDS and is read transposed (ds_read_b64_tr_b16)
+//                                       P^T operand, V stays row-major in LDS and is read transposed (att_pv_step,
+//                                       which has the slot mapping)
 // The chunks are double-buffered and register-staged: the global loads of chunk c + 1 are issued before the arithmetic
 // of chunk c and written to the other LDS buffer behind it, one barrier per chunk.  Key rows at or past T are staged
 // as zeros (they may not exist -- row-major -- or hold anything -- packed padding) and their scores set to -inf behind
@@ -23,28 +24,16 @@
 //
 // Workgroups of one (image, head) re-read the same keys and values, so they are placed on ONE XCD (workgroup i runs
 // on XCD i % 8): the heads are dealt to the XCDs round robin and the query blocks of a head follow each other there.
-#include "isc_common.h"
+#include "vit_attention.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef short tr4 __attribute__((__vector_size__(4 * sizeof(short))));  // what ds_read_b64_tr_b16 returns
-typedef short tr8 __attribute__((__vector_size__(8 * sizeof(short))));
-
 constexpr int AS_QB = 128;      // queries per workgroup (16 per wave)
-constexpr int AS_KC = 64;       // keys per chunk; a multiple of 32 (the P V slot mapping pairs keys in 32s)
+constexpr int AS_KC = 64;       // keys per chunk; a multiple of 32 (att_pv_step pairs key blocks in 32s)
 constexpr int AS_THREADS = 512;
-constexpr int AS_STRIDE = 72;   // halves per staged key / value row (64 + 8 pad, as in vit.hip)
 constexpr int AS_NKB = AS_KC / 16;
 constexpr int AS_XCDS = 8;
 static_assert(AS_KC % 32 == 0 && AS_QB == AS_THREADS / 64 * 16 && AS_KC * 8 == AS_THREADS, "geometry");
-
-// element (row, col) of a packed matrix of `cols` columns (the layout of include/imagescry_hip.h, pk_offset of vit.hip)
-__device__ __forceinline__ size_t as_pk_offset(long long row, int col, int cols) {
-    return (((size_t)(row >> 8) * (size_t)(cols >> 6) + (size_t)(col >> 6)) * 256 + (size_t)(row & 255)) * 64 + (size_t)(col & 63);
-}
 
 // One chunk of AS_KC staged keys / values against a wave's 16 queries.  qf: the lane's two query fragments, scaled by
 // 1/8; left = T - (first key of the chunk) > 0, only looked at when TAIL (left < AS_KC); first: chunk 0, no rescale.
@@ -57,13 +46,7 @@ __device__ __forceinline__ void as_chunk(const _Float16* __restrict__ Ks, const 
 #pragma unroll
     for (int kb = 0; kb < AS_NKB; ++kb) {
         f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (!TAIL || kb * 16 < left) {  // (wave-uniform) a block wholly past T is not computed
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const half8 kf = *reinterpret_cast<const half8*>(&Ks[(kb * 16 + qi) * AS_STRIDE + (kk * 4 + g) * 8]);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[kk], a, 0, 0, 0);
-            }
-        }
+        if (!TAIL || kb * 16 < left) a = att_score_block(Ks, kb, qf, qi, g);  // (wave-uniform) a block wholly past T is not computed
         if (TAIL) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -98,23 +81,7 @@ __device__ __forceinline__ void as_chunk(const _Float16* __restrict__ Ks, const 
 #pragma unroll
     for (int ks = 0; ks < AS_NKB / 2; ++ks) {
         if (TAIL && ks * 32 >= left) break;  // (wave-uniform) every probability of this step is 0
-        half8 pf;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            pf[r] = (_Float16)s[2 * ks][r];
-            pf[4 + r] = (_Float16)s[2 * ks + 1][r];
-        }
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-            // V^T fragment: slot j of lane group g is key 32 ks + 4 g + j (j < 4) / 32 ks + 16 + 4 g + (j - 4), of value
-            // column 16 db + qi; lane 4 q + p of a 16-lane group supplies the address of row q, columns 4 p .. 4 p + 3
-            // (EXEC is all ones here: the branches around this code are wave-uniform).
-            const _Float16* vb = &Vs[(ks * 32 + g * 4 + (qi >> 2)) * AS_STRIDE + db * 16 + (qi & 3) * 4];
-            const tr4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr4*)vb);
-            const tr4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr4*)(vb + 16 * AS_STRIDE));
-            const half8 vf = __builtin_bit_cast(half8, tr8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
-            o[db] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf, o[db], 0, 0, 0);
-        }
+        att_pv_step(Vs, ks, s[2 * ks], s[2 * ks + 1], qi, g, o);
     }
 }
 
@@ -122,8 +89,8 @@ __device__ __forceinline__ void as_chunk(const _Float16* __restrict__ Ks, const 
 template <bool PACKED>
 __global__ __launch_bounds__(AS_THREADS) void k_attention_f16_stream(const _Float16* __restrict__ qkv, int T, int heads,
                                                                        int pairs, int nqb, _Float16* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) _Float16 Kb[2][AS_KC * AS_STRIDE];
-    __shared__ __attribute__((aligned(16))) _Float16 Vb[2][AS_KC * AS_STRIDE];
+    __shared__ __attribute__((aligned(16))) _Float16 Kb[2][AS_KC * ATT_STRIDE];
+    __shared__ __attribute__((aligned(16))) _Float16 Vb[2][AS_KC * ATT_STRIDE];
     // workgroup -> (pair, query block): XCD blockIdx.x % 8 takes the pairs xcd, xcd + 8, ..., a pair's blocks in a row
     const int xcd = blockIdx.x % AS_XCDS;
     const int slot = blockIdx.x / AS_XCDS;
@@ -135,11 +102,6 @@ __global__ __launch_bounds__(AS_THREADS) void k_attention_f16_stream(const _Floa
     const int D = heads * 64;
     const long long row0 = (long long)b * T;
     const int tid = threadIdx.x;
-    // element address of (token t of this image, part 0/1/2 = q/k/v, 8-half chunk c of this head); 64-bit throughout
-    auto qkv_at = [&](int t, int part, int c) -> const _Float16* {
-        if (PACKED) return qkv + as_pk_offset(row0 + t, part * D + h * 64, 3 * D) + c * 8;
-        return qkv + (size_t)(row0 + t) * ((size_t)3 * D) + (size_t)(part * D + h * 64 + c * 8);
-    };
 
     // staging: thread tid holds 16 bytes of key row tid >> 3 of the chunk and the same of the value row
     const int st = tid >> 3, sc = tid & 7;
@@ -148,13 +110,13 @@ __global__ __launch_bounds__(AS_THREADS) void k_attention_f16_stream(const _Floa
         kreg = half8{0, 0, 0, 0, 0, 0, 0, 0};
         vreg = kreg;
         if (k0 + st < T) {  // rows at or past T are never read: they are staged as zeros
-            kreg = *reinterpret_cast<const half8*>(qkv_at(k0 + st, 1, sc));
-            vreg = *reinterpret_cast<const half8*>(qkv_at(k0 + st, 2, sc));
+            kreg = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row0 + (k0 + st), D, h, 1, sc));
+            vreg = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row0 + (k0 + st), D, h, 2, sc));
         }
     };
     auto stage_store = [&](int buf) {
-        *reinterpret_cast<half8*>(&Kb[buf][st * AS_STRIDE + sc * 8]) = kreg;
-        *reinterpret_cast<half8*>(&Vb[buf][st * AS_STRIDE + sc * 8]) = vreg;
+        *reinterpret_cast<half8*>(&Kb[buf][st * ATT_STRIDE + sc * 8]) = kreg;
+        *reinterpret_cast<half8*>(&Vb[buf][st * ATT_STRIDE + sc * 8]) = vreg;
     };
 
     const int lane = tid & 63;
@@ -165,12 +127,8 @@ __global__ __launch_bounds__(AS_THREADS) void k_attention_f16_stream(const _Floa
     const bool active = q0 + wave * 16 < T;  // (wave-uniform) a wave without queries only stages
     stage_load(0);
     half8 qf[2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-        qf[kk] = *reinterpret_cast<const half8*>(qkv_at(min(tq, T - 1), 0, kk * 4 + g));
-#pragma unroll
-        for (int j = 0; j < 8; ++j) qf[kk][j] = qf[kk][j] * (_Float16)0.125f;  // 1/sqrt(64): exact scaling
-    }
+    att_load_query<PACKED>(qf, qkv, row0 + min(tq, T - 1), D, h, g);
+    att_scale_query(qf, qf);
     stage_store(0);
     __syncthreads();
 
@@ -196,16 +154,8 @@ __global__ __launch_bounds__(AS_THREADS) void k_attention_f16_stream(const _Floa
     l += __shfl_xor(l, 16, 64);
     l += __shfl_xor(l, 32, 64);
     const float inv = 1.f / l;
-    if (tq < T) {  // rows behind the output and packed padding rows are not written
-        _Float16* orow = PACKED ? out + as_pk_offset(row0 + tq, h * 64, D) : out + (size_t)(row0 + tq) * (size_t)D + h * 64;
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-            half4 hv;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) hv[r] = (_Float16)(o[db][r] * inv);
-            *reinterpret_cast<half4*>(orow + db * 16 + g * 4) = hv;
-        }
-    }
+    // rows behind the output and packed padding rows are not written
+    if (tq < T) att_store_row(att_out_row<PACKED>(out, row0 + tq, D, h), o, inv, g);
 }
 
 }  // namespace

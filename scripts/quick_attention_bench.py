@@ -1,4 +1,8 @@
-"""Bring-up timing of isc_attention_f16 at the ViT-B/16 batch-512 shape (not the contract bench)."""
+"""Bring-up timing of isc_attention_f16 at the ViT-B/16 shape (not the contract bench).
+
+    python scripts/quick_attention_bench.py [--batch 512]
+
+The default batch of 512 runs the persistent form; --batch 16 (192 pairs, at most one per CU) the one-shot form."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -7,7 +11,8 @@ from imagescry_amd.vit import packed_elems
 
 dev = torch.device("cuda:0")
 lib = _lib.load()
-b, t, heads, hd = 512, 197, 12, 64
+b = int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else 512
+t, heads, hd = 197, 12, 64
 d = heads * hd
 g = torch.Generator(device=dev).manual_seed(0)
 for packed in (1, 0):
@@ -27,4 +32,4 @@ for packed in (1, 0):
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) / it * 1e3
     fl = 4.0 * t * t * hd * b * heads
-    print(f"attention packed={packed}: {us:.1f} us  {fl / us / 1e6:.1f} TFLOP/s  abl={os.environ.get('ISC_ATT_ABL', '0')}", flush=True)
+    print(f"attention B={b} packed={packed}: {us:.1f} us  {fl / us / 1e6:.1f} TFLOP/s  abl={os.environ.get('ISC_ATT_ABL', '0')}", flush=True)

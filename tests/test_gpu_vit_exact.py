@@ -268,6 +268,18 @@ def test_attention_random_is_within_the_derived_bound(device, form, t, scale, pk
     _note(name, mb.assert_within_bound(got, want, bound, f"{name}, T = {t}"))
 
 
+@pytest.mark.parametrize("pk", [False, True], ids=["rowmajor", "packed"])
+@pytest.mark.parametrize("t", [17, 197, 209])  # the generic, the thirteen-block and the fourteen-block instantiation
+def test_attention_forms_agree_bit_for_bit(device, t, pk):
+    """k_attention_f16_p's header: same staging, same query-block arithmetic, bit-identical results.  The persistent
+    batch goes through the persistent form, its first two images alone (6 pairs <= CUs) through the one-shot form."""
+    qkv = vb.random_case(_images("persistent"), t, HEADS, 0.5, seed=4000 + t)
+    assert _images("one-shot") == 2
+    persistent = _run_attention(device, qkv, pk)
+    one_shot = _run_attention(device, qkv[:2].contiguous(), pk)
+    assert torch.equal(one_shot, persistent[:2])
+
+
 # =============================================================================================== isc_layernorm
 # NV = 16-byte vectors per lane = ceil(D / 256): D = 4, 252, 256 -> 1; 260, 512 -> 2; 516, 768 -> 3; 772, 1024 -> 4; 1028,
 # 2044, 2048 -> the NV = 8 instantiation.  D / 4 % 64 != 0 (4, 252, 260, 516, 772, 1028, 2044) leaves the last lane row
