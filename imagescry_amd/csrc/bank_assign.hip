@@ -33,10 +33,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int AS_PASS = ISC_SEARCH_PASS_QUERIES;
 constexpr int AS_LIST = 8;  // candidate slots of a row while its tile streams (LDS)
 constexpr int AS_KEEP = 4;  // candidates a row may hand to k_assign_finish
@@ -112,15 +108,15 @@ __global__ __launch_bounds__(256) void k_assign_norms(const TQ* __restrict__ cen
         }
         return;
     }
-    // the denominator of the exact score: the lane's elements lane, lane + 64, ... in order, then the wave (k_row_scores)
+    // the denominator of the exact score (exact_dots.h, step 3 of the staged form, on the unpadded centroid: the padding
+    // adds fma(0, 0, nacc) = nacc)
     const TQ* src = centroids + (int64_t)c * ldc;
     double nacc = 0.0;
     for (int e = lane; e < d; e += 64) {
         const double v = (double)(float)(T)src[e];
         nacc = fma(v, v, nacc);
     }
-    nacc = isc_wave_sum(nacc);
-    const double dn = fmax(sqrt(nacc), 1e-12);
+    const double dn = isc_norm_denom(nacc);
     // the trust range of the filter's bound (k_final: filter_trusted), on the norm of the packed row
     const unsigned char* qrow = cpacked + ((size_t)(c / tnc) * ks * tnc + (c % tnc)) * ISC_KSTEP_BYTES;
     const double qnorm = sqrt(wave_query_norm<T>(qrow, ks, tnc));
@@ -140,26 +136,6 @@ __device__ __forceinline__ float assign_margin(int dpad, const float* __restrict
 }
 
 // ---- the matrix-core filter -------------------------------------------------------------------------------------------
-template <typename T>
-struct AssignMma;
-template <>
-struct AssignMma<_Float16> {
-    // cent: centroid i = lane & 15 of the block, bank: bank row j = lane & 15; both the 16-byte chunk (lane >> 4) of the half
-    static __device__ __forceinline__ void step(const u32x4& cent, const u32x4& bank, f32x4& acc) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, cent), __builtin_bit_cast(half8, bank), acc, 0,
-                                                     0, 0);
-    }
-};
-template <>
-struct AssignMma<float> {
-    // element j of both lanes' chunks feeds the j-th v_mfma_f32_16x16x4_f32: the same permutation of K on both operands
-    static __device__ __forceinline__ void step(const u32x4& cent, const u32x4& bank, f32x4& acc) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(cent[j]), __uint_as_float(bank[j]), acc, 0, 0, 0);
-    }
-};
-
 // One workgroup = one 256-row bank tile; wave w owns its rows 64 w .. 64 w + 63 as four 16-row blocks and, per centroid
 // tile, NB 16-centroid blocks.  Every bank byte is used by exactly one wave, so the bank fragments go from global memory
 // straight to registers (a lane reads the 16-byte chunks fg and 4 + fg of its row's 128-byte K-step segment: the wave
@@ -224,7 +200,7 @@ __global__ __launch_bounds__(256) void k_assign_filter(const unsigned char* __re
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-                    for (int mb = 0; mb < 4; ++mb) AssignMma<T>::step(b[nb][h], a[mb][h], acc[nb][mb]);
+                    for (int mb = 0; mb < 4; ++mb) Mma<T>::step(b[nb][h], a[mb][h], acc[nb][mb]);
             if (s + 1 < ks) {
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb)
@@ -315,14 +291,10 @@ __global__ __launch_bounds__(256) void k_assign_filter(const unsigned char* __re
     }
 }
 
-__device__ __forceinline__ bool mask_bit(const uint32_t* __restrict__ m, int64_t p) {
-    return m == nullptr || ((m[p >> 5] >> (p & 31)) & 1u);
-}
-
 // ---- the exact finish -------------------------------------------------------------------------------------------------
-// 8 lanes per packed position (lane ch: 16-byte chunk ch of every K step, as k_row_scores holds a row).  The score of a
-// candidate is k_row_scores' arithmetic: the lane's fma chain over the K steps and the chunk's elements in order,
-// group8_sum, the division by the stored denominator, the cast.
+// 8 lanes per packed position (lane ch: 16-byte chunk ch of every K step, the staged form's mapping).  The score of a
+// candidate is the packed-row form of exact_dots.h summed by group8_sum and divided by the stored denominator: the staged
+// form's operations on the same values, hence k_row_scores' bits.
 template <typename T>
 __global__ __launch_bounds__(256) void k_assign_finish(
     const unsigned char* __restrict__ bank, int ks, IscPerm pm, const uint32_t* __restrict__ row_mask,
@@ -331,11 +303,10 @@ __global__ __launch_bounds__(256) void k_assign_finish(
     const int32_t* __restrict__ ncand, const int32_t* __restrict__ cand, const float* __restrict__ cand_f, int c_base,
     int first_pass, int want_scores, int32_t* __restrict__ out_labels, float* __restrict__ out_scores,
     unsigned char* __restrict__ redo, int32_t* __restrict__ status) {
-    constexpr int PER = Chunk16<T>::N;
     const int ch = threadIdx.x & 7;
     const int64_t p = (int64_t)blockIdx.x * AS_FIN_ROWS + (threadIdx.x >> 3);
     if (p >= pm.n) return;
-    const bool live = mask_bit(row_mask, p);
+    const bool live = isc_mask_allows(row_mask, p);
     const int64_t orig = isc_perm_orig(pm, p);
     const int nc = ncand[p];
     const bool need_redo = live && (nc < 0 || *untrusted != 0);
@@ -360,14 +331,9 @@ __global__ __launch_bounds__(256) void k_assign_finish(
         const int c = cand[p * AS_KEEP + i];
         const unsigned char* qsrc = cpacked + ((size_t)(c / tnc) * ks * tnc + (c % tnc)) * ISC_KSTEP_BYTES + ch * 16;
         double acc = 0.0;
-        for (int s = 0; s < ks; ++s) {
-            double a[8], q[8];
-            Chunk16<T>::load(bsrc + (size_t)s * ISC_TILE_KSTEP_BYTES, a);
-            Chunk16<T>::load(qsrc + (size_t)s * tnc * ISC_KSTEP_BYTES, q);
-#pragma unroll
-            for (int e = 0; e < PER; ++e) acc = fma(q[e], a[e], acc);
-        }
-        const float sc = (float)(group8_sum(acc) / denom[c]);
+        for (int s = 0; s < ks; ++s)
+            acc = isc_packed_dot<T>(qsrc + (size_t)s * tnc * ISC_KSTEP_BYTES, bsrc + (size_t)s * ISC_TILE_KSTEP_BYTES, acc);
+        const float sc = isc_exact_score(acc, denom[c]);
         const unsigned long long key = isc_make_key(sc, c + c_base);
         if (key > bkey) {
             bkey = key;
@@ -392,34 +358,28 @@ __global__ __launch_bounds__(256) void k_assign_finish(
 }
 
 // ---- the exhaustive float64 kernel ------------------------------------------------------------------------------------
-// k_row_scores turned round: a workgroup owns 64 consecutive PACKED positions (a wave 8 of them, lane l: row l >> 3, chunk
-// l & 7) and walks ALL centroids in groups of 8, staged 8 K steps at a time as float64 rounded to the bank type first; per
-// (centroid, row) the operations and their order are k_row_scores', so the scores have its bits.  Each row keeps the best
-// key (isc_make_key(score, centroid)) and that score's bits.  With `redo` only the listed rows are answered, and a
-// workgroup that holds none leaves at once.
-constexpr int AX_THREADS = 512;
-constexpr int AX_ROWS = 64;
-constexpr int AX_GC = 8;
-constexpr int AX_KC = 8;
+// The staged form of exact_dots.h over ALL centroids: a workgroup owns 64 consecutive PACKED positions (a wave 8 of them,
+// lane l: row l >> 3, chunk l & 7) and walks the centroids in groups of 8 (isc_staged_scores, the stage loop of
+// k_row_scores: the scores have its bits).  Each row keeps the best key (isc_make_key(score, centroid)) and that score's
+// bits.  With `redo` only the listed rows are answered, and a workgroup that holds none leaves at once.
+constexpr int AX_ROWS = ISC_ST_THREADS / 64 * 8;
 
 template <typename T>
-__global__ __launch_bounds__(AX_THREADS) void k_assign_exact(const unsigned char* __restrict__ bank, int ks, IscPerm pm,
-                                                             const uint32_t* __restrict__ row_mask,
-                                                             const void* __restrict__ centroids, int c_f32, int64_t ldc,
-                                                             int d, int nc, const unsigned char* __restrict__ redo,
-                                                             int32_t* __restrict__ out_labels,
-                                                             float* __restrict__ out_scores, int32_t* __restrict__ status) {
-    constexpr int EPK = ISC_KSTEP_BYTES / (int)sizeof(T);
-    constexpr int PER = Chunk16<T>::N;
-    constexpr int CE = AX_KC * EPK;
-    __shared__ __attribute__((aligned(16))) double qd[AX_GC * CE];
-    __shared__ double denom_sh[AX_GC];
+__global__ __launch_bounds__(ISC_ST_THREADS) void k_assign_exact(const unsigned char* __restrict__ bank, int ks, IscPerm pm,
+                                                                 const uint32_t* __restrict__ row_mask,
+                                                                 const void* __restrict__ centroids, int c_f32, int64_t ldc,
+                                                                 int d, int nc, const unsigned char* __restrict__ redo,
+                                                                 int32_t* __restrict__ out_labels,
+                                                                 float* __restrict__ out_scores,
+                                                                 int32_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) double qd[ISC_ST_GQ * isc_st_elems<T>()];
+    __shared__ double denom_sh[ISC_ST_GQ];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane >> 3, ch = lane & 7;
     const int64_t p = (int64_t)blockIdx.x * AX_ROWS + wave * 8 + sub;
     const bool inside = p < pm.n;
-    const bool live = inside && mask_bit(row_mask, p);
+    const bool live = inside && isc_mask_allows(row_mask, p);
     const bool need = live && (redo == nullptr || redo[p] != 0);
     const int64_t orig = inside ? isc_perm_orig(pm, p) : 0;
     if (redo == nullptr && inside && !live && ch == 0) {
@@ -431,54 +391,10 @@ __global__ __launch_bounds__(AX_THREADS) void k_assign_exact(const unsigned char
 
     unsigned long long bkey = 0;
     float bscore = 0.f;
-    for (int g0 = 0; g0 < nc; g0 += AX_GC) {
-        const int gn = min(AX_GC, nc - g0);
-        double acc[AX_GC];
-#pragma unroll
-        for (int g = 0; g < AX_GC; ++g) acc[g] = 0.0;
-        double nacc = 0.0;
-        for (int s0 = 0; s0 < ks; s0 += AX_KC) {
-            const int sn = min(AX_KC, ks - s0);
-            const int e0 = s0 * EPK, en = sn * EPK;
-            __syncthreads();  // the previous stage (and the previous group's denominators) have been read
-            for (int g = 0; g < AX_GC; ++g) {
-                const float* qp32 = static_cast<const float*>(centroids) + (int64_t)(g0 + g) * ldc;
-                const _Float16* qp16 = static_cast<const _Float16*>(centroids) + (int64_t)(g0 + g) * ldc;
-                for (int e = tid; e < en; e += AX_THREADS) {
-                    double v = 0.0;
-                    if (g < gn && e0 + e < d) v = (double)(float)(T)(c_f32 ? qp32[e0 + e] : (float)qp16[e0 + e]);
-                    qd[g * CE + e] = v;
-                }
-            }
-            __syncthreads();
-            if (wave < AX_GC)
-                for (int e = lane; e < en; e += 64) nacc = fma(qd[wave * CE + e], qd[wave * CE + e], nacc);
-            for (int s = 0; s < sn; ++s) {
-                double a[8];
-                if (need) {
-                    Chunk16<T>::load(src + (size_t)(s0 + s) * ISC_TILE_KSTEP_BYTES, a);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < PER; ++e) a[e] = 0.0;
-                }
-                const double* qs = qd + s * EPK + ch * PER;
-#pragma unroll
-                for (int e = 0; e < PER; ++e)
-#pragma unroll
-                    for (int g = 0; g < AX_GC; ++g) acc[g] = fma(qs[g * CE + e], a[e], acc[g]);
-            }
-        }
-        if (wave < AX_GC) {
-            nacc = isc_wave_sum(nacc);
-            if (lane == 0) denom_sh[wave] = fmax(sqrt(nacc), 1e-12);
-        }
-        __syncthreads();
-        float mine = 0.f;
-#pragma unroll
-        for (int g = 0; g < AX_GC; ++g) {
-            const float sc = (float)(group8_sum(acc[g]) / denom_sh[g]);
-            if (ch == g) mine = sc;
-        }
+    for (int g0 = 0; g0 < nc; g0 += ISC_ST_GQ) {
+        const int gn = min(ISC_ST_GQ, nc - g0);
+        // (its leading barrier: the previous group's denominators have been read)
+        const float mine = isc_staged_scores<T, true>(src, need, ks, centroids, c_f32, ldc, d, g0, gn, qd, denom_sh);
         // the group's best over the row's 8 lanes (lane ch holds centroid g0 + ch)
         unsigned long long key = ch < gn ? isc_make_key(mine, g0 + ch) : 0ull;
         unsigned long long gk = key;
@@ -664,7 +580,7 @@ int assign_run(const void* bank, int64_t n, int d, const void* centroids, int c,
                            bytes, ks, pm, row_mask, w.cpacked, tnc, w.denom, w.untrusted, norm_bound, dpad, w.ncand, w.cand,
                            w.cand_f, c0, pass == 0 ? 1 : 0, scores != nullptr ? 1 : 0, out_labels, scores, w.redo, status);
     }
-    hipLaunchKernelGGL(k_assign_exact<T>, dim3((unsigned)isc_ceil_div<int64_t>(n, AX_ROWS)), dim3(AX_THREADS), 0, stream,
+    hipLaunchKernelGGL(k_assign_exact<T>, dim3((unsigned)isc_ceil_div<int64_t>(n, AX_ROWS)), dim3(ISC_ST_THREADS), 0, stream,
                        bytes, ks, pm, row_mask, centroids, std::is_same<TQ, float>::value ? 1 : 0, ldc, d, c, w.redo,
                        out_labels, scores, status);
     return isc_launch_status();
@@ -732,10 +648,10 @@ extern "C" int isc_bank_assign_exhaustive(const void* bank, int dtype, int64_t N
     const int cf = c_dtype == ISC_F32 ? 1 : 0;
     hipLaunchKernelGGL(k_assign_status_zero, dim3(1), dim3(64), 0, s, status);
     if (dtype == ISC_F16)
-        hipLaunchKernelGGL(k_assign_exact<_Float16>, dim3(blocks), dim3(AX_THREADS), 0, s, bytes, isc_ksteps(D, 2), pm,
+        hipLaunchKernelGGL(k_assign_exact<_Float16>, dim3(blocks), dim3(ISC_ST_THREADS), 0, s, bytes, isc_ksteps(D, 2), pm,
                            row_mask, centroids, cf, ldc, D, C, nullptr, out_labels, out_scores, status);
     else
-        hipLaunchKernelGGL(k_assign_exact<float>, dim3(blocks), dim3(AX_THREADS), 0, s, bytes, isc_ksteps(D, 4), pm,
+        hipLaunchKernelGGL(k_assign_exact<float>, dim3(blocks), dim3(ISC_ST_THREADS), 0, s, bytes, isc_ksteps(D, 4), pm,
                            row_mask, centroids, cf, ldc, D, C, nullptr, out_labels, out_scores, status);
     return isc_launch_status();
 }

@@ -39,96 +39,35 @@ __global__ __launch_bounds__(256) void k_bank_gather(const unsigned char* __rest
     }
 }
 
-// isc_cosine_scores: k_exact's score of every (query, listed row) pair, without the search around it.
+// isc_cosine_scores: the exact score of every (query, listed row) pair, without a search around it: the staged form of
+// exact_dots.h, hence the bits isc_cosine_topk_exhaustive returns for the pair.
 //
-// A workgroup owns SC_ROWS = 64 listed rows and a group of SC_GQ = 8 queries.  As in k_exact a wave takes 8 rows (lane l:
-// row l >> 3, 16-byte chunk l & 7 of every K step), the queries sit in LDS as float64 rounded to the bank type first, and
-// every product and sum is float64: per (query, row) the lane's fma chain runs over the K steps in order and over the
-// chunk's elements in order, the 8 lanes are summed by group8_sum, the sum is divided by max(||q||, 1e-12) -- the norm
-// summed per lane over elements lane, lane + 64, ... and then over the wave, as k_exact sums it -- and cast to float32.
-// Same operations in the same order: the bits are those isc_cosine_topk_exhaustive returns for the pair.
-//
-// The queries are staged SC_KC K steps at a time (zero-padded to the K-step width): the LDS image is 8 x 8 K steps of
-// float64 = 32 KiB (fp16) or 16 KiB (fp32) whatever D, so the query-group size does not depend on D and LDS never limits
-// the four 512-thread workgroups a CU can hold; the accumulators of the wave's 8 rows x 8 queries stay in registers across
-// the stages.  The grid is (row blocks) x (query groups), the query group running fastest: the workgroups that share a
-// row block are neighbours and re-read it from the cache.
-constexpr int SC_THREADS = 512;
-constexpr int SC_WAVES = SC_THREADS / 64;
-constexpr int SC_ROWS = SC_WAVES * 8;
-constexpr int SC_GQ = 8;
-constexpr int SC_KC = 8;
-static_assert(SC_GQ == 8, "lane l & 7 of a row's 8 lanes writes query l & 7 of the group");
-static_assert(SC_GQ <= SC_WAVES, "wave g sums the norm of query g");
+// A workgroup owns SC_ROWS = 64 listed rows (a wave 8 of them: lane l holds row l >> 3, 16-byte chunk l & 7 of every K
+// step) and a group of 8 queries, staged 8 K steps at a time (isc_staged_scores): the LDS image does not depend on D, so
+// neither does the query-group size, and LDS never limits the four 512-thread workgroups a CU can hold.  The grid is
+// (row blocks) x (query groups), the query group running fastest: the workgroups that share a row block are neighbours
+// and re-read it from the cache.
+constexpr int SC_ROWS = ISC_ST_THREADS / 64 * 8;
 
 template <typename T>
-__global__ __launch_bounds__(SC_THREADS) void k_row_scores(const unsigned char* __restrict__ bank, int ks, IscPerm pm,
-                                                           const void* __restrict__ queries, int q_f32, int64_t ldq, int d,
-                                                           int nq, int qgroups, const int64_t* __restrict__ rows, int64_t m,
-                                                           const uint32_t* __restrict__ fill_mask,
-                                                           float* __restrict__ scores, int64_t lds) {
-    constexpr int EPK = ISC_KSTEP_BYTES / (int)sizeof(T);  // elements per K step
-    constexpr int PER = Chunk16<T>::N;
-    constexpr int CE = SC_KC * EPK;  // elements per stage
-    __shared__ __attribute__((aligned(16))) double qd[SC_GQ * CE];
-    __shared__ double denom_sh[SC_GQ];
+__global__ __launch_bounds__(ISC_ST_THREADS) void k_row_scores(const unsigned char* __restrict__ bank, int ks, IscPerm pm,
+                                                               const void* __restrict__ queries, int q_f32, int64_t ldq,
+                                                               int d, int nq, int qgroups, const int64_t* __restrict__ rows,
+                                                               int64_t m, const uint32_t* __restrict__ fill_mask,
+                                                               float* __restrict__ scores, int64_t lds) {
+    __shared__ __attribute__((aligned(16))) double qd[ISC_ST_GQ * isc_st_elems<T>()];
+    __shared__ double denom_sh[ISC_ST_GQ];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane >> 3, ch = lane & 7;
-    const int q0 = (int)(blockIdx.x % (unsigned)qgroups) * SC_GQ;
-    const int gn = min(SC_GQ, nq - q0);
+    const int q0 = (int)(blockIdx.x % (unsigned)qgroups) * ISC_ST_GQ;
+    const int gn = min(ISC_ST_GQ, nq - q0);
     const int64_t j = (int64_t)(blockIdx.x / (unsigned)qgroups) * SC_ROWS + wave * 8 + sub;
     const int64_t p = j < m ? isc_live_pos(rows[j], pm, fill_mask) : -1;
     const unsigned char* src = bank + (p >= 0 ? isc_packed_offset(p, 0, ks) : 0) + ch * 16;
 
-    double acc[SC_GQ];
-#pragma unroll
-    for (int g = 0; g < SC_GQ; ++g) acc[g] = 0.0;
-    double nacc = 0.0;  // wave g: this lane's part of the squared norm of query g
-    for (int s0 = 0; s0 < ks; s0 += SC_KC) {
-        const int sn = min(SC_KC, ks - s0);
-        const int e0 = s0 * EPK, en = sn * EPK;
-        if (s0 > 0) __syncthreads();  // the previous stage has been read
-        for (int g = 0; g < SC_GQ; ++g) {
-            // the caller's query elements (fp16 or float32, `q_f32`) rounded to the bank type first, as k_exact reads them
-            const float* qp32 = static_cast<const float*>(queries) + (int64_t)(q0 + g) * ldq;
-            const _Float16* qp16 = static_cast<const _Float16*>(queries) + (int64_t)(q0 + g) * ldq;
-            for (int e = tid; e < en; e += SC_THREADS) {
-                double v = 0.0;
-                if (g < gn && e0 + e < d) v = (double)(float)(T)(q_f32 ? qp32[e0 + e] : (float)qp16[e0 + e]);
-                qd[g * CE + e] = v;
-            }
-        }
-        __syncthreads();
-        if (wave < SC_GQ)  // (e0 is a multiple of 64: the lane's elements are lane, lane + 64, ... of the whole query)
-            for (int e = lane; e < en; e += 64) nacc = fma(qd[wave * CE + e], qd[wave * CE + e], nacc);
-        for (int s = 0; s < sn; ++s) {
-            double a[8];
-            if (p >= 0) {
-                Chunk16<T>::load(src + (size_t)(s0 + s) * ISC_TILE_KSTEP_BYTES, a);
-            } else {
-#pragma unroll
-                for (int e = 0; e < PER; ++e) a[e] = 0.0;
-            }
-            const double* qs = qd + s * EPK + ch * PER;
-#pragma unroll
-            for (int e = 0; e < PER; ++e)
-#pragma unroll
-                for (int g = 0; g < SC_GQ; ++g) acc[g] = fma(qs[g * CE + e], a[e], acc[g]);
-        }
-    }
-    if (wave < SC_GQ) {
-        nacc = isc_wave_sum(nacc);
-        if (lane == 0) denom_sh[wave] = fmax(sqrt(nacc), 1e-12);
-    }
-    __syncthreads();
-    // after group8_sum every one of the row's 8 lanes holds the row's sums: lane `ch` keeps, and writes, query `ch`
-    float mine = 0.f;
-#pragma unroll
-    for (int g = 0; g < SC_GQ; ++g) {
-        const float sc = (float)(group8_sum(acc[g]) / denom_sh[g]);
-        if (ch == g) mine = sc;
-    }
+    // lane `ch` of the row's 8 lanes gets, and writes, query `ch`
+    const float mine = isc_staged_scores<T, false>(src, p >= 0, ks, queries, q_f32, ldq, d, q0, gn, qd, denom_sh);
     if (j < m && ch < gn) scores[(int64_t)(q0 + ch) * lds + j] = p >= 0 ? mine : -INFINITY;
 }
 
@@ -170,17 +109,17 @@ extern "C" int isc_cosine_scores(const void* bank, int dtype, int64_t capacity, 
     if (!isc_aligned(bank, 16) || !isc_aligned(queries, q_dtype == ISC_F16 ? 2 : 4) || !isc_aligned(rows, 8) ||
         !isc_aligned(fill_mask, 4) || !isc_aligned(scores, 4))
         return ISC_ERR_ALIGNMENT;
-    const int qgroups = isc_ceil_div(Q, SC_GQ);
+    const int qgroups = isc_ceil_div(Q, ISC_ST_GQ);
     const int64_t blocks = isc_ceil_div<int64_t>(M, SC_ROWS) * qgroups;
     if (blocks > 0x7fffffff) return ISC_ERR_UNSUPPORTED;
     const unsigned char* in = static_cast<const unsigned char*>(bank);
     const IscPerm pm = isc_make_perm(capacity);
     const int qf = q_dtype == ISC_F32 ? 1 : 0;
     if (dtype == ISC_F16)
-        hipLaunchKernelGGL(k_row_scores<_Float16>, dim3((unsigned)blocks), dim3(SC_THREADS), 0, isc_stream(stream), in,
+        hipLaunchKernelGGL(k_row_scores<_Float16>, dim3((unsigned)blocks), dim3(ISC_ST_THREADS), 0, isc_stream(stream), in,
                            isc_ksteps(D, 2), pm, queries, qf, ldq, D, Q, qgroups, rows, M, fill_mask, scores, lds);
     else
-        hipLaunchKernelGGL(k_row_scores<float>, dim3((unsigned)blocks), dim3(SC_THREADS), 0, isc_stream(stream), in,
+        hipLaunchKernelGGL(k_row_scores<float>, dim3((unsigned)blocks), dim3(ISC_ST_THREADS), 0, isc_stream(stream), in,
                            isc_ksteps(D, 4), pm, queries, qf, ldq, D, Q, qgroups, rows, M, fill_mask, scores, lds);
     return isc_launch_status();
 }

@@ -59,11 +59,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int TM = 256;        // bank rows per tile
 constexpr int NTHREADS = 512;  // 8 waves
 constexpr int CAP = 32;        // candidate slots per (segment, query); segment = (chunk, row-block wave, lane group)
@@ -450,81 +445,6 @@ __global__ __launch_bounds__(256) void k_prep_i8(const TQ* __restrict__ queries,
         qrec[qrow] = make_float4(live ? c : __uint_as_float(0x7fc00000u), (float)sqrt(qs) * (1.f + 1e-6f),
                                  (float)sqrt(rs) * (1.f + 1e-6f), 0.f);
 }
-
-// --- operand traits -------------------------------------------------------------------------------------------
-template <typename T>
-struct Mma;
-
-template <>
-struct Mma<_Float16> {
-    typedef f32x4 Acc;
-    // acc[n] += A(16 rows) . B(16 queries x n) over the 64 halves of one K step.  One 16-byte chunk = 8 halves = the
-    // k-slice one lane feeds to v_mfma_f32_16x16x32_f16; a0/b[0] hold chunks 0-3, a1/b[1] chunks 4-7.
-    static __device__ __forceinline__ void half(const u32x4& a, const u32x4 (&b)[4], f32x4 (&acc)[4]) {
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a),
-                                                            __builtin_bit_cast(half8, b[n]), acc[n], 0, 0, 0);
-    }
-    static __device__ __forceinline__ void row(const u32x4& a0, const u32x4& a1, const u32x4 (&b)[2][4],
-                                               f32x4 (&acc)[4]) {
-        half(a0, b[0], acc);
-        half(a1, b[1], acc);
-    }
-    // query blocks N0 .. N1 - 1 of `half` (the same instructions in the same order per accumulator)
-    template <int N0, int N1>
-    static __device__ __forceinline__ void part(const u32x4& a, const u32x4 (&b)[4], f32x4 (&acc)[4]) {
-#pragma unroll
-        for (int n = N0; n < N1; ++n)
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a),
-                                                            __builtin_bit_cast(half8, b[n]), acc[n], 0, 0, 0);
-    }
-};
-
-template <>
-struct Mma<float> {
-    typedef f32x4 Acc;
-    // one 16-byte chunk = 4 floats: element j of every lane's chunk goes to the j-th v_mfma_f32_16x16x4_f32.
-    // Lane group g therefore supplies k = 4 * chunk + j instead of k = g: a permutation of the K axis applied
-    // identically to both operands, which leaves the dot products unchanged.
-    static __device__ __forceinline__ void half(const u32x4& a, const u32x4 (&b)[4], f32x4 (&acc)[4]) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-                acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[j]), __uint_as_float(b[n][j]), acc[n],
-                                                              0, 0, 0);
-    }
-    static __device__ __forceinline__ void row(const u32x4& a0, const u32x4& a1, const u32x4 (&b)[2][4],
-                                               f32x4 (&acc)[4]) {
-        half(a0, b[0], acc);
-        half(a1, b[1], acc);
-    }
-    template <int N0, int N1>
-    static __device__ __forceinline__ void part(const u32x4& a, const u32x4 (&b)[4], f32x4 (&acc)[4]) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int n = N0; n < N1; ++n)
-                acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[j]), __uint_as_float(b[n][j]), acc[n],
-                                                              0, 0, 0);
-    }
-};
-
-// int8 (the shadow bank of an fp16 bank, bank_layout.h): one 16-byte chunk = 16 int8 = the k-slice one lane feeds to
-// v_mfma_i32_16x16x64_i8, so a 128-byte K step is 128 dimensions in the same two halves of four chunks and the loop
-// around it is the fp16 one, instruction for instruction.  Only the half-major loop (`part`) is instantiated.
-template <>
-struct Mma<signed char> {
-    typedef i32x4 Acc;
-    template <int N0, int N1>
-    static __device__ __forceinline__ void part(const u32x4& a, const u32x4 (&b)[4], i32x4 (&acc)[4]) {
-#pragma unroll
-        for (int n = N0; n < N1; ++n)
-            acc[n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b[n]),
-                                                           acc[n], 0, 0, 0);
-    }
-};
 
 // What the int8 instantiation of k_dots_filter takes in the place of a row filter: the shadow bank's tile records and the
 // per-query records k_prep_i8 wrote beside the int8 query tiles.
@@ -1975,15 +1895,10 @@ __device__ void exact_dots(const unsigned char* __restrict__ bank, int ks, const
         for (int s0 = 0; s0 < ks; s0 += 8) {
             const int s = s0 + sub;
             if (s < ks) {
-                double a[4][8], b[8];
+                const unsigned char* ap[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    Chunk16<T>::load(bank + isc_packed_offset(row[u] < 0 ? 0 : row[u], s, ks) + ch * 16, a[u]);
-                Chunk16<T>::load(qrow_base + (size_t)s * tnq * ISC_KSTEP_BYTES + ch * 16, b);
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int j = 0; j < Chunk16<T>::N; ++j) acc[u] = fma(a[u][j], b[j], acc[u]);
+                for (int u = 0; u < 4; ++u) ap[u] = bank + isc_packed_offset(row[u] < 0 ? 0 : row[u], s, ks) + ch * 16;
+                isc_packed_dot<T, 4>(ap, qrow_base + (size_t)s * tnq * ISC_KSTEP_BYTES + ch * 16, acc);
             }
         }
 #pragma unroll

@@ -1,4 +1,5 @@
-// Pieces shared by the search kernels (cosine_topk.hip, search_range.hip) and the exact float64 search (search_exact.hip).
+// Pieces shared by the search kernels (cosine_topk.hip, search_range.hip), the exact float64 search (search_exact.hip) and
+// the row-major kernels (bank_rows.hip, bank_assign.hip).  The float64 arithmetic of every exact score is in exact_dots.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,6 +8,7 @@
 #include <type_traits>
 
 #include "bank_layout.h"
+#include "exact_dots.h"
 #include "isc_common.h"
 
 // ---- (score, row) as one 64-bit key whose unsigned order is the search order ------------------------------------
@@ -97,17 +99,16 @@ __host__ __device__ __forceinline__ const uint32_t* isc_row_mask_ptr(RowMask... 
     else if constexpr (isc_grouped<RowMask...>()) return (row_mask, ...).mask;
     else return (row_mask, ...);
 }
+// bit p of a packed bitmap (a row filter, a bank's fill bitmap); ... of one that may be NULL: every position is set
+__device__ __forceinline__ bool isc_mask_bit(const uint32_t* m, int64_t p) { return (m[p >> 5] >> (p & 31)) & 1u; }
+__device__ __forceinline__ bool isc_mask_allows(const uint32_t* m, int64_t p) {
+    return m == nullptr || isc_mask_bit(m, p);
+}
 template <typename... RowMask>
 __device__ __forceinline__ bool isc_row_allowed(int64_t p, RowMask... row_mask) {
-    if constexpr (sizeof...(RowMask) == 0) {
-        return true;
-    } else if constexpr (isc_grouped<RowMask...>()) {
-        const uint32_t* m = isc_row_mask_ptr(row_mask...);
-        return m == nullptr || ((m[p >> 5] >> (p & 31)) & 1u);
-    } else {
-        const uint32_t* m = isc_row_mask_ptr(row_mask...);
-        return (m[p >> 5] >> (p & 31)) & 1u;
-    }
+    if constexpr (sizeof...(RowMask) == 0) return true;
+    else if constexpr (isc_grouped<RowMask...>()) return isc_mask_allows(isc_row_mask_ptr(row_mask...), p);
+    else return isc_mask_bit(isc_row_mask_ptr(row_mask...), p);
 }
 template <typename... RowMask>
 __host__ __device__ __forceinline__ const int32_t* isc_row_group_ptr(RowMask... row_mask) {
@@ -125,40 +126,98 @@ __device__ __forceinline__ bool isc_row_allowed_for(int64_t p, int qc, RowMask..
     else return isc_row_allowed(p, row_mask...);
 }
 
-// ---- float64 arithmetic shared by the exact re-scores of cosine_topk.hip and search_range.hip ---------------------
-// 16 bytes of a packed row as float64 values
+// ---- matrix-core operand traits of the filters (k_dots_filter, k_range_filter, k_assign_filter) ----------------------
+// One definition of the instructions a filter issues per 16-byte chunk, so one error bound holds for all of them:
+// |A - E| <= eps = Dpad 2^-23 ||q|| max||b|| for the float32 accumulator A of a dot E (the guard of k_final, the tau of the
+// range search, the margin m of isc_bank_assign).
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
 template <typename T>
-struct Chunk16;
+struct Mma;
+
 template <>
-struct Chunk16<_Float16> {
-    static constexpr int N = 8;
-    static __device__ __forceinline__ void load(const unsigned char* p, double (&v)[8]) {
-        const uint4 raw = *reinterpret_cast<const uint4*>(p);
-        const _Float16* h = reinterpret_cast<const _Float16*>(&raw);
+struct Mma<_Float16> {
+    typedef f32x4 Acc;
+    // acc[n] += A(16 rows) . B(16 queries x n) over the 64 halves of one K step.  One 16-byte chunk = 8 halves = the
+    // k-slice one lane feeds to v_mfma_f32_16x16x32_f16; a0/b[0] hold chunks 0-3, a1/b[1] chunks 4-7.
+    static __device__ __forceinline__ void half(const u32x4& a, const u32x4 (&b)[4], f32x4 (&acc)[4]) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (double)(float)h[j];
+        for (int n = 0; n < 4; ++n)
+            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a),
+                                                            __builtin_bit_cast(half8, b[n]), acc[n], 0, 0, 0);
     }
-};
-template <>
-struct Chunk16<float> {
-    static constexpr int N = 4;
-    static __device__ __forceinline__ void load(const unsigned char* p, double (&v)[8]) {
-        const float4 raw = *reinterpret_cast<const float4*>(p);
-        v[0] = (double)raw.x;
-        v[1] = (double)raw.y;
-        v[2] = (double)raw.z;
-        v[3] = (double)raw.w;
+    static __device__ __forceinline__ void row(const u32x4& a0, const u32x4& a1, const u32x4 (&b)[2][4],
+                                               f32x4 (&acc)[4]) {
+        half(a0, b[0], acc);
+        half(a1, b[1], acc);
+    }
+    // query blocks N0 .. N1 - 1 of `half` (the same instructions in the same order per accumulator)
+    template <int N0, int N1>
+    static __device__ __forceinline__ void part(const u32x4& a, const u32x4 (&b)[4], f32x4 (&acc)[4]) {
+#pragma unroll
+        for (int n = N0; n < N1; ++n)
+            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a),
+                                                            __builtin_bit_cast(half8, b[n]), acc[n], 0, 0, 0);
+    }
+    // one block of `half`: acc += A(16 rows) . B(16 rows) over one 16-byte chunk of each
+    static __device__ __forceinline__ void step(const u32x4& a, const u32x4& b, f32x4& acc) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), acc, 0, 0,
+                                                     0);
     }
 };
 
-// sum over the 8 lanes that share a bank row (k_exact, k_exact_collapse, k_row_scores: lane l holds the 16-byte chunk l & 7
-// of every K step of row l >> 3), left in all 8
-__device__ __forceinline__ double group8_sum(double v) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    return v;
-}
+template <>
+struct Mma<float> {
+    typedef f32x4 Acc;
+    // one 16-byte chunk = 4 floats: element j of every lane's chunk goes to the j-th v_mfma_f32_16x16x4_f32.
+    // Lane group g therefore supplies k = 4 * chunk + j instead of k = g: a permutation of the K axis applied
+    // identically to both operands, which leaves the dot products unchanged.
+    static __device__ __forceinline__ void half(const u32x4& a, const u32x4 (&b)[4], f32x4 (&acc)[4]) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+                acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[j]), __uint_as_float(b[n][j]), acc[n],
+                                                              0, 0, 0);
+    }
+    static __device__ __forceinline__ void row(const u32x4& a0, const u32x4& a1, const u32x4 (&b)[2][4],
+                                               f32x4 (&acc)[4]) {
+        half(a0, b[0], acc);
+        half(a1, b[1], acc);
+    }
+    template <int N0, int N1>
+    static __device__ __forceinline__ void part(const u32x4& a, const u32x4 (&b)[4], f32x4 (&acc)[4]) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int n = N0; n < N1; ++n)
+                acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[j]), __uint_as_float(b[n][j]), acc[n],
+                                                              0, 0, 0);
+    }
+    static __device__ __forceinline__ void step(const u32x4& a, const u32x4& b, f32x4& acc) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[j]), __uint_as_float(b[j]), acc, 0, 0, 0);
+    }
+};
+
+// int8 (the shadow bank of an fp16 bank, bank_layout.h): one 16-byte chunk = 16 int8 = the k-slice one lane feeds to
+// v_mfma_i32_16x16x64_i8, so a 128-byte K step is 128 dimensions in the same two halves of four chunks and the loop
+// around it is the fp16 one, instruction for instruction.  Only the half-major loop (`part`) is instantiated.
+template <>
+struct Mma<signed char> {
+    typedef i32x4 Acc;
+    template <int N0, int N1>
+    static __device__ __forceinline__ void part(const u32x4& a, const u32x4 (&b)[4], i32x4 (&acc)[4]) {
+#pragma unroll
+        for (int n = N0; n < N1; ++n)
+            acc[n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b[n]),
+                                                           acc[n], 0, 0, 0);
+    }
+};
 
 // ---- the packed image of a call's queries (k_prep of the searches, k_assign_prep of isc_bank_assign) ----------------
 // queries row-major [q][ldq] -> packed [qtile][K step][tnq rows][128 B]; rows >= q and columns >= d are zero.  Thread i
@@ -188,27 +247,8 @@ __device__ __forceinline__ void isc_pack_query_chunk(const TQ* __restrict__ quer
 __device__ __forceinline__ int64_t isc_live_pos(int64_t r, const IscPerm& pm, const uint32_t* __restrict__ fill_mask) {
     if (r < 0 || r >= pm.n) return -1;
     const int64_t p = isc_perm_pos(pm, r);
-    if (fill_mask && !((fill_mask[p >> 5] >> (p & 31)) & 1u)) return -1;
+    if (fill_mask && !isc_mask_bit(fill_mask, p)) return -1;
     return p;
-}
-
-// float64 norm of the packed query row at `qrow_base` (K step s at + s * tnq * 128 B); called by ONE wave, result in
-// every lane
-template <typename T>
-__device__ double wave_query_norm(const unsigned char* qrow_base, int ks, int tnq) {
-    const int lane = threadIdx.x & 63;
-    const int sub = lane >> 3, ch = lane & 7;
-    double acc = 0.0;
-    for (int s0 = 0; s0 < ks; s0 += 8) {
-        const int s = s0 + sub;
-        if (s < ks) {
-            double v[8];
-            Chunk16<T>::load(qrow_base + (size_t)s * tnq * ISC_KSTEP_BYTES + ch * 16, v);
-#pragma unroll
-            for (int j = 0; j < Chunk16<T>::N; ++j) acc = fma(v[j], v[j], acc);
-        }
-    }
-    return isc_wave_sum(acc);
 }
 
 // ---- exact float64 search of a LIST of queries (search_exact.hip) -------------------------------------------------

@@ -25,30 +25,68 @@ int ex_chunks(int64_t n, int k) {
     return want;
 }
 
-// 16 bytes of a packed row as float64 values
-template <typename T>
-struct Chunk;
-template <>
-struct Chunk<_Float16> {
-    static constexpr int N = 8;
-    static __device__ __forceinline__ void load(const unsigned char* p, double (&v)[8]) {
-        const uint4 raw = *reinterpret_cast<const uint4*>(p);
-        const _Float16* h = reinterpret_cast<const _Float16*>(&raw);
+// More than 64 KiB of dynamic LDS needs the opt-in, once per kernel AND device (a process may drive several GPUs):
+// `attr_done` is the kernel's mask with one bit per device id, set only after the call succeeded; a failure is reported,
+// not discarded.
+int ex_lds_opt_in(const void* kernel, unsigned long long& attr_done) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return ISC_ERR_NO_DEVICE;
+    const bool tracked = dev >= 0 && dev < 64;
+    if (!tracked || !((__atomic_load_n(&attr_done, __ATOMIC_RELAXED) >> dev) & 1ull)) {
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
+            (void)hipGetLastError();
+            return ISC_ERR_UNSUPPORTED;
+        }
+        if (tracked) __atomic_fetch_or(&attr_done, 1ull << dev, __ATOMIC_RELAXED);
+    }
+    return ISC_OK;
+}
+
+// ---- what k_exact and k_exact_collapse share: the staged form of exact_dots.h with the listed queries whole in LDS ----
+// listed queries redo_list[g0 .. g0 + gn) -> qd[GQ][dp] (no barrier)
+template <typename T, int GQ>
+__device__ __forceinline__ void ex_stage_group(const void* __restrict__ queries, int q_f32, int64_t ldq, int d, int dp,
+                                               const int32_t* __restrict__ redo_list, int g0, int gn,
+                                               double* __restrict__ qd) {
+    isc_stage_queries<T, GQ, EX_THREADS>(queries, q_f32, ldq, d, gn, 0, dp, dp, qd,
+                                         [&](int g) { return g < gn ? redo_list[g0 + g] : 0; });
+}
+
+// the denominators of the staged group (wave g sums query g); called after the barrier that ends the staging, ends with one
+template <int GQ>
+__device__ __forceinline__ void ex_group_denoms(const double* __restrict__ qd, int dp, double (&denom)[GQ]) {
+    static_assert(GQ <= EX_WAVES, "wave g sums the norm of query g");
+    __shared__ double denom_sh[GQ];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (wave < GQ) {
+        const double dn = isc_norm_denom(isc_norm_partial(qd + (size_t)wave * dp, dp, 0.0));
+        if (lane == 0) denom_sh[wave] = dn;
+    }
+    __syncthreads();
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (double)(float)h[j];
+    for (int g = 0; g < GQ; ++g) denom[g] = denom_sh[g];
+}
+
+// Publish this workgroup's partial lists and tell whether it is the last of `chunks` to arrive: the last one merges
+// (cdna_hip_programming.md guideline 16: every storing wave drains its stores, workgroup barrier, one agent-scope release,
+// asm wait, then the counter; the last arrival acquires before it reads the others' lists).  Called by every thread.
+__device__ __forceinline__ bool ex_publish_is_last(int32_t* __restrict__ done, int chunks) {
+    __shared__ int last_sh;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const int old = atomicAdd(done, 1);
+        last_sh = old == chunks - 1 ? 1 : 0;
+        if (last_sh) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
     }
-};
-template <>
-struct Chunk<float> {
-    static constexpr int N = 4;
-    static __device__ __forceinline__ void load(const unsigned char* p, double (&v)[8]) {
-        const float4 raw = *reinterpret_cast<const float4*>(p);
-        v[0] = (double)raw.x;
-        v[1] = (double)raw.y;
-        v[2] = (double)raw.z;
-        v[3] = (double)raw.w;
-    }
-};
+    __syncthreads();
+    return last_sh != 0;
+}
 
 // grid = chunks of consecutive bank tiles, 512 threads.  GQ listed queries are scored per sweep of the chunk: the
 // queries sit in LDS as float64, a wave takes 8 bank rows at a time (lane = row l >> 3, 16-byte chunk l & 7 of every K
@@ -72,13 +110,9 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact(const unsigned char* __res
     const int nf = *redo_count;
     if (nf <= 0) return;  // the normal case
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
-    constexpr int EPK = ISC_KSTEP_BYTES / (int)sizeof(T);  // elements per K step
-    constexpr int PER = Chunk<T>::N;
-    const int dp = ks * EPK;
+    const int dp = ks * (ISC_KSTEP_BYTES / (int)sizeof(T));  // the padded query length
     double* qd = reinterpret_cast<double*>(dyn);                                     // [GQ][dp]
     unsigned long long* lists = reinterpret_cast<unsigned long long*>(qd + (size_t)GQ * dp);  // [GQ][EX_WAVES][k]
-    __shared__ double denom_sh[GQ];
-    __shared__ int last_sh;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int chunk = blockIdx.x, chunks = gridDim.x;
@@ -89,29 +123,11 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact(const unsigned char* __res
     for (int g0 = 0; g0 < nf; g0 += GQ) {
         const int gn = min(GQ, nf - g0);
         __syncthreads();  // the previous group's lists have been merged
-        for (int g = 0; g < GQ; ++g) {
-            const int qi = g < gn ? redo_list[g0 + g] : 0;
-            // the caller's query elements (fp16 or float32, `q_f32`) rounded to the bank type first, as k_prep packs them
-            const float* qp32 = static_cast<const float*>(queries) + (int64_t)qi * ldq;
-            const _Float16* qp16 = static_cast<const _Float16*>(queries) + (int64_t)qi * ldq;
-            for (int e = tid; e < dp; e += EX_THREADS) {
-                double v = 0.0;
-                if (g < gn && e < d) v = (double)(float)(T)(q_f32 ? qp32[e] : (float)qp16[e]);
-                qd[(size_t)g * dp + e] = v;
-            }
-        }
+        ex_stage_group<T, GQ>(queries, q_f32, ldq, d, dp, redo_list, g0, gn, qd);
         for (int i = tid; i < GQ * EX_WAVES * k; i += EX_THREADS) lists[i] = 0ull;
         __syncthreads();
-        if (wave < GQ) {
-            double acc = 0.0;
-            for (int e = lane; e < dp; e += 64) acc = fma(qd[(size_t)wave * dp + e], qd[(size_t)wave * dp + e], acc);
-            acc = isc_wave_sum(acc);
-            if (lane == 0) denom_sh[wave] = fmax(sqrt(acc), 1e-12);
-        }
-        __syncthreads();
         double denom[GQ];
-#pragma unroll
-        for (int g = 0; g < GQ; ++g) denom[g] = denom_sh[g];
+        ex_group_denoms<GQ>(qd, dp, denom);
         [[maybe_unused]] int qcode[GQ];
         if constexpr (isc_grouped<RowMask...>()) {
 #pragma unroll
@@ -124,21 +140,11 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact(const unsigned char* __res
                 const unsigned char* src =
                     bank + ((int64_t)tile * ks * ISC_TILE_ROWS + grp * 8 + sub) * ISC_KSTEP_BYTES + ch * 16;
                 double acc[GQ];
-#pragma unroll
-                for (int g = 0; g < GQ; ++g) acc[g] = 0.0;
-                for (int s = 0; s < ks; ++s) {
-                    double a[8];
-                    Chunk<T>::load(src + (size_t)s * ISC_TILE_KSTEP_BYTES, a);
-                    const double* qs = qd + s * EPK + ch * PER;
-#pragma unroll
-                    for (int j = 0; j < PER; ++j)
-#pragma unroll
-                        for (int g = 0; g < GQ; ++g) acc[g] = fma(qs[(size_t)g * dp + j], a[j], acc[g]);
-                }
+                isc_row_dots<T, GQ>(src, ks, qd, dp, acc);
 #pragma unroll
                 for (int g = 0; g < GQ; ++g) {
                     if (g >= gn) break;
-                    const float sc = (float)(group8_sum(acc[g]) / denom[g]);
+                    const float sc = isc_exact_score(acc[g], denom[g]);
                     unsigned long long* wl = lists + ((size_t)g * EX_WAVES + wave) * k;
                     const unsigned long long worst = wl[k - 1];  // 0 while the list is not full
                     bool cand = ch == 0 && p < pm.n && isc_score_bits(sc) >= (unsigned)(worst >> 32);
@@ -186,22 +192,7 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact(const unsigned char* __res
         }
     }
 
-    // ---- publish; the last workgroup to arrive merges (cdna_hip_programming.md guideline 16: every storing wave drains
-    // its stores, workgroup barrier, one agent-scope release, asm wait, then the counter)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int old = atomicAdd(done, 1);
-        last_sh = old == chunks - 1 ? 1 : 0;
-        if (last_sh) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (!last_sh) return;
+    if (!ex_publish_is_last(done, chunks)) return;
 
     // k-way merge: a lane holds the heads of lists lane, lane + 64, ... (chunks <= 256: at most four)
     for (int f = wave; f < nf; f += EX_WAVES) {
@@ -314,20 +305,9 @@ int launch_exact(const void* bank, int64_t n, int d, const void* queries, int q_
     const int dp = ks * (ISC_KSTEP_BYTES / (int)sizeof(T));
     const size_t lds = (size_t)GQ * dp * 8 + (size_t)GQ * EX_WAVES * k * 8;
     const int ntiles = (int)isc_ceil_div<int64_t>(n, ISC_TILE_ROWS);
-    // more than 64 KiB of dynamic LDS needs the opt-in, once per kernel AND device (a process may drive several GPUs):
-    // one bit per device id, set only after the call succeeded; a failure is reported, not discarded
     static unsigned long long attr_done = 0ull;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return ISC_ERR_NO_DEVICE;
-    const bool tracked = dev >= 0 && dev < 64;
-    if (!tracked || !((__atomic_load_n(&attr_done, __ATOMIC_RELAXED) >> dev) & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_exact<T, GQ, RowMask...>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return ISC_ERR_UNSUPPORTED;
-        }
-        if (tracked) __atomic_fetch_or(&attr_done, 1ull << dev, __ATOMIC_RELAXED);
-    }
+    const int st = ex_lds_opt_in(reinterpret_cast<const void*>(&k_exact<T, GQ, RowMask...>), attr_done);
+    if (st != ISC_OK) return st;
     hipLaunchKernelGGL((k_exact<T, GQ, RowMask...>), dim3(ws.chunks), dim3(EX_THREADS), lds, stream,
                        static_cast<const unsigned char*>(bank), ks, isc_make_perm(n), ntiles, ws.tiles_per_chunk,
                        queries, q_f32, ldq, d, k, index_base, ws.redo_count, ws.redo_list, ws.part,
@@ -494,9 +474,7 @@ namespace {
 
 // the group code of query i of the pass: -1 (none) without query codes (a collapsed search may exclude nothing)
 __device__ __forceinline__ int collapse_query_code(const IscGroups& g, int i) {
-    if (g.query_group == nullptr || i >= g.nq) return -1;
-    const int c = g.query_group[i];
-    return c < 0 ? -1 : c;
+    return g.query_group == nullptr ? -1 : isc_query_code(g, i);
 }
 
 __device__ __forceinline__ void wave_sync_lds() {
@@ -521,14 +499,10 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact_collapse(
     const int nf = *redo_count;
     if (nf <= 0) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
-    constexpr int EPK = ISC_KSTEP_BYTES / (int)sizeof(T);
-    constexpr int PER = Chunk<T>::N;
-    const int dp = ks * EPK;
+    const int dp = ks * (ISC_KSTEP_BYTES / (int)sizeof(T));  // the padded query length
     double* qd = reinterpret_cast<double*>(dyn);                                                 // [GQ][dp]
     unsigned long long* lists = reinterpret_cast<unsigned long long*>(qd + (size_t)GQ * dp);    // [GQ][EX_WAVES][k]
     int* lcode = reinterpret_cast<int*>(lists + (size_t)GQ * EX_WAVES * k);                     // [GQ][EX_WAVES][k]
-    __shared__ double denom_sh[GQ];
-    __shared__ int last_sh;
     __shared__ int ocode[EX_WAVES][ISC_TOPK_MAX_K];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -540,35 +514,17 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact_collapse(
     for (int g0 = 0; g0 < nf; g0 += GQ) {
         const int gn = min(GQ, nf - g0);
         __syncthreads();  // the previous group's lists have been merged
-        for (int g = 0; g < GQ; ++g) {
-            const int qi = g < gn ? redo_list[g0 + g] : 0;
-            const float* qp32 = static_cast<const float*>(queries) + (int64_t)qi * ldq;
-            const _Float16* qp16 = static_cast<const _Float16*>(queries) + (int64_t)qi * ldq;
-            for (int e = tid; e < dp; e += EX_THREADS) {
-                double v = 0.0;
-                if (g < gn && e < d) v = (double)(float)(T)(q_f32 ? qp32[e] : (float)qp16[e]);
-                qd[(size_t)g * dp + e] = v;
-            }
-        }
+        ex_stage_group<T, GQ>(queries, q_f32, ldq, d, dp, redo_list, g0, gn, qd);
         for (int i = tid; i < GQ * EX_WAVES * k; i += EX_THREADS) {
             lists[i] = 0ull;
             lcode[i] = -1;
         }
         __syncthreads();
-        if (wave < GQ) {
-            double acc = 0.0;
-            for (int e = lane; e < dp; e += 64) acc = fma(qd[(size_t)wave * dp + e], qd[(size_t)wave * dp + e], acc);
-            acc = isc_wave_sum(acc);
-            if (lane == 0) denom_sh[wave] = fmax(sqrt(acc), 1e-12);
-        }
-        __syncthreads();
         double denom[GQ];
+        ex_group_denoms<GQ>(qd, dp, denom);
         int qcode[GQ];
 #pragma unroll
-        for (int g = 0; g < GQ; ++g) {
-            denom[g] = denom_sh[g];
-            qcode[g] = g < gn ? collapse_query_code(grp, redo_list[g0 + g]) : -1;
-        }
+        for (int g = 0; g < GQ; ++g) qcode[g] = g < gn ? collapse_query_code(grp, redo_list[g0 + g]) : -1;
 
         for (int tile = tile_begin; tile < tile_end; ++tile) {
             for (int rg = wave; rg < ISC_TILE_ROWS / 8; rg += EX_WAVES) {
@@ -576,23 +532,13 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact_collapse(
                 const unsigned char* src =
                     bank + ((int64_t)tile * ks * ISC_TILE_ROWS + rg * 8 + sub) * ISC_KSTEP_BYTES + ch * 16;
                 double acc[GQ];
-#pragma unroll
-                for (int g = 0; g < GQ; ++g) acc[g] = 0.0;
-                for (int s = 0; s < ks; ++s) {
-                    double a[8];
-                    Chunk<T>::load(src + (size_t)s * ISC_TILE_KSTEP_BYTES, a);
-                    const double* qs = qd + s * EPK + ch * PER;
-#pragma unroll
-                    for (int j = 0; j < PER; ++j)
-#pragma unroll
-                        for (int g = 0; g < GQ; ++g) acc[g] = fma(qs[(size_t)g * dp + j], a[j], acc[g]);
-                }
+                isc_row_dots<T, GQ>(src, ks, qd, dp, acc);
                 const bool real = ch == 0 && p < pm.n && isc_row_allowed(p, grp);
                 const int code = real ? grp.row_group[p] : -1;
 #pragma unroll
                 for (int g = 0; g < GQ; ++g) {
                     if (g >= gn) break;
-                    const float sc = (float)(group8_sum(acc[g]) / denom[g]);
+                    const float sc = isc_exact_score(acc[g], denom[g]);
                     unsigned long long* wl = lists + ((size_t)g * EX_WAVES + wave) * k;
                     int* wc = lcode + ((size_t)g * EX_WAVES + wave) * k;
                     const unsigned long long worst = wl[k - 1];  // 0 while the list is not full
@@ -665,21 +611,7 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact_collapse(
         }
     }
 
-    // ---- publish; the last workgroup to arrive merges (as in k_exact)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int old = atomicAdd(done, 1);
-        last_sh = old == chunks - 1 ? 1 : 0;
-        if (last_sh) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
-    if (!last_sh) return;
+    if (!ex_publish_is_last(done, chunks)) return;
 
     // k-way merge of the chunks' lists, best key first; a group already written is skipped (its first appearance was its
     // best row).  A lane holds the heads of lists lane, lane + 64, ... (chunks <= 256: at most four)
@@ -749,18 +681,9 @@ int launch_exact_collapse(const void* bank, int64_t n, int d, const void* querie
     const int dp = ks * (ISC_KSTEP_BYTES / (int)sizeof(T));
     const size_t lds = (size_t)GQ * dp * 8 + (size_t)GQ * EX_WAVES * k * 12;
     const int ntiles = (int)isc_ceil_div<int64_t>(n, ISC_TILE_ROWS);
-    static unsigned long long attr_done = 0ull;  // per device id, as in launch_exact
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return ISC_ERR_NO_DEVICE;
-    const bool tracked = dev >= 0 && dev < 64;
-    if (!tracked || !((__atomic_load_n(&attr_done, __ATOMIC_RELAXED) >> dev) & 1ull)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_exact_collapse<T, GQ>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return ISC_ERR_UNSUPPORTED;
-        }
-        if (tracked) __atomic_fetch_or(&attr_done, 1ull << dev, __ATOMIC_RELAXED);
-    }
+    static unsigned long long attr_done = 0ull;
+    const int st = ex_lds_opt_in(reinterpret_cast<const void*>(&k_exact_collapse<T, GQ>), attr_done);
+    if (st != ISC_OK) return st;
     hipLaunchKernelGGL((k_exact_collapse<T, GQ>), dim3(ws.chunks), dim3(EX_THREADS), lds, stream,
                        static_cast<const unsigned char*>(bank), ks, isc_make_perm(n), ntiles, ws.tiles_per_chunk, queries,
                        q_f32, ldq, d, k, index_base, ws.redo_count, ws.redo_list, ws.part, part_code, ws.done, out_s, out_i,

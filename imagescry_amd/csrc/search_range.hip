@@ -8,10 +8,11 @@
 //   per pass of <= 1024 queries:
 //     k_range_pack     queries -> packed [query tile of 64][K step][64 rows][128 B], rounded to the bank dtype
 //     k_range_qinfo    one wave per query: float64 norm, the filter threshold tau, the per-query mode
-//     k_range_filter   fp32 matrix-core scores A of 256 bank rows x 64 queries per workgroup (the instructions of the top-k
-//                      filter); every A > tau is appended as a candidate (query, packed row, A)
+//     k_range_filter   fp32 matrix-core scores A of 256 bank rows x 64 queries per workgroup (Mma<T>::step of
+//                      search_common.h: the instructions of the top-k filter, so the same eps bounds A); every A > tau is
+//                      appended as a candidate (query, packed row, A)
 //     k_range_scan     float64 sweep of the whole bank for the queries the filter cannot serve (normally none)
-//     k_range_rescore  every candidate of the pass re-scored in float64 (exact_dots' arithmetic); kept iff
+//     k_range_rescore  every candidate of the pass re-scored in float64 (exact_dots.h: the packed-row form); kept iff
 //                      float32(E / denom) >= t
 //   k_range_offsets    per-query counts -> exclusive scan -> offsets[Q + 1]; needed = candidates + rows of all-row queries
 //   k_range_scatter    kept candidates -> (score, original row) keys in their query's segment
@@ -43,36 +44,12 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RQT = 64;                          // queries per filter workgroup (one query tile)
 constexpr int RPASS = ISC_SEARCH_PASS_QUERIES;   // queries per pass: the workspace holds one pass's packed queries
 constexpr int64_t R_MAX_CAPACITY = 0x7fffffff;   // the segmented sort counts items in int
 
 enum : int32_t { MODE_FILTER = 0, MODE_SCAN = 1, MODE_NONE = 2, MODE_ALL = 3 };
-
-// acc += A(16 bank rows) . B(16 queries) over one 16-byte chunk of each: the instructions of the top-k filter (Mma<T> in
-// cosine_topk.hip), so the same eps bounds the result
-template <typename T>
-struct RangeMma;
-template <>
-struct RangeMma<_Float16> {
-    static __device__ __forceinline__ void step(const u32x4& a, const u32x4& b, f32x4& acc) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), acc, 0,
-                                                     0, 0);
-    }
-};
-template <>
-struct RangeMma<float> {
-    static __device__ __forceinline__ void step(const u32x4& a, const u32x4& b, f32x4& acc) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[j]), __uint_as_float(b[j]), acc, 0, 0, 0);
-    }
-};
 
 struct RangeWs {
     unsigned char* qpacked;           // [qpad][ks] x 128 B: one pass's queries, packed
@@ -329,7 +306,7 @@ __global__ __launch_bounds__(256) void k_range_filter(const unsigned char* __res
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
-                for (int nb = 0; nb < 4; ++nb) RangeMma<T>::step(av[m][h], bv[nb][h], acc[m][nb]);
+                for (int nb = 0; nb < 4; ++nb) Mma<T>::step(av[m][h], bv[nb][h], acc[m][nb]);
     };
     u32x4 a0[4][2], b0[4][2], a1[4][2], b1[4][2];
     load(0, a0, b0);
@@ -436,13 +413,9 @@ __global__ __launch_bounds__(256) void k_range_scan(const unsigned char* __restr
             if (row < n && isc_row_allowed_for(row, qc, row_mask...)) {
                 for (int s = 0; s < ks; ++s) {
 #pragma unroll
-                    for (int ch = 0; ch < 8; ++ch) {
-                        double a[8], b[8];
-                        Chunk16<T>::load(bank + isc_packed_offset(row, s, ks) + ch * 16, a);
-                        Chunk16<T>::load(qrow + (size_t)s * RQT * ISC_KSTEP_BYTES + ch * 16, b);
-#pragma unroll
-                        for (int j = 0; j < Chunk16<T>::N; ++j) e = fma(a[j], b[j], e);
-                    }
+                    for (int ch = 0; ch < 8; ++ch)
+                        e = isc_packed_dot<T>(bank + isc_packed_offset(row, s, ks) + ch * 16,
+                                              qrow + (size_t)s * RQT * ISC_KSTEP_BYTES + ch * 16, e);
                 }
                 keep = (float)(e / dn) >= t_dn;  // false for NaN
             }
@@ -456,8 +429,8 @@ __global__ __launch_bounds__(256) void k_range_scan(const unsigned char* __restr
     }
 }
 
-// Every candidate of the pass re-scored in float64, one wave per candidate, with the per-lane order and the wave sum of
-// exact_dots (cosine_topk.hip): E is bit for bit the top-k's, so a range result and a top-k result agree on every score.
+// Every candidate of the pass re-scored in float64, one wave per candidate: the packed-row form of exact_dots.h with the
+// top-k's lane mapping, so E is bit for bit the top-k's and a range result and a top-k result agree on every score.
 template <typename T>
 __global__ __launch_bounds__(256) void k_range_rescore(const unsigned char* __restrict__ bank, int ks,
                                                        const unsigned char* __restrict__ qpacked, int q0,
@@ -481,13 +454,9 @@ __global__ __launch_bounds__(256) void k_range_rescore(const unsigned char* __re
         double acc = 0.0;
         for (int s0 = 0; s0 < ks; s0 += 8) {
             const int s = s0 + sub;
-            if (s < ks) {
-                double a[8], b[8];
-                Chunk16<T>::load(bank + isc_packed_offset(row, s, ks) + ch * 16, a);
-                Chunk16<T>::load(qrow + (size_t)s * RQT * ISC_KSTEP_BYTES + ch * 16, b);
-#pragma unroll
-                for (int j = 0; j < Chunk16<T>::N; ++j) acc = fma(a[j], b[j], acc);
-            }
+            if (s < ks)
+                acc = isc_packed_dot<T>(bank + isc_packed_offset(row, s, ks) + ch * 16,
+                                        qrow + (size_t)s * RQT * ISC_KSTEP_BYTES + ch * 16, acc);
         }
         const double e = isc_wave_sum(acc);
         if (lane == 0) {

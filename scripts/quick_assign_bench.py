@@ -14,7 +14,9 @@ scores and must agree; the centroid bank ranks by dot / ||row|| -- a search norm
 dot / ||centroid||, so it may pick another centroid on a near tie when the stored centroids' norms differ in the last fp16
 bits: it is the closest older route, not the same function.  `stream_ms` is one read of the packed bank (N * D * 2 B) at the
 6.29 TB/s a float4 copy reaches.
-Usage: python scripts/quick_assign_bench.py [--out FILE.json] [--rows N] [--baseline-rows M] [C ...]"""
+`--exact` adds, on the same bank, the float64 passes nothing else times: `search_exhaustive` of 8 queries, `scores` of 8
+queries x 65536 rows and `assign_exhaustive` of 16 centroids (the median of 20 calls each).
+Usage: python scripts/quick_assign_bench.py [--out FILE.json] [--rows N] [--baseline-rows M] [--exact] [C ...]"""
 import json
 import os
 import statistics
@@ -38,6 +40,9 @@ if "--rows" in args:
     i = args.index("--rows")
     N = int(args[i + 1])
     del args[i : i + 2]
+exact = "--exact" in args
+if exact:
+    args.remove("--exact")
 if "--baseline-rows" in args:
     i = args.index("--baseline-rows")
     BASE_ROWS = int(args[i + 1])
@@ -126,6 +131,26 @@ for c in cs:
           "rows_differing_from_scores_argmax": diff_a, "rows_differing_from_centroid_bank": diff_b,
           "centroid_bank_timed_rows": BASE_ROWS})
     del cbank
+if exact:
+    # the float64 passes on the same bank (csrc/exact_dots.h), interleaved round by round like the routes above
+    q8 = torch.nn.functional.normalize(torch.randn(8, D, generator=g, device=dev), dim=1)
+    c16 = torch.nn.functional.normalize(torch.randn(16, D, generator=g, device=dev), dim=1)
+    some = torch.randperm(N, generator=g, device=dev)[: min(65536, N)]
+    passes = {
+        "search_exhaustive-Q8": lambda: bank.search_exhaustive(q8, 10),
+        "scores-8x64K": lambda: bank.scores(q8, some),
+        "assign_exhaustive-C16": lambda: bank.assign_exhaustive(c16),
+    }
+    for fn in passes.values():
+        fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in passes}
+    for _ in range(REPS):
+        for name, fn in passes.items():
+            times[name].append(timed(fn))
+    for name, t in times.items():
+        emit({"N": N, "D": D, "exact_pass": name, "ms": round(statistics.median(t), 3), "min_ms": round(min(t), 3),
+              "max_ms": round(max(t), 3)})
 if out_path:
     with open(out_path, "w") as f:
         json.dump(out, f, indent=1)

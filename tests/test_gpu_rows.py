@@ -31,7 +31,7 @@ from oracle import search_oracle  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 F16, F32 = torch.float16, torch.float32
-GQ = 8  # the query-group size of k_row_scores (csrc/bank_rows.hip: SC_GQ)
+GQ = 8  # the query-group size of k_row_scores (csrc/exact_dots.h: ISC_ST_GQ)
 QS = (1, GQ - 1, GQ, GQ + 1)
 MS = (1, 7, 8, 9, 300)
 K = 10
@@ -188,6 +188,47 @@ def test_scores_have_the_bits_of_the_exhaustive_search_and_of_search(name: str, 
                                            atol=1e-6)
                 assert np.all(s.cpu().numpy()[:, ~alive] == -np.inf)
     assert eb.scores(st["q"][:0], [1, 2]).shape == (0, 2) and eb.scores(st["q"], []).shape == (GQ + 1, 0)
+
+
+@pytest.mark.parametrize("dtype,d", [(F16, 520), (F32, 264)])
+def test_every_exact_family_gives_the_same_score_bits(dtype: torch.dtype, d: int, device: torch.device) -> None:
+    """One bank, every float64 pass (csrc/exact_dots.h): the score of a (query, row) pair has the same bits from `scores`,
+    `search_exhaustive`, `search_groups_exhaustive` on singleton groups, `assign_exhaustive` and `assign`; and
+    `search_range` at the k-th score of `search` returns `search`'s first k bit for bit.
+
+    257 rows: two tiles, the second holding one row.  D = 520 fp16 / 264 fp32: 9 K steps, the last ragged, so the 8-step
+    stage loop runs a second, short stage, the lanes of the wave-per-candidate re-scores wrap, and the zero padding is
+    summed.  9 queries / centroids: a second, partial group of 8 in the staged kernels, a third group in the list search."""
+    from imagescry_amd import EmbeddingBank
+
+    n, nq, k = 257, GQ + 1, 5
+    vec = _vectors(n, d, dtype, 61)
+    eb = EmbeddingBank(vec.to(device), dtype=dtype, normalize=False, row_groups=torch.arange(n))
+    q = _queries(nq, d, F32 if dtype == F16 else F16, False, 62, device)
+    table = eb.scores(q, torch.arange(n))  # [9, 257]: every pair
+    exact = search_oracle.exact_scores(vec, q.to(dtype).cpu())
+    np.testing.assert_allclose(table.cpu().numpy(), exact, rtol=0, atol=1e-6)
+
+    s, i = eb.search_exhaustive(q, k)
+    np.testing.assert_array_equal(_bits(table.gather(1, i)), _bits(s), err_msg="search_exhaustive")
+    gs, gi, gl = eb.search_groups_exhaustive(q, k)
+    assert torch.equal(gi, i) and torch.equal(gl, i)  # every row its own group, labelled by its index
+    np.testing.assert_array_equal(_bits(gs), _bits(s), err_msg="search_groups_exhaustive")
+
+    # the queries as centroids: per row the best of its column (score desc, ties to the lower centroid) and that entry
+    best = table.max(dim=0).values
+    first = torch.where(table == best, torch.arange(nq, device=device)[:, None], nq).min(dim=0).values
+    for what, fn in (("assign_exhaustive", eb.assign_exhaustive), ("assign", eb.assign)):
+        labels, sc = fn(q)
+        assert torch.equal(labels.long(), first), what
+        np.testing.assert_array_equal(_bits(sc), _bits(best), err_msg=what)
+
+    ss, si = eb.search(q, k)
+    res = eb.search_range(q, ss[:, k - 1].contiguous())
+    assert bool((res.counts >= k).all())
+    for qi in range(nq):
+        rs, ri = res[qi]
+        assert torch.equal(ri[:k], si[qi]) and torch.equal(rs[:k].view(torch.int32), ss[qi].view(torch.int32)), qi
 
 
 def _drop_self(s: torch.Tensor, i: torch.Tensor, own: torch.Tensor) -> tuple[np.ndarray, np.ndarray]:
