@@ -25,6 +25,7 @@ ISC_U8, ISC_F16, ISC_F32 = 0, 1, 2
 ISC_ACT_NONE, ISC_ACT_RELU, ISC_ACT_GELU, ISC_ACT_SILU, ISC_ACT_SIGMOID = 0, 1, 2, 3, 4
 ISC_ACT_RESIDUAL_AFTER = 0x100
 ISC_TOPK_MAX_K = 120
+ISC_TOPK_LARGE_MAX_K = 4096  # isc_cosine_topk_large / isc_cosine_topk_exhaustive_large
 ISC_SEARCH_MAX_D = 8192
 ISC_SEARCH_PASS_QUERIES = 1024  # queries per pass of isc_cosine_topk (the workspace is sized for one pass)
 ISC_ABI_VERSION = 4
@@ -193,6 +194,20 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
         c_int,
         [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p,
          c_void_p, c_size_t, c_void_p],
+    ),
+    "isc_cosine_topk_large_workspace_bytes": (c_int, [c_int, c_int64, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "isc_cosine_topk_large": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "isc_cosine_topk_exhaustive_large_workspace_bytes": (
+        c_int, [c_int, c_int64, c_int, c_int, c_int, POINTER(c_size_t)]
+    ),
+    "isc_cosine_topk_exhaustive_large": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p,
+         c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
     "isc_cosine_range_workspace_bytes": (c_int, [c_int, c_int64, c_int, c_int, c_int64, POINTER(c_size_t)]),
     "isc_cosine_range": (

@@ -11,8 +11,6 @@
 
 namespace {
 
-constexpr int EX_THREADS = 512;
-constexpr int EX_WAVES = EX_THREADS / 64;
 constexpr int EX_MAX_CHUNKS = 256;
 constexpr int EX_PASS = 1024;  // listed queries per pass of isc_cosine_topk_exhaustive
 
@@ -23,48 +21,6 @@ int ex_chunks(int64_t n, int k) {
     if (want > EX_MAX_CHUNKS) want = EX_MAX_CHUNKS;
     if (want > ntiles) want = (int)ntiles;
     return want;
-}
-
-// More than 64 KiB of dynamic LDS needs the opt-in, once per kernel AND device (a process may drive several GPUs):
-// `attr_done` is the kernel's mask with one bit per device id, set only after the call succeeded; a failure is reported,
-// not discarded.
-int ex_lds_opt_in(const void* kernel, unsigned long long& attr_done) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return ISC_ERR_NO_DEVICE;
-    const bool tracked = dev >= 0 && dev < 64;
-    if (!tracked || !((__atomic_load_n(&attr_done, __ATOMIC_RELAXED) >> dev) & 1ull)) {
-        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return ISC_ERR_UNSUPPORTED;
-        }
-        if (tracked) __atomic_fetch_or(&attr_done, 1ull << dev, __ATOMIC_RELAXED);
-    }
-    return ISC_OK;
-}
-
-// ---- what k_exact and k_exact_collapse share: the staged form of exact_dots.h with the listed queries whole in LDS ----
-// listed queries redo_list[g0 .. g0 + gn) -> qd[GQ][dp] (no barrier)
-template <typename T, int GQ>
-__device__ __forceinline__ void ex_stage_group(const void* __restrict__ queries, int q_f32, int64_t ldq, int d, int dp,
-                                               const int32_t* __restrict__ redo_list, int g0, int gn,
-                                               double* __restrict__ qd) {
-    isc_stage_queries<T, GQ, EX_THREADS>(queries, q_f32, ldq, d, gn, 0, dp, dp, qd,
-                                         [&](int g) { return g < gn ? redo_list[g0 + g] : 0; });
-}
-
-// the denominators of the staged group (wave g sums query g); called after the barrier that ends the staging, ends with one
-template <int GQ>
-__device__ __forceinline__ void ex_group_denoms(const double* __restrict__ qd, int dp, double (&denom)[GQ]) {
-    static_assert(GQ <= EX_WAVES, "wave g sums the norm of query g");
-    __shared__ double denom_sh[GQ];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (wave < GQ) {
-        const double dn = isc_norm_denom(isc_norm_partial(qd + (size_t)wave * dp, dp, 0.0));
-        if (lane == 0) denom_sh[wave] = dn;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int g = 0; g < GQ; ++g) denom[g] = denom_sh[g];
 }
 
 // Publish this workgroup's partial lists and tell whether it is the last of `chunks` to arrive: the last one merges

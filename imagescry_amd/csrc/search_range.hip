@@ -32,24 +32,17 @@
 // Its zero queries with t <= 0 take the scan as well: it collects every ALLOWED row (all score 0), and the sort puts them
 // in row order, so their segments need no row-order fill.
 //
+// k_range_pack, k_range_filter, k_range_rescore, the threshold (range_tau) and the sort live in range_kernels.h: the large-k
+// top-k search (search_large.hip) runs them behind a threshold it derives itself.
+//
 // If the candidates outgrow `capacity` the counter keeps counting, every later stage sees empty segments, and the caller
 // learns the exact size to re-issue with from `needed`.
-#include <math.h>
-
-#include <rocprim/device/device_segmented_radix_sort.hpp>
-
-#include "bank_layout.h"
-#include "isc_common.h"
-#include "search_common.h"
+#include "range_kernels.h"
 
 namespace {
 
-
-constexpr int RQT = 64;                          // queries per filter workgroup (one query tile)
 constexpr int RPASS = ISC_SEARCH_PASS_QUERIES;   // queries per pass: the workspace holds one pass's packed queries
 constexpr int64_t R_MAX_CAPACITY = 0x7fffffff;   // the segmented sort counts items in int
-
-enum : int32_t { MODE_FILTER = 0, MODE_SCAN = 1, MODE_NONE = 2, MODE_ALL = 3 };
 
 struct RangeWs {
     unsigned char* qpacked;           // [qpad][ks] x 128 B: one pass's queries, packed
@@ -76,25 +69,6 @@ struct RangeWs {
     size_t sort_bytes;
     size_t bytes;
 };
-
-// rocPRIM's default segmented sort for this architecture (it has no tuned gfx950 entry: 6 radix bits, 128 x 17 items,
-// warp sorts of 32 x 4 and 32 x 4) with the partitioning of segments by size switched off.  With partitioning the sort
-// reads the segment counts back to the host (hipMemcpyWithStream) once a call has 3000 segments or more, i.e. a range
-// search of >= 3000 queries would synchronise the host and could not be captured into a hipGraph.
-using SortConfig = rocprim::segmented_radix_sort_config<6, rocprim::kernel_config<128, 17>,
-                                                        rocprim::WarpSortConfig<32, 4, 256, 0xffffffffu, 32, 4, 256>, true>;
-
-hipError_t sort_keys_desc(void* tmp, size_t& bytes, const unsigned long long* in, unsigned long long* out, int64_t cap,
-                          int q, const int64_t* begin, const int64_t* end, hipStream_t stream) {
-    return rocprim::segmented_radix_sort_keys_desc<SortConfig>(tmp, bytes, in, out, (unsigned)cap, (unsigned)q, begin, end,
-                                                               0, 64, stream);
-}
-
-size_t sort_temp_bytes(int q, int64_t cap) {
-    size_t bytes = 0;
-    if (sort_keys_desc(nullptr, bytes, nullptr, nullptr, cap, q, nullptr, nullptr, (hipStream_t)0) != hipSuccess) return 0;
-    return bytes;
-}
 
 RangeWs carve(int ks, int q, int64_t cap, void* base) {
     RangeWs w{};
@@ -134,27 +108,6 @@ RangeWs carve(int ks, int q, int64_t cap, void* base) {
     return w;
 }
 
-// Wave-aggregated append: `cnt` entries of this lane go to slots [base + prefix, ...) of the candidate buffer; one atomic
-// per wave.  Returns this lane's first slot (every lane of the wave must call it).
-__device__ __forceinline__ unsigned long long wave_reserve(int cnt, unsigned long long* __restrict__ count) {
-    const int lane = threadIdx.x & 63;
-    int incl = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    const int total = __shfl(incl, 63, 64);
-    unsigned long long base = 0;
-    if (lane == 0 && total > 0) base = atomicAdd(count, (unsigned long long)total);
-    const unsigned lo = __shfl((unsigned)base, 0, 64), hi = __shfl((unsigned)(base >> 32), 0, 64);
-    return (((unsigned long long)hi << 32) | lo) + (unsigned long long)(incl - cnt);
-}
-
-__device__ __forceinline__ const unsigned char* qrow_of(const unsigned char* qpacked, int w, int ks) {
-    return qpacked + ((size_t)(w / RQT) * ks * RQT + (w % RQT)) * ISC_KSTEP_BYTES;
-}
-
 __global__ __launch_bounds__(256) void k_range_init(int q, int32_t* __restrict__ mode, int32_t* __restrict__ qcount,
                                                     int32_t* __restrict__ fill, unsigned long long* __restrict__ count,
                                                     unsigned long long* __restrict__ all_rows,
@@ -171,35 +124,6 @@ __global__ __launch_bounds__(256) void k_range_init(int q, int32_t* __restrict__
         *all_count = 0;
     }
     if (i0 < 4) status[i0] = 0;
-}
-
-// queries [qb][ldq] of TQ -> packed [qtile][K step][64 rows][128 B] of T (rows >= qb and columns >= d are zero); float32 ->
-// fp16 rounds to nearest even, as k_prep of cosine_topk.hip does.  Thread 0 also opens the pass.
-template <typename T, typename TQ>
-__global__ __launch_bounds__(256) void k_range_pack(const TQ* __restrict__ queries, int64_t ldq, int qb, int d, int ks,
-                                                    int qpad, unsigned char* __restrict__ packed,
-                                                    int32_t* __restrict__ fb_count,
-                                                    unsigned long long* __restrict__ pass_begin,
-                                                    const unsigned long long* __restrict__ count) {
-    constexpr int PER = 16 / (int)sizeof(T);
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i == 0) {
-        *fb_count = 0;
-        *pass_begin = *count;
-    }
-    if (i >= qpad * ks * 8) return;
-    const int c = i & 7;
-    const int row = (i >> 3) % RQT;
-    const int blk = (i >> 3) / RQT;  // qtile * ks + kstep
-    const int kstep = blk % ks;
-    const int qrow = (blk / ks) * RQT + row;
-    T v[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int e = (kstep * 8 + c) * PER + j;
-        v[j] = (qrow < qb && e < d) ? (T)queries[(int64_t)qrow * ldq + e] : (T)0.f;
-    }
-    *reinterpret_cast<uint4*>(packed + (size_t)i * 16) = *reinterpret_cast<const uint4*>(v);
 }
 
 // One wave per query slot of the pass: norm, mode, threshold (see the file header).  MASK: a masked call, whose all-row
@@ -239,16 +163,7 @@ __global__ __launch_bounds__(256) void k_range_qinfo(const unsigned char* __rest
         m = MODE_SCAN;  // outside the range where eps bounds the filter (a NaN / inf bound included)
     } else {
         m = MODE_FILTER;
-        const double ed = (double)nextafterf(t, -INFINITY) * denom;
-        const double t2 = ed - eps - fabs(ed) * 1e-12;
-        if (t2 > 3.0e38) {
-            tf = INFINITY;  // above every filter score and every reachable dot (|E| <= 1e37): nothing can pass
-        } else if (t2 < -3.0e38) {
-            tf = -INFINITY;  // every row (the filter scores of a trusted query are finite)
-        } else {
-            tf = (float)t2;
-            if ((double)tf >= t2) tf = nextafterf(tf, -INFINITY);
-        }
+        tf = range_tau(t, denom, eps);
     }
     tau[w] = tf;
     denom_out[w] = denom;
@@ -262,128 +177,6 @@ __global__ __launch_bounds__(256) void k_range_qinfo(const unsigned char* __rest
         qcount[qg] = (int32_t)n;
         atomicAdd(all_rows, (unsigned long long)n);
     }
-}
-
-// One workgroup = one 256-row bank tile x one 64-query tile; wave w owns rows 64 w .. 64 w + 63 of the tile (4 x 4 blocks of
-// 16 x 16 scores).  Fragments come straight from global memory (the bank tile's K step is 32 KiB of contiguous HBM, a
-// wave's share 8 KiB), one K step ahead of the matrix cores; consecutive workgroups are the query tiles of one bank tile,
-// so a bank tile read by several of them is served from L2.  Scores above tau are appended (wave_reserve); with a row filter
-// (RowMask, search_common.h) only those of allowed rows.
-template <typename T, typename... RowMask>
-__global__ __launch_bounds__(256) void k_range_filter(const unsigned char* __restrict__ bank, int64_t n, int ks, int nqt,
-                                                      const unsigned char* __restrict__ qpacked,
-                                                      const float* __restrict__ tau, int q0,
-                                                      unsigned long long* __restrict__ count, int64_t capacity,
-                                                      int32_t* __restrict__ cand_q, int32_t* __restrict__ cand_r,
-                                                      float* __restrict__ cand_a, RowMask... row_mask) {
-    const int64_t tile = blockIdx.x / nqt;
-    const int qt = blockIdx.x % nqt;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r16 = lane & 15, grp = lane >> 4;
-    // MFMA operand fragments: lane (r16, grp) feeds row r16 of a 16-row block, chunk grp (first half of the K step) and
-    // chunk 4 + grp (second half); the same K permutation on both operands leaves the dots unchanged
-    const unsigned char* a_base = bank + ((tile * ks * ISC_TILE_ROWS) + wave * 64 + r16) * ISC_KSTEP_BYTES + grp * 16;
-    const unsigned char* b_base = qpacked + ((size_t)qt * ks * RQT + r16) * ISC_KSTEP_BYTES + grp * 16;
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) acc[m][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto load = [&](int s, u32x4 (&av)[4][2], u32x4 (&bv)[4][2]) {
-        const unsigned char* ap = a_base + (size_t)s * ISC_TILE_KSTEP_BYTES;
-        const unsigned char* bp = b_base + (size_t)s * RQT * ISC_KSTEP_BYTES;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            av[m][0] = *reinterpret_cast<const u32x4*>(ap + m * 16 * ISC_KSTEP_BYTES);
-            av[m][1] = *reinterpret_cast<const u32x4*>(ap + m * 16 * ISC_KSTEP_BYTES + 64);
-            bv[m][0] = *reinterpret_cast<const u32x4*>(bp + m * 16 * ISC_KSTEP_BYTES);
-            bv[m][1] = *reinterpret_cast<const u32x4*>(bp + m * 16 * ISC_KSTEP_BYTES + 64);
-        }
-    };
-    auto mma = [&](const u32x4 (&av)[4][2], const u32x4 (&bv)[4][2]) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int nb = 0; nb < 4; ++nb) Mma<T>::step(av[m][h], bv[nb][h], acc[m][nb]);
-    };
-    u32x4 a0[4][2], b0[4][2], a1[4][2], b1[4][2];
-    load(0, a0, b0);
-    for (int s = 0; s < ks; s += 2) {
-        if (s + 1 < ks) load(s + 1, a1, b1);
-        mma(a0, b0);
-        if (s + 1 >= ks) break;
-        if (s + 2 < ks) load(s + 2, a0, b0);
-        mma(a1, b1);
-    }
-
-    // acc[m][nb][j] = score of bank row 16 m + 4 grp + j (of this wave's 64) with query 16 nb + r16 of the tile
-    const int64_t row0 = tile * ISC_TILE_ROWS + wave * 64 + grp * 4;
-    // row filter: disallowed rows score -inf, which no tau lets through ("A > tau" is false even for tau = -inf).  This
-    // wave's 64 rows are two words; row 16 m + 4 grp + j is bit 16 (m & 1) + 4 grp + j of word m / 2.
-    if constexpr (sizeof...(RowMask) > 0) {
-        const uint32_t* mb = isc_row_mask_ptr(row_mask...);  // (NULL only in a grouped call without a row filter)
-        if (!isc_grouped<RowMask...>() || mb != nullptr) {
-            const uint32_t* mw = mb + tile * (ISC_TILE_ROWS / 32) + wave * 2;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const uint32_t nib = mw[m >> 1] >> ((m & 1) * 16 + grp * 4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (!((nib >> j) & 1u)) {
-#pragma unroll
-                        for (int nb = 0; nb < 4; ++nb) acc[m][nb][j] = -INFINITY;
-                    }
-            }
-        }
-    }
-    // group exclusion: a row of the query's own group scores -inf for that query.  Row 16 m + 4 grp + j's code is element j
-    // of one 16-byte load per m; query column 16 nb + r16's code is read once.
-    if constexpr (isc_grouped<RowMask...>()) {
-        const IscGroups& gr = (row_mask, ...);
-        int qc[4];
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) qc[nb] = isc_query_code(gr, q0 + qt * RQT + nb * 16 + r16);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const i32x4 rc = *reinterpret_cast<const i32x4*>(gr.row_group + row0 + m * 16);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int nb = 0; nb < 4; ++nb)
-                    if (rc[j] == qc[nb]) acc[m][nb][j] = -INFINITY;
-        }
-    }
-    float tq[4];
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) tq[nb] = tau[qt * RQT + nb * 16 + r16];
-    int cnt = 0;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) cnt += (row0 + m * 16 + j < n && acc[m][nb][j] > tq[nb]) ? 1 : 0;
-    if (__ballot(cnt > 0) == 0ull) return;
-    unsigned long long pos = wave_reserve(cnt, count);
-    if (cnt == 0) return;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int64_t row = row0 + m * 16 + j;
-                if (row < n && acc[m][nb][j] > tq[nb]) {
-                    if (pos < (unsigned long long)capacity) {
-                        cand_q[pos] = q0 + qt * RQT + nb * 16 + r16;
-                        cand_r[pos] = (int32_t)row;
-                        cand_a[pos] = acc[m][nb][j];
-                    }
-                    ++pos;
-                }
-            }
 }
 
 // The float64 scan of the queries the filter cannot serve: one thread per bank row, the whole bank per listed query.  A row
@@ -424,53 +217,6 @@ __global__ __launch_bounds__(256) void k_range_scan(const unsigned char* __restr
                 cand_q[pos] = q0 + w;
                 cand_r[pos] = (int32_t)row;
                 cand_a[pos] = (float)e;
-            }
-        }
-    }
-}
-
-// Every candidate of the pass re-scored in float64, one wave per candidate: the packed-row form of exact_dots.h with the
-// top-k's lane mapping, so E is bit for bit the top-k's and a range result and a top-k result agree on every score.
-template <typename T>
-__global__ __launch_bounds__(256) void k_range_rescore(const unsigned char* __restrict__ bank, int ks,
-                                                       const unsigned char* __restrict__ qpacked, int q0,
-                                                       const unsigned long long* __restrict__ pass_begin,
-                                                       const unsigned long long* __restrict__ count, int64_t capacity,
-                                                       int32_t* __restrict__ cand_q, const int32_t* __restrict__ cand_r,
-                                                       float* __restrict__ cand_a, const double* __restrict__ denom,
-                                                       const double* __restrict__ eps, const int32_t* __restrict__ mode,
-                                                       const float* __restrict__ min_score, int32_t* __restrict__ qcount,
-                                                       int32_t* __restrict__ status) {
-    const unsigned long long end = *count;
-    if (end > (unsigned long long)capacity) return;  // the call has overflowed: nothing of it is usable
-    const int lane = threadIdx.x & 63;
-    const int sub = lane >> 3, ch = lane & 7;
-    const unsigned long long nw = (unsigned long long)gridDim.x * 4;
-    for (unsigned long long c = *pass_begin + blockIdx.x * 4 + (threadIdx.x >> 6); c < end; c += nw) {
-        const int qg = cand_q[c];
-        const int w = qg - q0;
-        const int64_t row = cand_r[c];
-        const unsigned char* qrow = qrow_of(qpacked, w, ks);
-        double acc = 0.0;
-        for (int s0 = 0; s0 < ks; s0 += 8) {
-            const int s = s0 + sub;
-            if (s < ks)
-                acc = isc_packed_dot<T>(bank + isc_packed_offset(row, s, ks) + ch * 16,
-                                        qrow + (size_t)s * RQT * ISC_KSTEP_BYTES + ch * 16, acc);
-        }
-        const double e = isc_wave_sum(acc);
-        if (lane == 0) {
-            // how far the filter scores are from the exact dots, in units of the bound (status[2], diagnostics)
-            if (mode[qg] == MODE_FILTER && eps[w] > 0.0) {
-                const float ratio = (float)(fabs((double)cand_a[c] - e) / eps[w]);
-                if (ratio == ratio) atomicMax(reinterpret_cast<unsigned*>(&status[2]), __float_as_uint(ratio));
-            }
-            const float sc = (float)(e / denom[w]);
-            if (sc >= min_score[qg]) {
-                cand_a[c] = sc;
-                atomicAdd(&qcount[qg], 1);
-            } else {
-                cand_q[c] = -1;
             }
         }
     }
@@ -557,11 +303,6 @@ __global__ __launch_bounds__(256) void k_range_emit(int q, const int64_t* __rest
         scores[i] = isc_key_score(k);
         indices[i] = (int64_t)isc_key_row(k) + index_base;
     }
-}
-
-int grid_for(int64_t items, int per_block, int cap) {
-    const int64_t b = (items + per_block - 1) / per_block;
-    return (int)(b < 1 ? 1 : b > cap ? cap : b);
 }
 
 template <typename T, typename TQ, typename... RowMask>

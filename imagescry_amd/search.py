@@ -1019,7 +1019,11 @@ class EmbeddingBank:
         if ws is None:
             lib = _lib.load()
             need = _lib.c_size_t()
-            if collapse:
+            if k > _lib.ISC_TOPK_MAX_K:  # the large-k search (its passes shrink as k grows: O(queries per pass x k))
+                st = lib.isc_cosine_topk_large_workspace_bytes(_lib.dtype_code(self.dtype), self.capacity, self.dim,
+                                                               key[0], k, need)
+                _lib.check(st, "isc_cosine_topk_large_workspace_bytes")
+            elif collapse:
                 st = lib.isc_cosine_topk_collapse_workspace_bytes(
                     _lib.dtype_code(self.dtype), self.capacity, self.dim, min(key[0], _lib.ISC_SEARCH_PASS_QUERIES),
                     k, max(self._max_group_rows, 1), need)
@@ -1102,7 +1106,8 @@ class EmbeddingBank:
         nq = queries.shape[0]
         scores, indices, status = out if out is not None else self._new_out(nq, k)
         ws = self._workspace(nq, k, lane)
-        shadow = self._shadow_for(nq, k) if mask is None and groups is None else None
+        large = k > _lib.ISC_TOPK_MAX_K  # isc_cosine_topk_large: one entry point for the three filters, no shadow
+        shadow = self._shadow_for(nq, k) if mask is None and groups is None and not large else None
         if stream is not None:
             # every tensor this call touches was allocated on some other stream: tell the allocator the lane uses it, so
             # that nothing handed back early (a dropped handle, a dropped bank, a workspace bucket pushed out of the cache)
@@ -1127,16 +1132,31 @@ class EmbeddingBank:
         )
         if shadow is not None:
             args += (shadow.data_ptr(),)
-        self._row_search("isc_cosine_topk_shadow" if shadow is not None else "isc_cosine_topk", args, mask, groups,
-                         stream.cuda_stream if stream is not None else _lib.stream_handle(self.device))
+        handle = stream.cuda_stream if stream is not None else _lib.stream_handle(self.device)
+        if large:
+            self._large_search("isc_cosine_topk_large", args, mask, groups, handle)
+        else:
+            self._row_search("isc_cosine_topk_shadow" if shadow is not None else "isc_cosine_topk", args, mask, groups,
+                             handle)
         self.last_status = status
         return scores, indices
+
+    def _large_search(self, name: str, args: tuple, mask: RowFilter | None, groups: Tensor | None, stream: int) -> None:
+        """One large-k call of the C ABI (120 < k <= `ISC_TOPK_LARGE_MAX_K`) on `stream`: `name` takes the row filter's
+        bitmap, the packed row codes and the query codes behind `args`, each NULL when the search has no such filter."""
+        with torch.cuda.device(self.device):
+            st = getattr(_lib.load(), name)(
+                *args, None if mask is None else mask.packed.data_ptr(),
+                None if groups is None else self._row_codes.data_ptr(), None if groups is None else groups.data_ptr(),
+                stream)
+        _lib.check(st, name)
 
     def search_exhaustive(self, queries: Tensor, k: int = 10, *, mask: "RowFilter | Tensor | None" = None,
                           exclude_group: Tensor | None = None) -> tuple[Tensor, Tensor]:
         """The same answer from the data-independent float64 kernel (`isc_cosine_topk_exhaustive`): every score of
         every query evaluated exactly.  Slow; the on-device reference the fast path is tested against.  `mask`,
-        `exclude_group`: as in `search`."""
+        `exclude_group`: as in `search`.  `k` up to `ISC_TOPK_LARGE_MAX_K`: above 120 the same scores are selected by a
+        radix select over the bank (`isc_cosine_topk_exhaustive_large`: nine sweeps per four queries)."""
         rf = self._as_filter(mask)
         q = self._prepare_queries(queries)
         nq = q.shape[0]
@@ -1145,13 +1165,15 @@ class EmbeddingBank:
             raise ValueError("search_exhaustive answers for one shard; merge the shards with search()")
         if not 1 <= k <= self.num_local_rows:
             raise ValueError(f"k={k} must be in [1, {self.num_local_rows}]")
+        if k > _lib.ISC_TOPK_LARGE_MAX_K:
+            raise ValueError(f"k must be <= {_lib.ISC_TOPK_LARGE_MAX_K}, got {k}")
         lib = _lib.load()
         code = _lib.dtype_code(self.dtype)
         need = _lib.c_size_t()
-        _lib.check(
-            lib.isc_cosine_topk_exhaustive_workspace_bytes(code, self.capacity, self.dim, nq, k, need),
-            "isc_cosine_topk_exhaustive_workspace_bytes",
-        )
+        # beyond ISC_TOPK_MAX_K: the radix-select form of the same sweep (isc_cosine_topk_exhaustive_large)
+        base = "isc_cosine_topk_exhaustive" + ("_large" if k > _lib.ISC_TOPK_MAX_K else "")
+        _lib.check(getattr(lib, base + "_workspace_bytes")(code, self.capacity, self.dim, nq, k, need),
+                   base + "_workspace_bytes")
         ews = torch.empty(need.value, dtype=torch.uint8, device=self.device)
         scores = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         indices = torch.empty((nq, k), dtype=torch.int64, device=self.device)
@@ -1159,7 +1181,10 @@ class EmbeddingBank:
             self._bank.data_ptr(), code, self.capacity, self.dim, q.data_ptr(), _lib.dtype_code(q.dtype), nq,
             q.stride(0), k, self.index_base, scores.data_ptr(), indices.data_ptr(), ews.data_ptr(), ews.numel(),
         )
-        self._row_search("isc_cosine_topk_exhaustive", args, rf, qg, _lib.stream_handle(self.device))
+        if k > _lib.ISC_TOPK_MAX_K:
+            self._large_search(base, args, rf, qg, _lib.stream_handle(self.device))
+        else:
+            self._row_search(base, args, rf, qg, _lib.stream_handle(self.device))
         return (scores, indices) if rf is None and qg is None else _unpad(scores, indices)
 
     def _merge_topk(self, scores: Tensor, indices: Tensor, k: int) -> tuple[Tensor, Tensor]:
@@ -1210,6 +1235,14 @@ class EmbeddingBank:
         is the masked search of the rows it may return, bit for bit, padded as above; a label no row carries excludes
         nothing.  The labels become codes on the device, so a grouped search stays capturable.
 
+        `k` may be up to `ISC_TOPK_LARGE_MAX_K` = 4096 on an unsharded bank.  Above `ISC_TOPK_MAX_K` = 120 the call is
+        `isc_cosine_topk_large` ("Top-k beyond 120"): a matrix-core pass proves a lower bound of each query's
+        k-th score, the range search's filter, float64 re-score and sort run behind it, and the first k rows are the
+        answer -- the same contract, filters and padding, about one pass over the bank more than `search_range` at the k-th
+        score.  `last_status` then holds [0] passes whose candidate buffer overflowed, [1] queries answered by the float64
+        last resort (`search_exhaustive`'s kernels), [2] the largest filter error over its bound (float bits, < 1),
+        [3] candidates the filter kept.  The int8 shadow is not used there.
+
         A world-1 `search` may be captured into a CUDA / HIP graph (`torch.cuda.graph`) and replayed.  The workspace a
         capture used stays allocated for the bank's lifetime so that replays stay valid: each distinct (query bucket, k)
         captured pins one `isc_cosine_topk_workspace_bytes` buffer -- up to a few hundred MB on a large bank -- until the
@@ -1259,7 +1292,11 @@ class EmbeddingBank:
         """`query_codes`: the int32 `[Q]` codes of the queries' groups themselves, in place of `exclude_group` labels
         (`search_rows` reads them from the stored codes)."""
         rf = self._as_filter(mask)
-        self._check_k(k)
+        self._check_k(k, _lib.ISC_TOPK_LARGE_MAX_K)
+        if k > _lib.ISC_TOPK_MAX_K and self.process_group is not None:
+            # (isc_topk_merge holds at most 4096 inputs per query: G shards of k > 120 candidates do not fit)
+            raise ValueError(f"a sharded bank searches k <= {_lib.ISC_TOPK_MAX_K}, got {k}: the merge of the shards' "
+                             "lists has no large-k form")
         q = self._prepare_queries(queries)
         nq = q.shape[0]
         filt = self._filter_kwargs(rf, self._query_codes(exclude_group, nq) if query_codes is None else query_codes)
@@ -1732,13 +1769,14 @@ class EmbeddingBank:
         _lib.check(st, "isc_topk_merge_groups")
         return out_s, out_i, out_l
 
-    def _check_k(self, k: int) -> None:
+    def _check_k(self, k: int, limit: int = _lib.ISC_TOPK_MAX_K) -> None:
+        """`limit`: `ISC_TOPK_MAX_K`, or `ISC_TOPK_LARGE_MAX_K` for the calls that have a large-k path."""
         if not isinstance(k, int) or isinstance(k, bool):
             raise TypeError(f"k must be an int, got {type(k).__name__}")
         if k < 1:
             raise ValueError(f"k must be >= 1, got {k}")
-        if k > _lib.ISC_TOPK_MAX_K:
-            raise ValueError(f"k must be <= {_lib.ISC_TOPK_MAX_K}, got {k}")
+        if k > limit:
+            raise ValueError(f"k must be <= {limit}, got {k}")
 
     @staticmethod
     def _filter_kwargs(rf: RowFilter | None, qg: Tensor | None) -> dict[str, object]:

@@ -548,6 +548,43 @@ int isc_cosine_topk_exhaustive_grouped(const void* bank, int dtype, int64_t N, i
                                        const uint32_t* row_mask, const int32_t* row_group, const int32_t* query_group,
                                        void* stream);
 
+/* Exact top-k beyond ISC_TOPK_MAX_K: 1 <= k <= min(N, ISC_TOPK_LARGE_MAX_K).  Semantics, ordering, query rounding,
+ * index_base and padding are those of isc_cosine_topk_masked / isc_cosine_topk_grouped: score float32(dot_f64 / max(||q||,
+ * 1e-12)), order (score descending, original row ascending, NaN last), a query with fewer than k rows it may return padded
+ * with score NaN, index INT64_MAX.  One entry point for the three filters:
+ *   row_mask     the packed row filter (isc_row_mask_pack), or NULL: every row is allowed
+ *   row_group, query_group   both NULL, or the packed row codes and the int32 [Q] query codes of isc_cosine_topk_grouped
+ * The selection does not live in LDS (search_large.hip): a matrix-core pass over the bank proves a lower bound of every
+ * query's k-th score on the device, the range search's filter, float64 re-score and segmented sort run behind that bound,
+ * and the first k rows of each query's list are the answer -- the first k rows isc_cosine_range returns for the k-th score
+ * as threshold, bit for bit.  Queries that path cannot prove (a scale where the filter's error bound does not hold, a NaN /
+ * inf norm_bound, a zero or non-finite query, a pass whose candidate buffer overflowed: thousands of rows tied around the
+ * k-th score) are answered on the device by isc_cosine_topk_exhaustive_large's kernels.  The result is FINAL when the stream
+ * has run the call; no host synchronisation; the workspace's contents on entry do not matter; the call may be captured.
+ * Calls run as passes of min(1024, max(64, 2^20 / k)) queries over one workspace, whose size is O(queries per pass x k) and
+ * does not grow with N.
+ *   status       int32_t [4] device words, diagnostics only: [0] = passes whose candidate buffer overflowed, [1] = queries
+ *                answered by the float64 last resort, [2] = float bits of max |filter score - exact dot| / eps over the
+ *                re-scored candidates (must stay < 1), [3] = candidates the filter kept, summed over the passes and
+ *                saturating at INT32_MAX (about 1.1 - 1.4 k per query on a bank in random order)
+ *
+ * isc_cosine_topk_exhaustive_large: the same contract at data-independent cost and with a fixed launch sequence, the
+ * scores those of isc_cosine_topk_exhaustive bit for bit: every score of every query in float64, the k-th (score, row) key
+ * found by an 8-round radix select (one bank sweep per round and four queries), the k rows at or above it collected and
+ * sorted.  Memory O(queries per pass x k).  The reference implementation of the large search on the device. */
+#define ISC_TOPK_LARGE_MAX_K 4096
+int isc_cosine_topk_large_workspace_bytes(int dtype, int64_t N, int D, int Q, int k, size_t* bytes);
+int isc_cosine_topk_large(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype, int Q,
+                          int64_t ldq, int k, int64_t index_base, const float* norm_bound, float* out_scores,
+                          int64_t* out_indices, int32_t* status, void* workspace, size_t workspace_bytes,
+                          const uint32_t* row_mask, const int32_t* row_group, const int32_t* query_group, void* stream);
+int isc_cosine_topk_exhaustive_large_workspace_bytes(int dtype, int64_t N, int D, int Q, int k, size_t* bytes);
+int isc_cosine_topk_exhaustive_large(const void* bank, int dtype, int64_t N, int D, const void* queries, int q_dtype,
+                                     int Q, int64_t ldq, int k, int64_t index_base, float* out_scores,
+                                     int64_t* out_indices, void* workspace, size_t workspace_bytes,
+                                     const uint32_t* row_mask, const int32_t* row_group, const int32_t* query_group,
+                                     void* stream);
+
 /* The scores of chosen rows: scores[q, j] = the score of query q against ORIGINAL row rows[j] of the image laid out for
  * `capacity` rows, float32(dot_f64(q, b) / max(||q||_2, 1e-12)) with the query rounded to the bank dtype first -- computed
  * with isc_cosine_topk_exhaustive's operations in its order, so the bits are the ones that call returns for the pair.  The
