@@ -5,7 +5,8 @@ Public surface (same names as the reference where the reference has them):
 * `ImageBatch`, `EmbeddingBatch`                 -- reference src/imagescry/data.py:29-144
 * `resize`, `normalize_per_channel`, `to_4d`     -- reference src/imagescry/image/transforms.py
 * `EmbeddingModule`, `EfficientNetEmbedder`,
-  `ResNet50Embedder`, `ViTB16Embedder`           -- reference src/imagescry/models/embedding.py:27-183
+  `ResNet50Embedder`, `ViTB16Embedder`,
+  `DINOv2Embedder`                               -- reference src/imagescry/models/embedding.py:27-183
 * `PCA`, `EmbeddingPCAPipeline`                  -- reference src/imagescry/models/decomposition.py, pipelines.py
 * `EmbedSearchPipeline`                          -- encode -> search on two HIP streams (BASELINE config 5; new)
 * `EmbeddingBank`, `RangeResult`, `RowFilter`    -- cosine top-k and range search, optionally over a row filter and
@@ -19,6 +20,7 @@ from imagescry_amd.batching import ImageTensorDataset, SimilarShapeBatcher
 from imagescry_amd.data import EmbeddingBatch, ImageBatch
 from imagescry_amd.decomposition import PCA, KMeans
 from imagescry_amd.embedding import (
+    DINOv2Embedder,
     EfficientNetEmbedder,
     EmbeddingModule,
     ResNet50Embedder,
@@ -30,6 +32,7 @@ from imagescry_amd.search import EmbeddingBank, RangeResult, RowFilter, SearchHa
 from imagescry_amd.transforms import normalize_per_channel, resize, to_4d
 
 __all__ = [
+    "DINOv2Embedder",
     "EfficientNetEmbedder",
     "EmbeddingBank",
     "EmbeddingBatch",

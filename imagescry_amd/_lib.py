@@ -158,6 +158,11 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
         c_int,
         [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p],
     ),
+    "isc_gemm_f16_scaled": (
+        c_int,
+        [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
+         c_void_p],
+    ),
     "isc_layernorm": (
         c_int,
         [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int64, c_int, c_void_p],
@@ -170,6 +175,17 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "isc_vit_pos_resample": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "isc_vit_tokens_out": (
         c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_float, c_void_p, c_void_p]
+    ),
+    "isc_patchify_f16_padded": (
+        c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]
+    ),
+    "isc_vit_assemble_reg": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+    ),
+    "isc_vit_pos_resample_aa": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "isc_vit_tokens_out_skip": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_float, c_void_p, c_void_p],
     ),
     "isc_cosine_topk_workspace_bytes": (c_int, [c_int, c_int64, c_int, c_int, c_int, POINTER(c_size_t)]),
     "isc_cosine_topk": (

@@ -51,7 +51,10 @@ constexpr int A_ST = 3, B_ST = 2;
 constexpr int DA = A_ST - 1, DB = B_ST - 1;
 constexpr int NA = 4, NB = 4;   // LDS-DMA instructions per thread per K step and operand
 
-enum { EPI_F16 = 0, EPI_F16_GELU = 1, EPI_F32 = 2 };
+// EPI_F32_SCALED: EPI_F32 with a per-feature float32 scale between the bias and the residual (LayerScale,
+// isc_gemm_f16_scaled): out = residual + scale[n] * (a . w^T + bias[n])
+enum { EPI_F16 = 0, EPI_F16_GELU = 1, EPI_F32 = 2, EPI_F32_SCALED = 3 };
+constexpr bool epi_f32(int epi) { return epi == EPI_F32 || epi == EPI_F32_SCALED; }
 
 struct StreamGemmParams {
     const unsigned char* a;  // tokens, packed [token tile][K step][row][128 B]
@@ -63,6 +66,7 @@ struct StreamGemmParams {
     int N, ksteps, ntiles, tiles_per_chunk, out_packed;
     int group, ngroups, npairs;  // XCD-aware mapping, see the kernel
     int seg_off, seg_len;        // this launch covers tiles [seg_off, seg_off + seg_len) of every chunk
+    const float* scale;          // [N] (EPI_F32_SCALED only)
 };
 
 #define GS_DS_READ(dst_, addr_, off_) \
@@ -150,7 +154,7 @@ __global__ __launch_bounds__(GTHREADS) void k_gemm_f16_stream(const StreamGemmPa
     // float32 output keeps the NATURAL order (MFMA block n = features 16 n .. 16 n + 15, a lane's four values of block n
     // are features 16 n + 4 fg + j): a store / residual-load instruction then covers 64 contiguous bytes per token row
     // (four lanes x 16 B) instead of four 16-byte pieces 64 bytes apart, which is what the permutation gives it
-    constexpr bool NATURAL = EPI == EPI_F32 && DBG == 0;
+    constexpr bool NATURAL = epi_f32(EPI) && DBG == 0;
     const int wperm = NATURAL ? srow : 16 * ((srow & 15) >> 2) + 4 * (srow >> 4) + (srow & 3);
     const unsigned char* a_stream = p.a + (int64_t)tile_begin * ksteps * TILE_BYTES + srow * 128 + sw16;
     const unsigned char* b_stream = p.w + (int64_t)fb * ksteps * TILE_BYTES + wperm * 128 + sw16;
@@ -224,6 +228,13 @@ __global__ __launch_bounds__(GTHREADS) void k_gemm_f16_stream(const StreamGemmPa
         bias[n] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + nb + NS * n) : f32x4{0.f, 0.f, 0.f, 0.f};
     // the bias loads above are ordinary vector-memory operations: drain them before the DMA ring starts counting
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(bias[0]), "+v"(bias[1]), "+v"(bias[2]), "+v"(bias[3])::"memory");
+    // the scale sits in registers beside the bias, for the same reason
+    f32x4 scale[4];
+    if constexpr (EPI == EPI_F32_SCALED) {
+#pragma unroll
+        for (int n = 0; n < 4; ++n) scale[n] = *reinterpret_cast<const f32x4*>(p.scale + nb + NS * n);
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(scale[0]), "+v"(scale[1]), "+v"(scale[2]), "+v"(scale[3])::"memory");
+    }
 
     f32x4 acc[MB][4];
 #pragma unroll
@@ -253,7 +264,11 @@ __global__ __launch_bounds__(GTHREADS) void k_gemm_f16_stream(const StreamGemmPa
         }
         if constexpr (DBG == 1 || DBG == 3) {
             if (c[0][0] + c[1][1] + c[2][2] + c[3][3] == 123.456f) reinterpret_cast<float*>(p.out)[0] = 1.f;
-        } else if constexpr (EPI == EPI_F32) {
+        } else if constexpr (epi_f32(EPI)) {
+            if constexpr (EPI == EPI_F32_SCALED) {
+#pragma unroll
+                for (int n = 0; n < 4; ++n) c[n] *= scale[n];
+            }
             if (token < p.M) {
                 const size_t o = (size_t)token * p.N + nb;
                 if (p.res) {
@@ -295,7 +310,7 @@ __global__ __launch_bounds__(GTHREADS) void k_gemm_f16_stream(const StreamGemmPa
     // boundary (measured without any epilogue: 0.38 - 0.43 of peak; with all of it at the boundary: 0.17 - 0.34).
     // The float32 + residual epilogue needs loads whose waits would drain the DMA ring eight times per tile; it stays
     // at the boundary (one drain).
-    constexpr bool DEFER = EPI != EPI_F32 && !SPLIT;
+    constexpr bool DEFER = !epi_f32(EPI) && !SPLIT;
 
     auto main_loop = [&](auto stagger_tag) {
     constexpr bool STAGGER = decltype(stagger_tag)::value;
@@ -442,7 +457,7 @@ __global__ __launch_bounds__(GTHREADS) void k_gemm_f16_stream(const StreamGemmPa
             // packed fp16 output (two unconditional stores per row block): leave the 16 stores and the 8 token pieces
             // of step + 2 in flight; otherwise (float32 output: residual loads, predicated stores) drain.
             if (wm == 0) {
-                if (EPI != EPI_F32 && p.out_packed && step + 2 < total_steps) gs_wait_vmcnt<2 * NA + 16>();
+                if (!epi_f32(EPI) && p.out_packed && step + 2 < total_steps) gs_wait_vmcnt<2 * NA + 16>();
                 else gs_wait_vmcnt<0>();
             }
         } else if (drained) {
@@ -485,13 +500,15 @@ static constexpr int gemm_seg_tiles() { return 0; }
 #endif
 
 // Called by isc_gemm_f16 for packed operands with N a multiple of 256.  epi: 0 = fp16 out, 1 = fp16 out with GELU,
-// 2 = float32 out (+ optional float32 residual).
+// 2 = float32 out (+ optional float32 residual), 3 = 2 with `scale` (float32 [N]) applied before the residual.
 int isc_gemm_f16_stream_launch(const void* a, long long M, int K, const void* w, int N, const float* bias,
-                               const float* residual, int epi, void* out, int out_packed, hipStream_t stream) {
+                               const float* scale, const float* residual, int epi, void* out, int out_packed,
+                               hipStream_t stream) {
     StreamGemmParams p;
     p.a = static_cast<const unsigned char*>(a);
     p.w = static_cast<const unsigned char*>(w);
     p.bias = bias;
+    p.scale = scale;
     p.res = residual;
     p.out = out;
     p.M = M;
@@ -521,6 +538,8 @@ int isc_gemm_f16_stream_launch(const void* a, long long M, int K, const void* w,
         if (epi == EPI_F16) hipLaunchKernelGGL((k_gemm_f16_stream<EPI_F16, DBG_, SPLIT_>), grid, block, 0, stream, p);  \
         else if (epi == EPI_F16_GELU)                                                                                   \
             hipLaunchKernelGGL((k_gemm_f16_stream<EPI_F16_GELU, DBG_, SPLIT_>), grid, block, 0, stream, p);             \
+        else if (epi == EPI_F32_SCALED)                                                                                 \
+            hipLaunchKernelGGL((k_gemm_f16_stream<EPI_F32_SCALED, DBG_, SPLIT_>), grid, block, 0, stream, p);           \
         else hipLaunchKernelGGL((k_gemm_f16_stream<EPI_F32, DBG_, SPLIT_>), grid, block, 0, stream, p);                 \
     } while (0)
 #ifdef ISC_ABLATION

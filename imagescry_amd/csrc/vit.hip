@@ -51,6 +51,7 @@ struct GemmParams {
     long long M;
     int N, K, ksteps, act, out_f32;
     int a_packed, w_packed, out_packed;  // operand / fp16 output in the K-step-major tile layout (pk_offset, packed_matrix.h)
+    const float* scale;                  // [N], k_gemm_f16_dma<0, true> only: multiplies (product + bias) before the residual
 };
 
 // byte offset of the first K step of `row`, and the byte distance between consecutive K steps of a row
@@ -96,7 +97,8 @@ __device__ __forceinline__ bool gemm_tile(const GemmParams& p, long long& m0, in
 
 // DBG (ISC_GEMM_DEBUG, bring-up only, wrong results): 1 = no DMA after the prologue, 2 = no fragment reads, 3 = no MFMAs,
 // 4 = no epilogue (nothing stored).
-template <int DBG>
+// SCALED (isc_gemm_f16_scaled, LayerScale): out = residual + scale[n] * (product + bias[n]), float32 out, no activation.
+template <int DBG, bool SCALED = false>
 __global__ __launch_bounds__(256, 2) void k_gemm_f16_dma(const GemmParams p) {
     constexpr int STAGE = 32768;  // [weights 128 rows | activations 128 rows] x 128 B
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * STAGE];
@@ -235,6 +237,14 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16_dma(const GemmParams p) {
         bias[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (p.bias && nb + 4 * mi < p.N) bias[mi] = *reinterpret_cast<const f32x4*>(p.bias + nb + 4 * mi);
     }
+    f32x4 scale[4];
+    if constexpr (SCALED) {
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) {
+            scale[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (nb + 4 * mi < p.N) scale[mi] = *reinterpret_cast<const f32x4*>(p.scale + nb + 4 * mi);
+        }
+    }
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
         const long long m = m0 + wm * 64 + ni * 16 + frow;
@@ -250,7 +260,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16_dma(const GemmParams p) {
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
             v[mi] = acc[mi][ni] + bias[mi];
-            if (p.act == ISC_ACT_GELU) {
+            if constexpr (SCALED) v[mi] *= scale[mi];
+            if (!SCALED && p.act == ISC_ACT_GELU) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[mi][q] = gelu_fast(v[mi][q]);
             }
@@ -821,31 +832,92 @@ __global__ __launch_bounds__(256) void k_patchify_f16(const float* __restrict__ 
     }
 }
 
-// tokens[b][0] = cls + pos[0];  tokens[b][t] = patch_embed[b * (T - 1) + t - 1] + pos[t]
+// The same rows for ANY even P, `kpad` (a multiple of 64, >= C * P * P) halves wide, columns C * P * P .. kpad - 1 zero:
+// a thread writes one 16-byte piece of an output row, four pairs (k, k + 1) -- P is even, so a pair stays inside one
+// patch row and is one 8-byte load.
+__global__ __launch_bounds__(256) void k_patchify_f16_padded(const float* __restrict__ x, int C, int H, int W, int P,
+                                                             int kpad, size_t total8, _Float16* __restrict__ y,
+                                                             int packed) {
+    const int gw = W / P, gh = H / P;
+    const int pp = P * P, kdim = C * pp;
+    const int kv = kpad / 8;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total8; i += (size_t)gridDim.x * 256) {
+        const int k0 = (int)(i % kv) * 8;
+        const size_t m = i / kv;
+        const int pw = (int)(m % gw);
+        const size_t rest = m / gw;
+        const int ph = (int)(rest % gh);
+        const size_t b = rest / gh;
+        half8 o = half8{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = k0 + 2 * j;
+            if (k >= kdim) continue;  // kdim is even: a pair is inside or outside as a whole
+            const int c = k / pp, rs = k - c * pp;
+            const int r = rs / P, s = rs - r * P;
+            const float2 v = *reinterpret_cast<const float2*>(x + ((b * C + c) * H + ph * P + r) * (size_t)W + pw * P + s);
+            o[2 * j] = (_Float16)v.x;
+            o[2 * j + 1] = (_Float16)v.y;
+        }
+        *reinterpret_cast<half8*>(y + (packed ? pk_offset((long long)m, k0, kpad) : m * kpad + k0)) = o;
+    }
+}
+
+// tokens[b][0] = cls + pos[0];  tokens[b][1 + r] = reg[r] (r < R, no position);
+// tokens[b][1 + R + j] = patch_embed[b * P + j] + pos[1 + j]   with P = T - 1 - R patches and pos [1 + P, D]
 __global__ __launch_bounds__(256) void k_vit_assemble(const float* __restrict__ pe, const float* __restrict__ cls,
-                                                      const float* __restrict__ pos, int T, int D, size_t total4,
-                                                      float* __restrict__ y) {
+                                                      const float* __restrict__ reg, const float* __restrict__ pos,
+                                                      int T, int R, int D, size_t total4, float* __restrict__ y) {
     const int dv = D / 4;
+    const int np = T - 1 - R;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
         const int c = (int)(i % dv);
         const size_t bt = i / dv;
         const int t = (int)(bt % T);
         const size_t b = bt / T;
-        f32x4 v = t == 0 ? *reinterpret_cast<const f32x4*>(cls + 4 * c)
-                         : *reinterpret_cast<const f32x4*>(pe + (b * (T - 1) + t - 1) * (size_t)D + 4 * c);
-        v += *reinterpret_cast<const f32x4*>(pos + (size_t)t * D + 4 * c);
+        f32x4 v;
+        if (t >= 1 && t <= R) {
+            v = *reinterpret_cast<const f32x4*>(reg + (size_t)(t - 1) * D + 4 * c);
+        } else {
+            const int pt = t == 0 ? 0 : t - R;  // row of the position table
+            v = t == 0 ? *reinterpret_cast<const f32x4*>(cls + 4 * c)
+                       : *reinterpret_cast<const f32x4*>(pe + (b * np + pt - 1) * (size_t)D + 4 * c);
+            v += *reinterpret_cast<const f32x4*>(pos + (size_t)pt * D + 4 * c);
+        }
         *reinterpret_cast<f32x4*>(y + i * 4) = v;
     }
 }
 
 }  // namespace
 int isc_gemm_f16_stream_launch(const void* a, long long M, int K, const void* w, int N, const float* bias,
-                               const float* residual, int epi, void* out, int out_packed, hipStream_t stream);
+                               const float* scale, const float* residual, int epi, void* out, int out_packed,
+                               hipStream_t stream);
 namespace {
 
 int grid_for(size_t work_items) {
     const size_t blocks = isc_ceil_div<size_t>(work_items, 256);
     return (int)(blocks < 16384 ? (blocks ? blocks : 1) : 16384);
+}
+
+GemmParams gemm_params(const void* a, int64_t M, int K, const void* w, int N, const float* bias, const float* scale,
+                       const float* residual, int act, void* out, int out_dtype, int flags) {
+    GemmParams p;
+    p.a = reinterpret_cast<const _Float16*>(a);
+    p.w = reinterpret_cast<const _Float16*>(w);
+    p.bias = bias;
+    p.res = residual;
+    p.out = out;
+    p.M = M;
+    p.N = N;
+    p.K = K;
+    p.ksteps = K / 64;
+    p.act = act;
+    p.out_f32 = out_dtype == ISC_F32;
+    p.a_packed = (flags & ISC_GEMM_A_PACKED) != 0;
+    p.w_packed = (flags & ISC_GEMM_W_PACKED) != 0;
+    p.out_packed = (flags & ISC_GEMM_OUT_PACKED) != 0;
+    p.scale = scale;
+    return p;
 }
 
 }  // namespace
@@ -869,26 +941,12 @@ extern "C" int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int 
         N % 256 == 0 && !(out_dtype == ISC_F32 && act != ISC_ACT_NONE) && !(out_dtype == ISC_F16 && residual)) {
         const int epi = out_dtype == ISC_F32 ? 2 : act == ISC_ACT_GELU ? 1 : 0;
         isc_timing_begin(ISC_KERNEL_GEMM_F16, isc_stream(stream));
-        const int st = isc_gemm_f16_stream_launch(a, M, K, w, N, bias, residual, epi, out,
+        const int st = isc_gemm_f16_stream_launch(a, M, K, w, N, bias, nullptr, residual, epi, out,
                                                   (flags & ISC_GEMM_OUT_PACKED) != 0, isc_stream(stream));
         isc_timing_end(ISC_KERNEL_GEMM_F16, isc_stream(stream));
         return st;
     }
-    GemmParams p;
-    p.a = reinterpret_cast<const _Float16*>(a);
-    p.w = reinterpret_cast<const _Float16*>(w);
-    p.bias = bias;
-    p.res = residual;
-    p.out = out;
-    p.M = M;
-    p.N = N;
-    p.K = K;
-    p.ksteps = K / 64;
-    p.act = act;
-    p.out_f32 = out_dtype == ISC_F32;
-    p.a_packed = (flags & ISC_GEMM_A_PACKED) != 0;
-    p.w_packed = (flags & ISC_GEMM_W_PACKED) != 0;
-    p.out_packed = (flags & ISC_GEMM_OUT_PACKED) != 0;
+    const GemmParams p = gemm_params(a, M, K, w, N, bias, nullptr, residual, act, out, out_dtype, flags);
     const long long tiles = isc_ceil_div<long long>(M, 128) * isc_ceil_div<long long>(N, 128);
     if (tiles > 0x7ffffff0LL) return ISC_ERR_UNSUPPORTED;
     hipStream_t s = isc_stream(stream);
@@ -929,6 +987,37 @@ extern "C" int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int 
 #endif
             hipLaunchKernelGGL(k_gemm_f16_dma<0>, dim3((unsigned)grid1), dim3(256), 0, s, p);
     }
+    isc_timing_end(ISC_KERNEL_GEMM_F16, s);
+    return isc_launch_status();
+}
+
+extern "C" int isc_gemm_f16_scaled(const void* a, int64_t M, int K, const void* w, int N, const float* bias,
+                                   const float* scale, const float* residual, int act, void* out, int out_dtype,
+                                   int flags, void* stream) {
+    ISC_REQUIRE(a && w && out && scale && M > 0 && K > 0 && N > 0);
+    ISC_REQUIRE(act == ISC_ACT_NONE || act == ISC_ACT_GELU);
+    ISC_REQUIRE(out_dtype == ISC_F16 || out_dtype == ISC_F32);
+    ISC_REQUIRE((flags & ~(ISC_GEMM_A_PACKED | ISC_GEMM_W_PACKED | ISC_GEMM_OUT_PACKED | ISC_GEMM_TILE_256 |
+                           ISC_GEMM_TILE_128)) == 0);
+    if (K % 64 != 0 || N % 4 != 0) return ISC_ERR_UNSUPPORTED;
+    // the forms the encoder reaches: float32 output, no activation, the streaming and the 128 x 128 kernel
+    if (out_dtype != ISC_F32 || act != ISC_ACT_NONE || (flags & (ISC_GEMM_OUT_PACKED | ISC_GEMM_TILE_256)))
+        return ISC_ERR_UNSUPPORTED;
+    if (!isc_aligned(a, 16) || !isc_aligned(w, 16) || !isc_aligned(out, 16) || !isc_aligned(scale, 16) ||
+        (bias && !isc_aligned(bias, 16)) || (residual && !isc_aligned(residual, 16)))
+        return ISC_ERR_ALIGNMENT;
+    hipStream_t s = isc_stream(stream);
+    if ((flags & ISC_GEMM_A_PACKED) && (flags & ISC_GEMM_W_PACKED) && !(flags & ISC_GEMM_TILE_128) && N % 256 == 0) {
+        isc_timing_begin(ISC_KERNEL_GEMM_F16, s);
+        const int st = isc_gemm_f16_stream_launch(a, M, K, w, N, bias, scale, residual, 3, out, 0, s);
+        isc_timing_end(ISC_KERNEL_GEMM_F16, s);
+        return st;
+    }
+    const GemmParams p = gemm_params(a, M, K, w, N, bias, scale, residual, act, out, out_dtype, flags);
+    const long long tiles = isc_ceil_div<long long>(M, 128) * isc_ceil_div<long long>(N, 128);
+    if (tiles > 0x7ffffff0LL) return ISC_ERR_UNSUPPORTED;
+    isc_timing_begin(ISC_KERNEL_GEMM_F16, s);
+    hipLaunchKernelGGL((k_gemm_f16_dma<0, true>), dim3((unsigned)(isc_ceil_div<long long>(tiles, 8) * 8)), dim3(256), 0, s, p);
     isc_timing_end(ISC_KERNEL_GEMM_F16, s);
     return isc_launch_status();
 }
@@ -1034,15 +1123,33 @@ extern "C" int isc_patchify_f16(const float* x, int B, int C, int H, int W, int 
     return isc_launch_status();
 }
 
-extern "C" int isc_vit_assemble(const float* patch_embed, const float* cls_token, const float* pos_embed, int B, int T,
-                                int D, float* tokens, void* stream) {
-    ISC_REQUIRE(patch_embed && cls_token && pos_embed && tokens && B > 0 && T > 1 && D > 0);
+extern "C" int isc_patchify_f16_padded(const float* x, int B, int C, int H, int W, int patch, int kpad, void* patches,
+                                       int packed, void* stream) {
+    ISC_REQUIRE(x && patches && B > 0 && C > 0 && H > 0 && W > 0 && patch > 0 && kpad > 0);
+    if (patch % 2 != 0 || H % patch != 0 || W % patch != 0) return ISC_ERR_UNSUPPORTED;
+    if (kpad % 64 != 0 || (long long)kpad < (long long)C * patch * patch) return ISC_ERR_UNSUPPORTED;
+    if (!isc_aligned(x, 16) || !isc_aligned(patches, 16)) return ISC_ERR_ALIGNMENT;
+    const size_t total8 = (size_t)B * (H / patch) * (W / patch) * (kpad / 8);
+    hipLaunchKernelGGL(k_patchify_f16_padded, dim3(grid_for(total8)), dim3(256), 0, isc_stream(stream), x, C, H, W, patch,
+                       kpad, total8, reinterpret_cast<_Float16*>(patches), packed ? 1 : 0);
+    return isc_launch_status();
+}
+
+extern "C" int isc_vit_assemble_reg(const float* patch_embed, const float* cls_token, const float* reg_tokens,
+                                    const float* pos_embed, int B, int T, int R, int D, float* tokens, void* stream) {
+    ISC_REQUIRE(patch_embed && cls_token && pos_embed && tokens && B > 0 && D > 0 && R >= 0 && (R == 0 || reg_tokens));
+    ISC_REQUIRE(T > 1 + R);
     if (D % 4 != 0) return ISC_ERR_UNSUPPORTED;
     if (!isc_aligned(patch_embed, 16) || !isc_aligned(cls_token, 16) || !isc_aligned(pos_embed, 16) ||
-        !isc_aligned(tokens, 16))
+        !isc_aligned(tokens, 16) || (R > 0 && !isc_aligned(reg_tokens, 16)))
         return ISC_ERR_ALIGNMENT;
     const size_t total4 = (size_t)B * T * (D / 4);
     hipLaunchKernelGGL(k_vit_assemble, dim3(grid_for(total4)), dim3(256), 0, isc_stream(stream), patch_embed, cls_token,
-                       pos_embed, T, D, total4, tokens);
+                       reg_tokens, pos_embed, T, R, D, total4, tokens);
     return isc_launch_status();
+}
+
+extern "C" int isc_vit_assemble(const float* patch_embed, const float* cls_token, const float* pos_embed, int B, int T,
+                                int D, float* tokens, void* stream) {
+    return isc_vit_assemble_reg(patch_embed, cls_token, nullptr, pos_embed, B, T, 0, D, tokens, stream);
 }

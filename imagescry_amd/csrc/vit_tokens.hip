@@ -1,5 +1,5 @@
-// Patch-token output of the ViT encoder (include/imagescry_hip.h: isc_vit_pos_resample, isc_vit_tokens_out): the
-// position table of an h x w token grid, and the head that turns the residual stream into the channels-first
+// Patch-token output of the ViT encoder (include/imagescry_hip.h: isc_vit_pos_resample, isc_vit_pos_resample_aa,
+// isc_vit_tokens_out, isc_vit_tokens_out_skip): the position table of an h x w token grid, and the head that turns the residual stream into the channels-first
 // embedding map [B, D, h, w] every other embedder returns.
 #include "isc_common.h"
 
@@ -56,7 +56,63 @@ __global__ __launch_bounds__(256) void k_vit_pos_resample(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// out[b][e][t - 1] = normalize?( LayerNorm(tokens[b][t]) )[e] for the patch tokens t = 1 .. T - 1 of every image.
+// The ANTIALIASED form (torch _upsample_bicubic2d_aa, align_corners = False): a separable filter whose support grows
+// with the downscaling factor.  Per axis, s = g / h: centre = s (dst + 0.5), support = 2 max(s, 1), taps
+// [max(0, int(centre - support + 0.5)), min(g, int(centre + support + 0.5))), weight of tap j
+// cubic((j - centre + 0.5) / max(s, 1)) with A = -0.5, divided by the sum over the taps that fall inside the table.
+__device__ __forceinline__ float cubic_aa(float x) {
+    constexpr float A = -0.5f;
+    x = fabsf(x);
+    if (x < 1.f) return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
+    if (x < 2.f) return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
+    return 0.f;
+}
+
+struct AaTaps {
+    int lo, n;
+    float centre, inv, total;
+    __device__ __forceinline__ AaTaps(int dst, float scale, int g) {
+        centre = scale * ((float)dst + 0.5f);
+        const float support = 2.f * fmaxf(scale, 1.f);
+        inv = 1.f / fmaxf(scale, 1.f);
+        lo = max((int)(centre - support + 0.5f), 0);
+        n = min((int)(centre + support + 0.5f), g) - lo;
+        total = 0.f;
+        for (int j = 0; j < n; ++j) total += raw(j);
+    }
+    __device__ __forceinline__ float raw(int j) const { return cubic_aa(((float)(j + lo) - centre + 0.5f) * inv); }
+    __device__ __forceinline__ float weight(int j) const { return raw(j) / total; }
+};
+
+// One thread per (output row, four channels), rows of the source first (as the separable passes of torch go), runs
+// once per grid: up to g x g taps a thread.
+__global__ __launch_bounds__(256) void k_vit_pos_resample_aa(const float* __restrict__ pos, int g, int h, int w, int D,
+                                                             float scale_h, float scale_w, float* __restrict__ out) {
+    const int dv = D >> 2;
+    const int total = (1 + h * w) * dv;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int c = i % dv;
+    const int row = i / dv;
+    if (row == 0) {
+        *reinterpret_cast<f32x4*>(out + 4 * c) = *reinterpret_cast<const f32x4*>(pos + 4 * c);
+        return;
+    }
+    const int oy = (row - 1) / w, ox = (row - 1) - oy * w;
+    const AaTaps ty(oy, scale_h, g), tx(ox, scale_w, g);
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int a = 0; a < ty.n; ++a) {
+        f32x4 line = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < tx.n; ++b)
+            line += tx.weight(b) * *reinterpret_cast<const f32x4*>(pos + (size_t)(1 + (ty.lo + a) * g + tx.lo + b) * D + 4 * c);
+        acc += ty.weight(a) * line;
+    }
+    *reinterpret_cast<f32x4*>(out + (size_t)row * D + 4 * c) = acc;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// out[b][e][t - skip] = normalize?( LayerNorm(tokens[b][t]) )[e] for the patch tokens t = skip .. T - 1 of every image
+// (skip = the rows in front of the patches: the class token and any register tokens).
 //
 // A workgroup owns a tile of 32 consecutive cells of one image and all D channels of them:
 //   phase 1  LayerNorm, one wave per token (k_layernorm's arithmetic: the same lane -> channel map, the same two passes
@@ -80,14 +136,15 @@ template <int NV>
 __global__ __launch_bounds__(TO_THREADS) void k_vit_tokens_out(const float* __restrict__ tokens, int T, int D,
                                                                const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float eps, int normalize,
-                                                               float l2_eps, float* __restrict__ out, int tiles) {
+                                                               float l2_eps, float* __restrict__ out, int tiles,
+                                                               int skip) {
     extern __shared__ __attribute__((aligned(16))) float to_lds[];
     const int nvec = D >> 2;
     float* const tile = to_lds;                     // [nvec][TO_PITCH]
     float* const denom = to_lds + nvec * TO_PITCH;  // [TO_CELLS]
     const int b = blockIdx.x / tiles;
     const int c0 = (blockIdx.x - b * tiles) * TO_CELLS;
-    const int cells = T - 1;
+    const int cells = T - skip;
     const int ncell = min(TO_CELLS, cells - c0);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -98,7 +155,7 @@ __global__ __launch_bounds__(TO_THREADS) void k_vit_tokens_out(const float* __re
 #pragma unroll
     for (int k = 0; k < TO_TOKENS; ++k) {
         const int j = wave + TO_WAVES * k;
-        const float* xr = tokens + ((size_t)b * T + 1 + c0 + min(j, ncell - 1)) * D;
+        const float* xr = tokens + ((size_t)b * T + skip + c0 + min(j, ncell - 1)) * D;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int c = lane + 64 * i;
@@ -204,13 +261,26 @@ extern "C" int isc_vit_pos_resample(const float* pos_embed, int g, int h, int w,
     return isc_launch_status();
 }
 
-extern "C" int isc_vit_tokens_out(const float* tokens, int B, int T, int D, const float* gamma, const float* beta,
-                                  float eps, int normalize, float l2_eps, float* out, void* stream) {
-    ISC_REQUIRE(tokens && gamma && beta && out && B > 0 && T > 1 && D > 0 && eps >= 0.f && l2_eps >= 0.f);
+extern "C" int isc_vit_pos_resample_aa(const float* pos_embed, int g, int h, int w, int D, float* out, void* stream) {
+    ISC_REQUIRE(pos_embed && out && g > 0 && h > 0 && w > 0 && D > 0);
+    if (D % 4 != 0) return ISC_ERR_UNSUPPORTED;
+    if ((long long)g * g >= (1 << 24) || (long long)h * w >= (1 << 24) || (1ll + (long long)h * w) * (D / 4) > 0x7fffffffLL)
+        return ISC_ERR_UNSUPPORTED;
+    if (!isc_aligned(pos_embed, 16) || !isc_aligned(out, 16)) return ISC_ERR_ALIGNMENT;
+    const int total = (1 + h * w) * (D / 4);
+    hipLaunchKernelGGL(k_vit_pos_resample_aa, dim3(isc_ceil_div(total, 256)), dim3(256), 0, isc_stream(stream), pos_embed,
+                       g, h, w, D, (float)g / (float)h, (float)g / (float)w, out);
+    return isc_launch_status();
+}
+
+extern "C" int isc_vit_tokens_out_skip(const float* tokens, int B, int T, int skip, int D, const float* gamma,
+                                       const float* beta, float eps, int normalize, float l2_eps, float* out,
+                                       void* stream) {
+    ISC_REQUIRE(tokens && gamma && beta && out && B > 0 && skip >= 1 && T > skip && D > 0 && eps >= 0.f && l2_eps >= 0.f);
     if (D % 4 != 0 || D > TO_MAX_D) return ISC_ERR_UNSUPPORTED;
     if (!isc_aligned(tokens, 16) || !isc_aligned(gamma, 16) || !isc_aligned(beta, 16) || !isc_aligned(out, 16))
         return ISC_ERR_ALIGNMENT;
-    const int tiles = isc_ceil_div(T - 1, TO_CELLS);
+    const int tiles = isc_ceil_div(T - skip, TO_CELLS);
     if ((long long)B * tiles > 0x7fffffffLL) return ISC_ERR_UNSUPPORTED;
     const int nv = (D / 4 + 63) / 64;
     const size_t lds = (size_t)(D / 4) * TO_PITCH * 4 + TO_CELLS * 4;
@@ -220,7 +290,7 @@ extern "C" int isc_vit_tokens_out(const float* tokens, int B, int T, int D, cons
         static unsigned long long attr_done = 0;                                                                    \
         if (!tokens_out_prepare(reinterpret_cast<const void*>(kern), &attr_done)) return ISC_ERR_UNSUPPORTED;       \
         hipLaunchKernelGGL(kern, dim3((unsigned)(B * tiles)), dim3(TO_THREADS), lds, isc_stream(stream), tokens, T, D, \
-                           gamma, beta, eps, normalize ? 1 : 0, l2_eps, out, tiles);                                \
+                           gamma, beta, eps, normalize ? 1 : 0, l2_eps, out, tiles, skip);                          \
     } while (0)
     if (nv <= 1) ISC_TO_LAUNCH(1);
     else if (nv <= 2) ISC_TO_LAUNCH(2);
@@ -228,4 +298,9 @@ extern "C" int isc_vit_tokens_out(const float* tokens, int B, int T, int D, cons
     else ISC_TO_LAUNCH(4);
 #undef ISC_TO_LAUNCH
     return isc_launch_status();
+}
+
+extern "C" int isc_vit_tokens_out(const float* tokens, int B, int T, int D, const float* gamma, const float* beta,
+                                  float eps, int normalize, float l2_eps, float* out, void* stream) {
+    return isc_vit_tokens_out_skip(tokens, B, T, 1, D, gamma, beta, eps, normalize, l2_eps, out, stream);
 }

@@ -19,7 +19,7 @@ from imagescry_amd import _lib, efficientnet, resnet50, vit
 from imagescry_amd.data import EmbeddingBatch, ImageBatch
 from imagescry_amd.transforms import normalize_per_channel, resize
 
-__all__ = ["EfficientNetEmbedder", "EmbeddingModule", "ResNet50Embedder", "ViTB16Embedder", "l2_normalize_channels"]
+__all__ = ["DINOv2Embedder", "EfficientNetEmbedder", "EmbeddingModule", "ResNet50Embedder", "ViTB16Embedder", "l2_normalize_channels"]
 
 
 def l2_normalize_channels(x: Tensor, eps: float = 1e-12) -> Tensor:
@@ -506,7 +506,7 @@ class ViTB16Embedder(EmbeddingModule):
             raise ValueError(f"module is on {self.device} but the input is on {x.device}; call .to() first")
         x = x.contiguous()
         b = x.shape[0]
-        step = vit.images_per_pass(grid[0] * grid[1] + 1, self.max_images_per_pass)
+        step = vit.images_per_pass(grid[0] * grid[1] + self.config.num_prefix, self.max_images_per_pass)
         cap = self._patch_cap if self.grid == "aspect" else None
         if self.output == "patches":
             out = torch.empty((b, self.config.dim, *grid), dtype=torch.float32, device=x.device)
@@ -536,3 +536,44 @@ class ViTB16Embedder(EmbeddingModule):
             # a one-cell map: isc_l2norm_channels sums a lone row in another order than the head does
             return EmbeddingBatch(indices=batch.indices, embeddings=l2_normalize_channels(self.forward(x)))
         return EmbeddingBatch(indices=batch.indices, embeddings=self._forward(x, normalized=True))
+
+
+# (variant, registers) -> configuration
+DINOV2_PRESETS: dict[tuple[str, bool], vit.ViTConfig] = {
+    ("vits14", False): vit.DINOV2_S14, ("vits14", True): vit.DINOV2_S14_REG,
+    ("vitb14", False): vit.DINOV2_B14, ("vitb14", True): vit.DINOV2_B14_REG,
+    ("vitl14", False): vit.DINOV2_L14, ("vitl14", True): vit.DINOV2_L14_REG,
+}
+
+
+class DINOv2Embedder(ViTB16Embedder):
+    """DINOv2 ViT-S/B/L with a patch size of 14 -> 384 / 768 / 1024-d embeddings: `ViTB16Embedder` on one of the
+    `vit.DINOV2_*` configurations (LayerScale; with `registers` four register tokens, which the patch map leaves out
+    like the class token, and the antialiased position resampling of those checkpoints).
+
+    `state_dict` takes a `dinov2_vit{s,b,l}14[_reg]` checkpoint under its facebookresearch/dinov2 or timm names, or a
+    Hugging Face one through `vit.from_transformers_state_dict`; without it the weights are seeded random ones.  The
+    checkpoints' native grid is 37 x 37 (518 pixels); `output="patches", grid="aspect", max_patches=256` turns a square
+    image into a 16 x 16 map.  Preprocessing is this package's (`resize` + `normalize_per_channel`), and a grid other
+    than the native one resamples the position table by its size (`transformers.Dinov2Model`), not with the hub models'
+    `+ 0.1` offset."""
+
+    def __init__(
+        self,
+        variant: str = "vitb14",
+        registers: bool = False,
+        *,
+        state_dict: dict[str, Tensor] | None = None,
+        seed: int = 0,
+        max_images_per_pass: int = 1024,
+        output: str = "cls",
+        grid: str = "fixed",
+        max_patches: int | None = None,
+    ) -> None:
+        if not isinstance(registers, bool):
+            raise TypeError(f"registers must be a bool, got {registers!r}")
+        if (variant, registers) not in DINOV2_PRESETS:
+            raise ValueError(f"variant must be one of {sorted({v for v, _ in DINOV2_PRESETS})}, got {variant!r}")
+        super().__init__(config=DINOV2_PRESETS[variant, registers], state_dict=state_dict, seed=seed,
+                         max_images_per_pass=max_images_per_pass, output=output, grid=grid, max_patches=max_patches)
+        self.hparams.update(variant=variant, registers=registers)

@@ -8,12 +8,17 @@ is the build's own definition behind the same `EmbeddingModule` contract.  State
 token after the final LayerNorm (pre-LN encoder, erf-form GELU, LayerNorm eps 1e-6 by default) -- `forward_cls` -- or
 the map of its patch tokens -- `forward_tokens` --, on the checkpoint's square token grid or on any `h x w` grid of at
 most as many patches (`token_grid`, `position_table`: bicubically resampled position embeddings).
+
+The DINOv2 backbones (`DINOV2_S14` ... `DINOV2_L14_REG`; checkpoint names of facebookresearch/dinov2 and of timm, a
+Hugging Face one through `from_transformers_state_dict`) are the same encoder with a patch size of 14, LayerScale behind
+the attention and the MLP branch, and -- the `_REG` presets -- four register tokens between the class token and the
+patches, whose position table is resampled with antialiasing.
 """
 
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import torch
 from torch import Tensor
@@ -30,17 +35,38 @@ class ViTConfig:
     heads: int = 12
     mlp_dim: int = 3072
     ln_eps: float = 1e-6
+    registers: int = 0  # register tokens between the class token and the patches (no position embedding)
+    layerscale: bool = False  # per-channel scale (`ls1.gamma`, `ls2.gamma`) on the attention and the MLP branch
+    pos_antialias: bool = False  # resample the position table with antialiasing (the register checkpoints)
 
     @property
     def grid(self) -> int:
         return self.image_size // self.patch_size
 
     @property
+    def num_prefix(self) -> int:
+        """Token rows in front of the patches: the class token and the registers."""
+        return 1 + self.registers
+
+    @property
     def tokens(self) -> int:
-        return self.grid * self.grid + 1
+        """Sequence length on the native grid.  (`pos_embed` has `1 + grid ** 2` rows whatever `registers` is.)"""
+        return self.grid * self.grid + self.num_prefix
+
+    @property
+    def patch_kdim(self) -> int:
+        """Inner dimension of the patch-embedding GEMM: `3 P^2` padded with zeros to whole K steps of 64."""
+        return -(-3 * self.patch_size**2 // 64) * 64
 
 
 VIT_B16 = ViTConfig()
+# DINOv2 (ViT-g/14 is not among them: SwiGLU MLP, head size 96)
+DINOV2_S14 = ViTConfig(image_size=518, patch_size=14, dim=384, depth=12, heads=6, mlp_dim=1536, layerscale=True)
+DINOV2_B14 = ViTConfig(image_size=518, patch_size=14, dim=768, depth=12, heads=12, mlp_dim=3072, layerscale=True)
+DINOV2_L14 = ViTConfig(image_size=518, patch_size=14, dim=1024, depth=24, heads=16, mlp_dim=4096, layerscale=True)
+DINOV2_S14_REG = replace(DINOV2_S14, registers=4, pos_antialias=True)
+DINOV2_B14_REG = replace(DINOV2_B14, registers=4, pos_antialias=True)
+DINOV2_L14_REG = replace(DINOV2_L14, registers=4, pos_antialias=True)
 MAX_PATCHES = 4096  # the largest token grid an embedder may ask for: 64 x 64 patches, 1024 x 1024 pixels
 ONE_SHOT_TOKENS = 224  # isc_attention_f16 holds a head's keys whole up to here; longer sequences stream them
 PASS_ROWS = 1024 * 197  # token rows of the default configuration's largest pass (1024 images x 197 tokens)
@@ -67,7 +93,9 @@ def token_grid(height: int, width: int, max_patches: int = VIT_B16.grid**2) -> t
 
 def make_state_dict(cfg: ViTConfig = VIT_B16, *, seed: int = 0, randomize_affine: bool = False) -> dict[str, Tensor]:
     """Seeded random parameters (CPU float32): truncated-normal(std 0.02) weights / tokens, zero biases and identity
-    LayerNorms -- or, with `randomize_affine`, random biases and LayerNorm affines so that every term is exercised."""
+    LayerNorms -- or, with `randomize_affine`, random biases and LayerNorm affines so that every term is exercised.
+    Register tokens and LayerScale factors (ones; with `randomize_affine` log-uniform in [1e-5, 1], the range trained
+    checkpoints cover) are drawn after everything else: a seed gives the other keys the same tensors with or without."""
     g = torch.Generator().manual_seed(seed)
 
     def tn(*shape: int) -> Tensor:
@@ -82,7 +110,7 @@ def make_state_dict(cfg: ViTConfig = VIT_B16, *, seed: int = 0, randomize_affine
     d = cfg.dim
     sd: dict[str, Tensor] = {
         "cls_token": tn(1, 1, d),
-        "pos_embed": tn(1, cfg.tokens, d),
+        "pos_embed": tn(1, 1 + cfg.grid**2, d),
         "patch_embed.proj.weight": tn(d, 3, cfg.patch_size, cfg.patch_size),
         "patch_embed.proj.bias": bias(d),
     }
@@ -95,6 +123,13 @@ def make_state_dict(cfg: ViTConfig = VIT_B16, *, seed: int = 0, randomize_affine
         sd[f"{p}.mlp.fc1.weight"], sd[f"{p}.mlp.fc1.bias"] = tn(cfg.mlp_dim, d), bias(cfg.mlp_dim)
         sd[f"{p}.mlp.fc2.weight"], sd[f"{p}.mlp.fc2.bias"] = tn(d, cfg.mlp_dim), bias(d)
     sd["norm.weight"], sd["norm.bias"] = gamma(d), bias(d)
+    if cfg.registers:
+        sd["register_tokens"] = tn(1, cfg.registers, d)
+    if cfg.layerscale:
+        for i in range(cfg.depth):
+            for name in ("ls1", "ls2"):
+                sd[f"blocks.{i}.{name}.gamma"] = (10.0 ** (-5.0 * torch.rand(d, generator=g)) if randomize_affine
+                                                  else torch.ones(d))
     return sd
 
 
@@ -102,7 +137,7 @@ def gemm_flops(cfg: ViTConfig = VIT_B16) -> int:
     """Multiply-add FLOPs (2 per MAC) of the GEMMs and the attention products for ONE image."""
     t, d = cfg.tokens, cfg.dim
     per_layer = 2 * t * d * (3 * d) + 2 * t * d * d + 2 * 2 * t * d * cfg.mlp_dim + 2 * 2 * t * t * d
-    return 2 * (t - 1) * d * (3 * cfg.patch_size**2) + cfg.depth * per_layer
+    return 2 * (t - cfg.num_prefix) * d * (3 * cfg.patch_size**2) + cfg.depth * per_layer
 
 
 def pack_rows(x: Tensor) -> Tensor:
@@ -159,61 +194,132 @@ class Block:
     norm2: Norm
     fc1: Linear
     fc2: Linear
+    ls1: Tensor | None = None  # float32 [D] LayerScale of the attention branch (scales `proj`'s output), or None
+    ls2: Tensor | None = None  # ... of the MLP branch (`fc2`)
 
     def to(self, device: torch.device) -> "Block":
-        return Block(*(getattr(self, f).to(device) for f in ("norm1", "qkv", "proj", "norm2", "fc1", "fc2")))
+        return Block(*(getattr(self, f).to(device) for f in ("norm1", "qkv", "proj", "norm2", "fc1", "fc2")),
+                     *(None if s is None else s.to(device) for s in (self.ls1, self.ls2)))
 
 
 @dataclass
 class PreparedViT:
     cfg: ViTConfig
     cls_token: Tensor  # float32 [D]
-    pos_embed: Tensor  # float32 [T, D]
-    patch: Linear  # [D, 3 * P * P]
+    pos_embed: Tensor  # float32 [1 + grid ** 2, D]
+    patch: Linear  # [D, cfg.patch_kdim]: columns past 3 * P * P are zero
     blocks: list[Block] = field(default_factory=list)
     norm: Norm | None = None
+    reg_tokens: Tensor | None = None  # float32 [registers, D]
     # resampled position tables, (h, w) -> float32 [1 + h * w, D] on pos_embed's device; belongs to THIS prepared net
     # (`to` starts an empty one), bounded by POS_CACHE_MAX
     pos_cache: dict[tuple[int, int], Tensor] = field(default_factory=dict, repr=False, compare=False)
 
     def to(self, device: torch.device) -> "PreparedViT":
         return PreparedViT(self.cfg, self.cls_token.to(device), self.pos_embed.to(device), self.patch.to(device),
-                           [b.to(device) for b in self.blocks], self.norm.to(device))
+                           [b.to(device) for b in self.blocks], self.norm.to(device),
+                           None if self.reg_tokens is None else self.reg_tokens.to(device))
 
 
 def prepare(sd: dict[str, Tensor], cfg: ViTConfig = VIT_B16) -> PreparedViT:
     """Cast GEMM weights to fp16 (round-to-nearest-even) and store them in the packed layout the GEMM kernels stream; keep
-    biases / LayerNorm / tokens in float32."""
+    biases / LayerNorm / LayerScale / tokens in float32.  The patch weight's inner dimension is zero-padded to whole K
+    steps of 64 (`cfg.patch_kdim`: 588 -> 640 for a patch size of 14).  LayerScale stays a float32 vector for the GEMM
+    epilogue: trained values go down to 1e-5, and folded into the weights they would land in fp16 subnormals.
+    `register_tokens` may be spelled `reg_token` (timm); `mask_token` is ignored."""
     d = cfg.dim
-    if cfg.dim % 64 or cfg.mlp_dim % 64 or (3 * cfg.patch_size**2) % 64 or cfg.dim // cfg.heads != 64:
+    if cfg.dim % 64 or cfg.mlp_dim % 64 or cfg.dim // cfg.heads != 64:
         raise ValueError("this build supports head size 64 and GEMM inner dimensions that are multiples of 64")
-    if tuple(sd["pos_embed"].shape) != (1, cfg.tokens, d):
-        raise ValueError(f"pos_embed has shape {tuple(sd['pos_embed'].shape)}, expected (1, {cfg.tokens}, {d})")
+    if cfg.patch_size % 2:
+        raise ValueError(f"this build supports even patch sizes, got {cfg.patch_size}")
+    rows = 1 + cfg.grid**2
+    if tuple(sd["pos_embed"].shape) != (1, rows, d):
+        raise ValueError(f"pos_embed has shape {tuple(sd['pos_embed'].shape)}, expected (1, {rows}, {d})")
 
-    def lin(name: str) -> Linear:
+    def need(key: str, what: str) -> Tensor:
+        if key not in sd:
+            raise ValueError(f"the config asks for {what}, but the state dict has no `{key}`")
+        return sd[key]
+
+    def lin(name: str, pad_to: int = 0) -> Linear:
         w = sd[f"{name}.weight"]
         w2 = w.reshape(w.shape[0], -1).to(torch.float16)
+        if pad_to > w2.shape[1]:
+            w2 = torch.nn.functional.pad(w2, (0, pad_to - w2.shape[1]))
         return Linear(pack_rows(w2), sd[f"{name}.bias"].float().contiguous(), w2.shape[0], w2.shape[1])
+
+    def scale(key: str) -> Tensor | None:
+        return need(key, "LayerScale").reshape(d).float().contiguous() if cfg.layerscale else None
 
     def norm(name: str) -> Norm:
         return Norm(sd[f"{name}.weight"].float().contiguous(), sd[f"{name}.bias"].float().contiguous())
 
     net = PreparedViT(cfg, sd["cls_token"].reshape(d).float().contiguous(),
-                      sd["pos_embed"].reshape(cfg.tokens, d).float().contiguous(), lin("patch_embed.proj"))
+                      sd["pos_embed"].reshape(rows, d).float().contiguous(), lin("patch_embed.proj", cfg.patch_kdim))
+    if cfg.registers:
+        key = "register_tokens" if "register_tokens" in sd or "reg_token" not in sd else "reg_token"
+        reg = need(key, f"{cfg.registers} register tokens")
+        if tuple(reg.shape) != (1, cfg.registers, d):
+            raise ValueError(f"{key} has shape {tuple(reg.shape)}, expected (1, {cfg.registers}, {d})")
+        net.reg_tokens = reg.reshape(cfg.registers, d).float().contiguous()
     for i in range(cfg.depth):
         p = f"blocks.{i}"
         net.blocks.append(Block(norm(f"{p}.norm1"), lin(f"{p}.attn.qkv"), lin(f"{p}.attn.proj"), norm(f"{p}.norm2"),
-                                lin(f"{p}.mlp.fc1"), lin(f"{p}.mlp.fc2")))
+                                lin(f"{p}.mlp.fc1"), lin(f"{p}.mlp.fc2"), scale(f"{p}.ls1.gamma"),
+                                scale(f"{p}.ls2.gamma")))
     net.norm = norm("norm")
     return net
 
 
+def from_transformers_state_dict(hf: dict[str, Tensor]) -> dict[str, Tensor]:
+    """The state dict of a Hugging Face `Dinov2Model` / `Dinov2WithRegistersModel` (with or without a leading
+    `dinov2.` / `dinov2_with_registers.`) under this module's names: separate query / key / value are fused into
+    `attn.qkv` in `[q; k; v]` row order, `layer_scale1.lambda1` becomes `ls1.gamma`, `layernorm` becomes `norm`.  Keys
+    that belong to no encoder parameter (`mask_token`, a classifier head) are dropped."""
+    wrappers = ("dinov2", "dinov2_with_registers")
+    hf = {k.split(".", 1)[1] if k.split(".", 1)[0] in wrappers else k: v for k, v in hf.items()}
+    sd: dict[str, Tensor] = {}
+    for ours, theirs in (("cls_token", "embeddings.cls_token"), ("pos_embed", "embeddings.position_embeddings"),
+                         ("register_tokens", "embeddings.register_tokens"),
+                         ("patch_embed.proj.weight", "embeddings.patch_embeddings.projection.weight"),
+                         ("patch_embed.proj.bias", "embeddings.patch_embeddings.projection.bias"),
+                         ("norm.weight", "layernorm.weight"), ("norm.bias", "layernorm.bias")):
+        if theirs in hf:
+            sd[ours] = hf[theirs]
+    per_layer = (("norm1", "norm1"), ("attn.proj", "attention.output.dense"), ("norm2", "norm2"), ("mlp.fc1", "mlp.fc1"),
+                 ("mlp.fc2", "mlp.fc2"))
+    i = 0
+    while f"encoder.layer.{i}.norm1.weight" in hf:
+        p, q = f"blocks.{i}", f"encoder.layer.{i}"
+        for ours, theirs in per_layer:
+            for kind in ("weight", "bias"):
+                sd[f"{p}.{ours}.{kind}"] = hf[f"{q}.{theirs}.{kind}"]
+        for kind in ("weight", "bias"):
+            sd[f"{p}.attn.qkv.{kind}"] = torch.cat([hf[f"{q}.attention.attention.{n}.{kind}"]
+                                                    for n in ("query", "key", "value")])
+        for n in ("1", "2"):
+            if f"{q}.layer_scale{n}.lambda1" in hf:
+                sd[f"{p}.ls{n}.gamma"] = hf[f"{q}.layer_scale{n}.lambda1"]
+        i += 1
+    if i == 0:
+        raise ValueError("no `encoder.layer.0.*` keys: not a transformers Dinov2 state dict")
+    return sd
+
+
 def _gemm(a: Tensor, m: int, lin: Linear, out: Tensor, *, act: int = _lib.ISC_ACT_NONE, residual: Tensor | None = None,
-          stream: int = 0) -> Tensor:
+          scale: Tensor | None = None, stream: int = 0) -> Tensor:
     """`out = act(a . W^T + b) + residual`; `a` is a packed fp16 activation buffer of `m` rows, `out` either a packed
-    fp16 buffer (next GEMM operand) or a row-major float32 `[m, N]` tensor (residual stream)."""
+    fp16 buffer (next GEMM operand) or a row-major float32 `[m, N]` tensor (residual stream).  With `scale` (float32
+    `[N]`, LayerScale; float32 output only): `out = scale * (a . W^T + b) + residual`, one launch
+    (`isc_gemm_f16_scaled`)."""
     f16 = out.dtype == torch.float16
     flags = _lib.ISC_GEMM_A_PACKED | _lib.ISC_GEMM_W_PACKED | (_lib.ISC_GEMM_OUT_PACKED if f16 else 0)
+    if scale is not None:
+        st = _lib.load().isc_gemm_f16_scaled(a.data_ptr(), m, lin.in_features, lin.weight.data_ptr(), lin.out_features,
+                                             lin.bias.data_ptr(), scale.data_ptr(), _lib.ptr(residual), act,
+                                             out.data_ptr(), _lib.ISC_F16 if f16 else _lib.ISC_F32, flags, stream)
+        _lib.check(st, "isc_gemm_f16_scaled")
+        return out
     st = _lib.load().isc_gemm_f16(a.data_ptr(), m, lin.in_features, lin.weight.data_ptr(), lin.out_features,
                                   lin.bias.data_ptr(), _lib.ptr(residual), act, out.data_ptr(),
                                   _lib.ISC_F16 if f16 else _lib.ISC_F32, flags, stream)
@@ -234,8 +340,9 @@ POS_CACHE_MAX = 16  # resampled position tables kept per prepared net (0.6 MB ea
 
 def position_table(net: PreparedViT, grid: tuple[int, int]) -> Tensor:
     """float32 `[1 + h * w, D]` position table of an `h x w` token grid: the class row as it is, the `g x g` patch rows
-    resampled bicubically (`isc_vit_pos_resample`, the arithmetic of `F.interpolate(mode="bicubic")`).  The native
-    grid returns `net.pos_embed` itself, no launch; other grids are computed once per device and cached on `net`."""
+    resampled bicubically (`isc_vit_pos_resample`, the arithmetic of `F.interpolate(mode="bicubic")`; with
+    `cfg.pos_antialias` `isc_vit_pos_resample_aa`, that of `antialias=True`).  The native grid returns `net.pos_embed`
+    itself, no launch; other grids are computed once per device and cached on `net`."""
     h, w = grid
     g = net.cfg.grid
     if (h, w) == (g, g):
@@ -245,10 +352,11 @@ def position_table(net: PreparedViT, grid: tuple[int, int]) -> Tensor:
         _lib.require_device(net.pos_embed, "pos_embed")
         dev = net.pos_embed.device
         table = torch.empty((1 + h * w, net.cfg.dim), dtype=torch.float32, device=dev)
+        name = "isc_vit_pos_resample_aa" if net.cfg.pos_antialias else "isc_vit_pos_resample"
         with torch.cuda.device(dev):
-            st = _lib.load().isc_vit_pos_resample(net.pos_embed.data_ptr(), g, h, w, net.cfg.dim, table.data_ptr(),
-                                                  _lib.stream_handle(dev))
-        _lib.check(st, "isc_vit_pos_resample")
+            st = getattr(_lib.load(), name)(net.pos_embed.data_ptr(), g, h, w, net.cfg.dim, table.data_ptr(),
+                                            _lib.stream_handle(dev))
+        _lib.check(st, name)
         net.pos_cache.pop((h, w), None)
         if len(net.pos_cache) >= POS_CACHE_MAX:  # bound what a net pins: drop the oldest grid
             net.pos_cache.pop(next(iter(net.pos_cache)))
@@ -258,20 +366,21 @@ def position_table(net: PreparedViT, grid: tuple[int, int]) -> Tensor:
 
 def _encode(net: PreparedViT, x: Tensor, grid: tuple[int, int]) -> Tensor:
     """float32 `[B, 3, P h, P w]` (already preprocessed) on a HIP device -> the float32 residual stream `[B * T, D]`
-    after the last block, `T = h w + 1` (the final LayerNorm is the caller's).
+    after the last block, `T = h w + cfg.num_prefix` (the final LayerNorm is the caller's).
 
     Every fp16 activation (patches, LayerNorm outputs, qkv, attention output, MLP hidden) lives in the packed layout;
     the float32 residual stream is row-major."""
     cfg = net.cfg
     b = x.shape[0]
     gh, gw = grid
-    t, d = gh * gw + 1, cfg.dim
+    npatch, d = gh * gw, cfg.dim
+    t = npatch + cfg.num_prefix
     m = b * t
     dev = x.device
     lib = _lib.load()
     stream = _lib.stream_handle(dev)
     f16, f32 = torch.float16, torch.float32
-    kdim = 3 * cfg.patch_size**2
+    kdim = cfg.patch_kdim
 
     def packed(rows: int, cols: int) -> Tensor:
         # rows past `rows` in the last tile are never read into a result that is kept; they only have to be finite
@@ -279,16 +388,26 @@ def _encode(net: PreparedViT, x: Tensor, grid: tuple[int, int]) -> Tensor:
         return torch.empty(packed_elems(rows, cols), dtype=f16, device=dev)
 
     pos = position_table(net, grid)
-    patches = packed(b * (t - 1), kdim)
-    _lib.check(lib.isc_patchify_f16(x.data_ptr(), b, 3, gh * cfg.patch_size, gw * cfg.patch_size, cfg.patch_size,
-                                    patches.data_ptr(), 1, stream), "isc_patchify_f16")
-    pe = torch.empty((b * (t - 1), d), dtype=f32, device=dev)
-    _gemm(patches, b * (t - 1), net.patch, pe, stream=stream)
+    patches = packed(b * npatch, kdim)
+    if cfg.patch_size % 8 == 0 and kdim == 3 * cfg.patch_size**2:
+        _lib.check(lib.isc_patchify_f16(x.data_ptr(), b, 3, gh * cfg.patch_size, gw * cfg.patch_size, cfg.patch_size,
+                                        patches.data_ptr(), 1, stream), "isc_patchify_f16")
+    else:  # any even patch size; the padding columns of the K steps are written as zeros
+        _lib.check(lib.isc_patchify_f16_padded(x.data_ptr(), b, 3, gh * cfg.patch_size, gw * cfg.patch_size,
+                                               cfg.patch_size, kdim, patches.data_ptr(), 1, stream),
+                   "isc_patchify_f16_padded")
+    pe = torch.empty((b * npatch, d), dtype=f32, device=dev)
+    _gemm(patches, b * npatch, net.patch, pe, stream=stream)
     del patches
     xa = torch.empty((m, d), dtype=f32, device=dev)  # residual stream (ping)
     xb = torch.empty((m, d), dtype=f32, device=dev)  # residual stream (pong)
-    _lib.check(lib.isc_vit_assemble(pe.data_ptr(), net.cls_token.data_ptr(), pos.data_ptr(), b, t, d,
-                                    xa.data_ptr(), stream), "isc_vit_assemble")
+    if cfg.registers:
+        _lib.check(lib.isc_vit_assemble_reg(pe.data_ptr(), net.cls_token.data_ptr(), net.reg_tokens.data_ptr(),
+                                            pos.data_ptr(), b, t, cfg.registers, d, xa.data_ptr(), stream),
+                   "isc_vit_assemble_reg")
+    else:
+        _lib.check(lib.isc_vit_assemble(pe.data_ptr(), net.cls_token.data_ptr(), pos.data_ptr(), b, t, d,
+                                        xa.data_ptr(), stream), "isc_vit_assemble")
     del pe
     hbuf, qkv, att, mlp = packed(m, d), packed(m, 3 * d), packed(m, d), packed(m, cfg.mlp_dim)
     for blk in net.blocks:
@@ -300,10 +419,10 @@ def _encode(net: PreparedViT, x: Tensor, grid: tuple[int, int]) -> Tensor:
         else:  # the keys of a head no longer fit in LDS: the streaming kernel
             _lib.check(lib.isc_attention_f16_stream(qkv.data_ptr(), b, t, cfg.heads, d // cfg.heads, att.data_ptr(), 1,
                                                     stream), "isc_attention_f16_stream")
-        _gemm(att, m, blk.proj, xb, residual=xa, stream=stream)
+        _gemm(att, m, blk.proj, xb, residual=xa, scale=blk.ls1, stream=stream)
         _layernorm_packed(xb, m, blk.norm2, cfg.ln_eps, hbuf, stream)
         _gemm(hbuf, m, blk.fc1, mlp, act=_lib.ISC_ACT_GELU, stream=stream)
-        _gemm(mlp, m, blk.fc2, xa, residual=xb, stream=stream)
+        _gemm(mlp, m, blk.fc2, xa, residual=xb, scale=blk.ls2, stream=stream)
     return xa
 
 
@@ -325,7 +444,7 @@ def forward_cls(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = None
     cfg = net.cfg
     grid = (cfg.grid, cfg.grid) if grid is None else grid
     _check_grid(net, x, grid, max_patches)
-    b, d, t = x.shape[0], cfg.dim, grid[0] * grid[1] + 1
+    b, d, t = x.shape[0], cfg.dim, grid[0] * grid[1] + cfg.num_prefix
     xa = _encode(net, x, grid)
     out = torch.empty((b, d), dtype=torch.float32, device=x.device)
     st = _lib.load().isc_layernorm(xa.data_ptr(), b, d, t * d, net.norm.weight.data_ptr(), net.norm.bias.data_ptr(),
@@ -337,8 +456,9 @@ def forward_cls(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = None
 
 def forward_tokens(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = None, normalize: bool = False,
                    out: Tensor | None = None, max_patches: int | None = None) -> Tensor:
-    """float32 `[B, 3, P h, P w]` -> the float32 patch-token map `[B, D, h, w]`: cell `(i, j)` is token `1 + i w + j`
-    after the final LayerNorm, L2-normalised per cell (`F.normalize`, eps 1e-12) when `normalize` -- LayerNorm,
+    """float32 `[B, 3, P h, P w]` -> the float32 patch-token map `[B, D, h, w]`: cell `(i, j)` is token
+    `cfg.num_prefix + i w + j` (the class token and any registers are left out) after the final LayerNorm, L2-normalised
+    per cell (`F.normalize`, eps 1e-12) when `normalize` -- LayerNorm,
     normalisation and the transposition into the channels-first map are one kernel (`isc_vit_tokens_out`).  `out`: a
     contiguous `[B, D, h, w]` tensor to write into.  `max_patches`: the most patches `grid` may hold, the native grid's
     count by default."""
@@ -346,17 +466,22 @@ def forward_tokens(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = N
     grid = (cfg.grid, cfg.grid) if grid is None else grid
     _check_grid(net, x, grid, max_patches)
     h, w = grid
-    b, d, t = x.shape[0], cfg.dim, h * w + 1
+    b, d, t = x.shape[0], cfg.dim, h * w + cfg.num_prefix
     if out is None:
         out = torch.empty((b, d, h, w), dtype=torch.float32, device=x.device)
     elif tuple(out.shape) != (b, d, h, w) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
         raise ValueError(f"out must be a contiguous float32 [{b}, {d}, {h}, {w}] tensor on {x.device}")
     xa = _encode(net, x, grid)
-    st = _lib.load().isc_vit_tokens_out(xa.data_ptr(), b, t, d, net.norm.weight.data_ptr(), net.norm.bias.data_ptr(),
-                                        cfg.ln_eps, int(normalize), 1e-12, out.data_ptr(), _lib.stream_handle(x.device))
-    _lib.check(st, "isc_vit_tokens_out")
+    args = (d, net.norm.weight.data_ptr(), net.norm.bias.data_ptr(), cfg.ln_eps, int(normalize), 1e-12, out.data_ptr(),
+            _lib.stream_handle(x.device))
+    if cfg.registers:
+        _lib.check(_lib.load().isc_vit_tokens_out_skip(xa.data_ptr(), b, t, cfg.num_prefix, *args),
+                   "isc_vit_tokens_out_skip")
+    else:
+        _lib.check(_lib.load().isc_vit_tokens_out(xa.data_ptr(), b, t, *args), "isc_vit_tokens_out")
     return out
 
 
-__all__ = ["MAX_PATCHES", "VIT_B16", "ViTConfig", "forward_cls", "forward_tokens", "gemm_flops", "images_per_pass",
-           "make_state_dict", "pack_rows", "position_table", "prepare", "token_grid", "unpack_rows"]
+__all__ = ["DINOV2_B14", "DINOV2_B14_REG", "DINOV2_L14", "DINOV2_L14_REG", "DINOV2_S14", "DINOV2_S14_REG", "MAX_PATCHES",
+           "VIT_B16", "ViTConfig", "forward_cls", "forward_tokens", "from_transformers_state_dict", "gemm_flops",
+           "images_per_pass", "make_state_dict", "pack_rows", "position_table", "prepare", "token_grid", "unpack_rows"]

@@ -359,6 +359,15 @@ int isc_pool_linear_l2norm(const float* x, int B, int H, int W, int C, const flo
 int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int N, const float* bias, const float* residual,
                  int act, void* out, int out_dtype, int flags, void* stream);
 
+/* LayerScale in the GEMM epilogue: out[M,N] = residual[M,N] + scale[N] * (a[M,K] . w[N,K]^T + bias[N]).  `scale`
+ * float32 [N], 16-byte aligned, never NULL (ISC_ERR_INVALID_ARG); it multiplies in float32, after the bias and before
+ * the residual is added; bias and residual may be NULL.  Everything else as isc_gemm_f16.  Built for the forms the
+ * encoder reaches -- out_dtype == ISC_F32 and act == ISC_ACT_NONE, on the streaming kernel (packed a and w, N % 256
+ * == 0) and on the 128 x 128-tile kernel (anything else, or ISC_GEMM_TILE_128).  ISC_ERR_UNSUPPORTED for out_dtype ==
+ * ISC_F16 (and so for ISC_GEMM_OUT_PACKED), for act == ISC_ACT_GELU and for ISC_GEMM_TILE_256. */
+int isc_gemm_f16_scaled(const void* a, int64_t M, int K, const void* w, int N, const float* bias, const float* scale,
+                        const float* residual, int act, void* out, int out_dtype, int flags, void* stream);
+
 /* LayerNorm over the last axis (biased variance, float32 statistics): x float32 [rows, D] with row stride ldx,
  * y fp16 or float32 (`y_dtype`) with row stride ldy (strides in elements, multiples of 4), or -- y_packed != 0, fp16,
  * D % 64 == 0 -- in the packed layout.  D % 4 == 0, D <= 2048. */
@@ -386,9 +395,23 @@ int isc_attention_stream_geometry(int* query_block, int* key_chunk);
  * order).  P % 8 == 0, H % P == 0, W % P == 0. */
 int isc_patchify_f16(const float* x, int B, int C, int H, int W, int patch, void* patches, int packed, void* stream);
 
+/* The same rows for any EVEN patch size, `kpad` halves wide: columns 0 .. C * P * P - 1 as isc_patchify_f16 writes them,
+ * columns C * P * P .. kpad - 1 zero (a GEMM inner dimension padded to whole K steps; the weight's padding columns are
+ * zero too).  kpad % 64 == 0 and kpad >= C * P * P, P % 2 == 0, H % P == 0, W % P == 0, else ISC_ERR_UNSUPPORTED.
+ * patch = 16, kpad = 768 (C = 3) writes the bytes of isc_patchify_f16. */
+int isc_patchify_f16_padded(const float* x, int B, int C, int H, int W, int patch, int kpad, void* patches, int packed,
+                            void* stream);
+
 /* tokens[b][0] = cls + pos[0]; tokens[b][t] = patch_embed[b * (T - 1) + t - 1] + pos[t]; all float32, D % 4 == 0. */
 int isc_vit_assemble(const float* patch_embed, const float* cls_token, const float* pos_embed, int B, int T, int D,
                      float* tokens, void* stream);
+
+/* The same with R >= 0 register tokens between the class token and the patches, T = 1 + R + P:
+ * tokens[b][0] = cls + pos[0]; tokens[b][1 + r] = reg_tokens[r] (no position); tokens[b][1 + R + j] =
+ * patch_embed[b * P + j] + pos[1 + j].  pos_embed is [1 + P, D] whatever R is; reg_tokens float32 [R, D] (may be NULL
+ * when R == 0, which is isc_vit_assemble bit for bit).  R < 0 or T <= 1 + R: ISC_ERR_INVALID_ARG. */
+int isc_vit_assemble_reg(const float* patch_embed, const float* cls_token, const float* reg_tokens,
+                         const float* pos_embed, int B, int T, int R, int D, float* tokens, void* stream);
 
 /* Position table of an h x w token grid from the g x g one: out[0] = pos_embed[0] (class token); the patch rows, seen
  * as [D, g, g], resampled to [D, h, w] by bicubic interpolation -- align_corners = False, no antialias, A = -0.75,
@@ -403,6 +426,18 @@ int isc_vit_pos_resample(const float* pos_embed, int g, int h, int w, int D, flo
  * all pointers 16-byte aligned. */
 int isc_vit_tokens_out(const float* tokens, int B, int T, int D, const float* gamma, const float* beta, float eps,
                        int normalize, float l2_eps, float* out, void* stream);
+
+/* The same head with the first `skip` rows of every image left out (the class token and any register tokens):
+ * out[b][e][t - skip] for t = skip .. T - 1, out float32 [B, D, T - skip].  1 <= skip < T, else ISC_ERR_INVALID_ARG;
+ * skip == 1 is isc_vit_tokens_out bit for bit (one kernel serves both). */
+int isc_vit_tokens_out_skip(const float* tokens, int B, int T, int skip, int D, const float* gamma, const float* beta,
+                            float eps, int normalize, float l2_eps, float* out, void* stream);
+
+/* isc_vit_pos_resample with antialiasing (torch.nn.functional.interpolate(mode="bicubic", align_corners=False,
+ * antialias=True)): cubic with A = -0.5; per axis, with s = g / h, the taps of output index i are the source indices
+ * within 2 max(s, 1) of the centre s (i + 0.5), weighted cubic((j - centre + 0.5) / max(s, 1)), clipped to the table and
+ * normalised to sum 1.  The class row is copied.  Same shapes and limits as isc_vit_pos_resample. */
+int isc_vit_pos_resample_aa(const float* pos_embed, int g, int h, int w, int D, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * PCA fit (reference src/imagescry/models/decomposition.py:118-131: mean, centring, SVD of the [N, F] rows on
