@@ -6,7 +6,8 @@ Public surface (same names as the reference where the reference has them):
 * `resize`, `normalize_per_channel`, `to_4d`     -- reference src/imagescry/image/transforms.py
 * `EmbeddingModule`, `EfficientNetEmbedder`,
   `ResNet50Embedder`, `ViTB16Embedder`,
-  `DINOv2Embedder`                               -- reference src/imagescry/models/embedding.py:27-183
+  `DINOv2Embedder`, `CLIPEmbedder`               -- reference src/imagescry/models/embedding.py:27-183
+* `clip`                                         -- CLIP configs, state dicts and the text tower (text -> image search; new)
 * `PCA`, `EmbeddingPCAPipeline`                  -- reference src/imagescry/models/decomposition.py, pipelines.py
 * `EmbedSearchPipeline`                          -- encode -> search on two HIP streams (BASELINE config 5; new)
 * `EmbeddingBank`, `RangeResult`, `RowFilter`    -- cosine top-k and range search, optionally over a row filter and
@@ -16,10 +17,12 @@ All arithmetic runs in hand-written HIP kernels behind the C ABI of include/imag
 PyTorch is used for device memory, streams and `torch.distributed` only.
 """
 
+from imagescry_amd import clip
 from imagescry_amd.batching import ImageTensorDataset, SimilarShapeBatcher
 from imagescry_amd.data import EmbeddingBatch, ImageBatch
 from imagescry_amd.decomposition import PCA, KMeans
 from imagescry_amd.embedding import (
+    CLIPEmbedder,
     DINOv2Embedder,
     EfficientNetEmbedder,
     EmbeddingModule,
@@ -32,6 +35,7 @@ from imagescry_amd.search import EmbeddingBank, RangeResult, RowFilter, SearchHa
 from imagescry_amd.transforms import normalize_per_channel, resize, to_4d
 
 __all__ = [
+    "CLIPEmbedder",
     "DINOv2Embedder",
     "EfficientNetEmbedder",
     "EmbeddingBank",
@@ -47,6 +51,7 @@ __all__ = [
     "RowFilter",
     "ResNet50Embedder",
     "ViTB16Embedder",
+    "clip",
     "l2_normalize_channels",
     "ImageBatch",
     "ImageTensorDataset",

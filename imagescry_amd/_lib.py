@@ -22,7 +22,7 @@ LIB_NAME = "libimagescry_hip.so"
 LIB_PATH = Path(os.environ.get("ISC_LIB") or Path(__file__).resolve().parent / LIB_NAME)
 
 ISC_U8, ISC_F16, ISC_F32 = 0, 1, 2
-ISC_ACT_NONE, ISC_ACT_RELU, ISC_ACT_GELU, ISC_ACT_SILU, ISC_ACT_SIGMOID = 0, 1, 2, 3, 4
+ISC_ACT_NONE, ISC_ACT_RELU, ISC_ACT_GELU, ISC_ACT_SILU, ISC_ACT_SIGMOID, ISC_ACT_QUICK_GELU = 0, 1, 2, 3, 4, 5
 ISC_ACT_RESIDUAL_AFTER = 0x100
 ISC_TOPK_MAX_K = 120
 ISC_TOPK_LARGE_MAX_K = 4096  # isc_cosine_topk_large / isc_cosine_topk_exhaustive_large
@@ -170,6 +170,15 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "isc_attention_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "isc_attention_f16_stream": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "isc_attention_stream_geometry": (c_int, [POINTER(c_int), POINTER(c_int)]),
+    "isc_attention_f16_causal": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "isc_text_embed": (
+        c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    ),
+    "isc_text_pool_layernorm": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int,
+         c_void_p],
+    ),
     "isc_patchify_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "isc_vit_assemble": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "isc_vit_pos_resample": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -48,6 +48,13 @@ static inline T isc_ceil_div(T a, T b) {
 
 static inline size_t isc_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// ISC_ACT_QUICK_GELU, v * sigmoid(1.702 v), in the form include/imagescry_hip.h states: one product, v_exp_f32, one
+// addition, a reciprocal, one product.  exp2 saturates to +inf / 0 for large |v|, where the result is -0 / v.
+__device__ __forceinline__ float isc_quick_gelu(float v) {
+    const float e = __builtin_amdgcn_exp2f(v * -2.4554669595930157f);  // exp(-1.702 v)
+    return v * __frcp_rn(1.f + e);
+}
+
 // ---- wave-level reductions (64 lanes) ---------------------------------------------------------
 __device__ __forceinline__ float isc_wave_sum(float v) {
 #pragma unroll

@@ -98,7 +98,8 @@ __device__ __forceinline__ bool gemm_tile(const GemmParams& p, long long& m0, in
 // DBG (ISC_GEMM_DEBUG, bring-up only, wrong results): 1 = no DMA after the prologue, 2 = no fragment reads, 3 = no MFMAs,
 // 4 = no epilogue (nothing stored).
 // SCALED (isc_gemm_f16_scaled, LayerScale): out = residual + scale[n] * (product + bias[n]), float32 out, no activation.
-template <int DBG, bool SCALED = false>
+// QGELU (ISC_ACT_QUICK_GELU): isc_quick_gelu in place of the run-time choice between no activation and GELU.
+template <int DBG, bool SCALED = false, bool QGELU = false>
 __global__ __launch_bounds__(256, 2) void k_gemm_f16_dma(const GemmParams p) {
     constexpr int STAGE = 32768;  // [weights 128 rows | activations 128 rows] x 128 B
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * STAGE];
@@ -261,7 +262,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16_dma(const GemmParams p) {
         for (int mi = 0; mi < 4; ++mi) {
             v[mi] = acc[mi][ni] + bias[mi];
             if constexpr (SCALED) v[mi] *= scale[mi];
-            if (!SCALED && p.act == ISC_ACT_GELU) {
+            if constexpr (QGELU) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[mi][q] = isc_quick_gelu(v[mi][q]);
+            } else if (!SCALED && p.act == ISC_ACT_GELU) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[mi][q] = gelu_fast(v[mi][q]);
             }
@@ -543,6 +547,107 @@ __global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ x, 
             *reinterpret_cast<half4*>(reinterpret_cast<_Float16*>(y) + at) = h;
         }
     }
+}
+
+// k_layernorm's arithmetic on input row `in_row` of x into output row `row` of y, for k_text_pool_layernorm.  A second
+// copy, statement for statement: with this function inlined into it k_layernorm itself compiles to one or two more VGPRs
+// in five of its ten instantiations, and it keeps its figures.  Change the two together: tests/test_gpu_clip.py holds
+// isc_text_pool_layernorm to the bits isc_layernorm gives on the pooled rows, for every NV and output form.
+template <bool OUT_F32, int NV>
+__device__ __forceinline__ void layernorm_row(const float* __restrict__ x, long long in_row, long long row, int D,
+                                              long long ldx, const float* __restrict__ gamma,
+                                              const float* __restrict__ beta, float eps, void* __restrict__ y,
+                                              long long ldy, int y_packed) {
+    const int lane = threadIdx.x & 63;
+    const float* xr = x + (size_t)in_row * ldx;
+    const int nvec = D >> 2;
+    f32x4 v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c < nvec) v[i] = *reinterpret_cast<const f32x4*>(xr + 4 * c);
+        s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+    }
+    const float mean = isc_wave_sum(s) / (float)D;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nvec) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float d = v[i][r] - mean;
+                q += d * d;
+            }
+        }
+    }
+    const float rstd = 1.f / sqrtf(isc_wave_sum(q) / (float)D + eps);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = lane + 64 * i;
+        if (c >= nvec) continue;
+        const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + 4 * c);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(beta + 4 * c);
+        f32x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = (v[i][r] - mean) * rstd * g[r] + b[r];
+        if (OUT_F32) {
+            *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(y) + (size_t)row * ldy + 4 * c) = o;
+        } else {
+            half4 h = half4{(_Float16)o[0], (_Float16)o[1], (_Float16)o[2], (_Float16)o[3]};
+            const size_t at = y_packed ? pk_offset(row, 4 * c, D) : (size_t)row * ldy + 4 * c;
+            *reinterpret_cast<half4*>(reinterpret_cast<_Float16*>(y) + at) = h;
+        }
+    }
+}
+
+// The pooling head of a text tower (isc_text_pool_layernorm): a wave per sequence finds the pooled position -- the first
+// id equal to eos_id, else the first maximum id -- and runs layernorm_row on that token row into output row b.
+template <bool OUT_F32, int NV>
+__global__ __launch_bounds__(256) void k_text_pool_layernorm(const float* __restrict__ tokens,
+                                                             const long long* __restrict__ ids, int B, int T, int D,
+                                                             long long eos_id, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, float eps,
+                                                             void* __restrict__ y, int y_packed) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    const long long* row_ids = ids + (size_t)b * T;
+    int eos_at = T;              // first position holding eos_id among this lane's
+    long long top = row_ids[0];  // the lane's largest id and its first position
+    int top_at = 0;
+    for (int t = lane; t < T; t += 64) {
+        const long long id = row_ids[t];
+        if (eos_id >= 0 && id == eos_id && t < eos_at) eos_at = t;
+        if (id > top) {  // positions ascend within a lane: `>` keeps the first
+            top = id;
+            top_at = t;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        eos_at = min(eos_at, __shfl_xor(eos_at, off, 64));
+        const long long o_top = __shfl_xor(top, off, 64);
+        const int o_at = __shfl_xor(top_at, off, 64);
+        if (o_top > top || (o_top == top && o_at < top_at)) {
+            top = o_top;
+            top_at = o_at;
+        }
+    }
+    const int t = eos_at < T ? eos_at : top_at;
+    layernorm_row<OUT_F32, NV>(tokens, (long long)b * T + t, b, D, D, gamma, beta, eps, y, D, y_packed);
+}
+
+template <bool OUT_F32>
+void launch_text_pool(int nv, dim3 grid, hipStream_t s, const float* tokens, const long long* ids, int B, int T, int D,
+                      long long eos_id, const float* gamma, const float* beta, float eps, void* y, int y_packed) {
+    if (nv <= 1) hipLaunchKernelGGL((k_text_pool_layernorm<OUT_F32, 1>), grid, dim3(256), 0, s, tokens, ids, B, T, D, eos_id, gamma, beta, eps, y, y_packed);
+    else if (nv <= 2) hipLaunchKernelGGL((k_text_pool_layernorm<OUT_F32, 2>), grid, dim3(256), 0, s, tokens, ids, B, T, D, eos_id, gamma, beta, eps, y, y_packed);
+    else if (nv <= 3) hipLaunchKernelGGL((k_text_pool_layernorm<OUT_F32, 3>), grid, dim3(256), 0, s, tokens, ids, B, T, D, eos_id, gamma, beta, eps, y, y_packed);
+    else if (nv <= 4) hipLaunchKernelGGL((k_text_pool_layernorm<OUT_F32, 4>), grid, dim3(256), 0, s, tokens, ids, B, T, D, eos_id, gamma, beta, eps, y, y_packed);
+    else hipLaunchKernelGGL((k_text_pool_layernorm<OUT_F32, 8>), grid, dim3(256), 0, s, tokens, ids, B, T, D, eos_id, gamma, beta, eps, y, y_packed);
 }
 
 template <bool OUT_F32>
@@ -888,6 +993,28 @@ __global__ __launch_bounds__(256) void k_vit_assemble(const float* __restrict__ 
     }
 }
 
+// tokens[bt] = table[ids[bt]] + pos[bt % T]: one float32 addition per element.  An id outside [0, vocab) never indexes
+// the table: its row is zeros, and the thread that writes the row's first vector counts it in *bad (when given).
+__global__ __launch_bounds__(256) void k_text_embed(const long long* __restrict__ ids, int T, int vocab, int D,
+                                                    const float* __restrict__ table, const float* __restrict__ pos,
+                                                    size_t total4, float* __restrict__ y, int* __restrict__ bad) {
+    const int dv = D / 4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % dv);
+        const size_t bt = i / dv;
+        const int t = (int)(bt % T);
+        const long long id = ids[bt];
+        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (id >= 0 && id < vocab) {
+            v = *reinterpret_cast<const f32x4*>(table + (size_t)id * D + 4 * c);
+            v += *reinterpret_cast<const f32x4*>(pos + (size_t)t * D + 4 * c);
+        } else if (c == 0 && bad) {
+            atomicAdd(bad, 1);
+        }
+        *reinterpret_cast<f32x4*>(y + i * 4) = v;
+    }
+}
+
 }  // namespace
 int isc_gemm_f16_stream_launch(const void* a, long long M, int K, const void* w, int N, const float* bias,
                                const float* scale, const float* residual, int epi, void* out, int out_packed,
@@ -925,7 +1052,7 @@ GemmParams gemm_params(const void* a, int64_t M, int K, const void* w, int N, co
 extern "C" int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int N, const float* bias,
                             const float* residual, int act, void* out, int out_dtype, int flags, void* stream) {
     ISC_REQUIRE(a && w && out && M > 0 && K > 0 && N > 0);
-    ISC_REQUIRE(act == ISC_ACT_NONE || act == ISC_ACT_GELU);
+    ISC_REQUIRE(act == ISC_ACT_NONE || act == ISC_ACT_GELU || act == ISC_ACT_QUICK_GELU);
     ISC_REQUIRE(out_dtype == ISC_F16 || out_dtype == ISC_F32);
     ISC_REQUIRE((flags & ~(ISC_GEMM_A_PACKED | ISC_GEMM_W_PACKED | ISC_GEMM_OUT_PACKED | ISC_GEMM_TILE_256 |
                            ISC_GEMM_TILE_128)) == 0);
@@ -939,7 +1066,7 @@ extern "C" int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int 
     // older kernels below explicitly.
     if ((flags & ISC_GEMM_A_PACKED) && (flags & ISC_GEMM_W_PACKED) && !(flags & (ISC_GEMM_TILE_128 | ISC_GEMM_TILE_256)) &&
         N % 256 == 0 && !(out_dtype == ISC_F32 && act != ISC_ACT_NONE) && !(out_dtype == ISC_F16 && residual)) {
-        const int epi = out_dtype == ISC_F32 ? 2 : act == ISC_ACT_GELU ? 1 : 0;
+        const int epi = out_dtype == ISC_F32 ? 2 : act == ISC_ACT_GELU ? 1 : act == ISC_ACT_QUICK_GELU ? 4 : 0;
         isc_timing_begin(ISC_KERNEL_GEMM_F16, isc_stream(stream));
         const int st = isc_gemm_f16_stream_launch(a, M, K, w, N, bias, nullptr, residual, epi, out,
                                                   (flags & ISC_GEMM_OUT_PACKED) != 0, isc_stream(stream));
@@ -972,6 +1099,10 @@ extern "C" int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int 
         else
 #endif
             hipLaunchKernelGGL(k_gemm_f16_big<0>, dim3((unsigned)grid2), dim3(256), 0, s, p);
+    } else if (act == ISC_ACT_QUICK_GELU) {
+        // DBG = 0 in every build: the ISC_GEMM_DEBUG bring-up variants below exist for the plain instantiation only
+        hipLaunchKernelGGL((k_gemm_f16_dma<0, false, true>), dim3((unsigned)(isc_ceil_div<long long>(tiles, 8) * 8)), dim3(256), 0,
+                           s, p);
     } else {
         const long long grid1 = isc_ceil_div<long long>(tiles, 8) * 8;
 #ifdef ISC_ABLATION
@@ -995,7 +1126,7 @@ extern "C" int isc_gemm_f16_scaled(const void* a, int64_t M, int K, const void* 
                                    const float* scale, const float* residual, int act, void* out, int out_dtype,
                                    int flags, void* stream) {
     ISC_REQUIRE(a && w && out && scale && M > 0 && K > 0 && N > 0);
-    ISC_REQUIRE(act == ISC_ACT_NONE || act == ISC_ACT_GELU);
+    ISC_REQUIRE(act == ISC_ACT_NONE || act == ISC_ACT_GELU || act == ISC_ACT_QUICK_GELU);
     ISC_REQUIRE(out_dtype == ISC_F16 || out_dtype == ISC_F32);
     ISC_REQUIRE((flags & ~(ISC_GEMM_A_PACKED | ISC_GEMM_W_PACKED | ISC_GEMM_OUT_PACKED | ISC_GEMM_TILE_256 |
                            ISC_GEMM_TILE_128)) == 0);
@@ -1152,4 +1283,37 @@ extern "C" int isc_vit_assemble_reg(const float* patch_embed, const float* cls_t
 extern "C" int isc_vit_assemble(const float* patch_embed, const float* cls_token, const float* pos_embed, int B, int T,
                                 int D, float* tokens, void* stream) {
     return isc_vit_assemble_reg(patch_embed, cls_token, nullptr, pos_embed, B, T, 0, D, tokens, stream);
+}
+
+extern "C" int isc_text_embed(const int64_t* ids, int B, int T, int vocab, int D, const float* table, const float* pos,
+                              float* tokens, int32_t* bad_count, void* stream) {
+    ISC_REQUIRE(ids && table && pos && tokens && B > 0 && T > 0 && vocab > 0 && D > 0);
+    if (D % 4 != 0) return ISC_ERR_UNSUPPORTED;
+    if (!isc_aligned(ids, 8) || !isc_aligned(table, 16) || !isc_aligned(pos, 16) || !isc_aligned(tokens, 16) ||
+        (bad_count && !isc_aligned(bad_count, 4)))
+        return ISC_ERR_ALIGNMENT;
+    const size_t total4 = (size_t)B * T * (D / 4);
+    hipLaunchKernelGGL(k_text_embed, dim3(grid_for(total4)), dim3(256), 0, isc_stream(stream),
+                       reinterpret_cast<const long long*>(ids), T, vocab, D, table, pos, total4, tokens,
+                       reinterpret_cast<int*>(bad_count));
+    return isc_launch_status();
+}
+
+extern "C" int isc_text_pool_layernorm(const float* tokens, const int64_t* ids, int B, int T, int D, int64_t eos_id,
+                                       const float* gamma, const float* beta, float eps, void* out, int out_dtype,
+                                       int out_packed, void* stream) {
+    ISC_REQUIRE(tokens && ids && gamma && beta && out && B > 0 && T > 0 && D > 0 && eps >= 0.f);
+    ISC_REQUIRE(out_dtype == ISC_F16 || out_dtype == ISC_F32);
+    if (D % 4 != 0 || D > 2048) return ISC_ERR_UNSUPPORTED;
+    if (out_packed && (out_dtype != ISC_F16 || D % 64 != 0)) return ISC_ERR_UNSUPPORTED;
+    if (!isc_aligned(tokens, 16) || !isc_aligned(ids, 8) || !isc_aligned(gamma, 16) || !isc_aligned(beta, 16) ||
+        !isc_aligned(out, 16))
+        return ISC_ERR_ALIGNMENT;
+    const dim3 grid((unsigned)isc_ceil_div<long long>(B, 4));
+    hipStream_t s = isc_stream(stream);
+    const long long* idp = reinterpret_cast<const long long*>(ids);
+    const int nv = (D / 4 + 63) / 64;
+    if (out_dtype == ISC_F32) launch_text_pool<true>(nv, grid, s, tokens, idp, B, T, D, (long long)eos_id, gamma, beta, eps, out, 0);
+    else launch_text_pool<false>(nv, grid, s, tokens, idp, B, T, D, (long long)eos_id, gamma, beta, eps, out, out_packed ? 1 : 0);
+    return isc_launch_status();
 }

@@ -15,11 +15,11 @@ from typing import Iterable
 import torch
 from torch import Tensor
 
-from imagescry_amd import _lib, efficientnet, resnet50, vit
+from imagescry_amd import _lib, clip, efficientnet, resnet50, vit
 from imagescry_amd.data import EmbeddingBatch, ImageBatch
 from imagescry_amd.transforms import normalize_per_channel, resize
 
-__all__ = ["DINOv2Embedder", "EfficientNetEmbedder", "EmbeddingModule", "ResNet50Embedder", "ViTB16Embedder", "l2_normalize_channels"]
+__all__ = ["CLIPEmbedder", "DINOv2Embedder", "EfficientNetEmbedder", "EmbeddingModule", "ResNet50Embedder", "ViTB16Embedder", "l2_normalize_channels"]
 
 
 def l2_normalize_channels(x: Tensor, eps: float = 1e-12) -> Tensor:
@@ -460,14 +460,15 @@ class ViTB16Embedder(EmbeddingModule):
 
     @property
     def embedding_dim(self) -> int:
-        return self.config.dim
+        return self.config.embed_dim or self.config.dim  # a projection head (CLIP) sets the width
 
     @property
     def _patch_cap(self) -> int:
         """The most patches an aspect grid may hold."""
         return self.config.grid**2 if self.max_patches is None else self.max_patches
 
-    def preprocess(self, images: Tensor) -> Tensor:
+    def _resized(self, images: Tensor) -> Tensor:
+        """uint8 `[B, C, H, W]` at the size this mode's `forward` takes: `image_size` squared, or the aspect grid's."""
         if not isinstance(images, Tensor) or images.dtype != torch.uint8:
             raise TypeError("images must be a uint8 tensor")
         if images.ndim != 4:
@@ -479,7 +480,10 @@ class ViTB16Embedder(EmbeddingModule):
             size = (self.config.image_size, self.config.image_size)
         if tuple(images.shape[-2:]) != size:
             images = resize(images, output_size=size)
-        return normalize_per_channel(images, min_value=-3, max_value=3)
+        return images
+
+    def preprocess(self, images: Tensor) -> Tensor:
+        return normalize_per_channel(self._resized(images), min_value=-3, max_value=3)
 
     def _token_grid_of(self, x: Tensor) -> tuple[int, int]:
         """The token grid `forward` runs a float32 input on, or ValueError for a shape this mode does not take."""
@@ -515,7 +519,7 @@ class ViTB16Embedder(EmbeddingModule):
                     vit.forward_tokens(self._net, x[b0 : b0 + step], grid, normalize=normalized, out=out[b0 : b0 + step],
                                        max_patches=cap)
             return out
-        out = torch.empty((b, self.config.dim), dtype=torch.float32, device=x.device)
+        out = torch.empty((b, self.embedding_dim), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             for b0 in range(0, b, step):
                 out[b0 : b0 + step] = vit.forward_cls(self._net, x[b0 : b0 + step], grid, max_patches=cap)
@@ -577,3 +581,81 @@ class DINOv2Embedder(ViTB16Embedder):
         super().__init__(config=DINOV2_PRESETS[variant, registers], state_dict=state_dict, seed=seed,
                          max_images_per_pass=max_images_per_pass, output=output, grid=grid, max_patches=max_patches)
         self.hparams.update(variant=variant, registers=registers)
+
+
+class CLIPEmbedder(ViTB16Embedder):
+    """CLIP: images and texts in one space.  The vision tower is `ViTB16Embedder` on a `clip.PRESETS` configuration
+    ("ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336": a LayerNorm in front of the blocks and a bias-free projection
+    to E = 512 / 768 dimensions behind the class token) and yields `[B, E, 1, 1]` rows for an `EmbeddingBank`;
+    `encode_text` runs the text tower on token ids and returns unit-norm float32 `[Q, E]` queries for `bank.search`.
+
+    `state_dict` holds both towers under `clip`'s names (`clip.from_openai_state_dict`, `clip.from_transformers_state_dict`,
+    `clip.make_state_dict`); without it the weights are seeded random ones.  `act` is a property of the checkpoint:
+    "quick_gelu" for OpenAI's, "gelu" for open_clip / LAION ones.  `preset` may also be a `clip.CLIPConfig`.
+    `output="patches"` is refused: a projected patch map is not what the checkpoints were trained to align with text.
+
+    `preprocess` is this package's squash-`resize` to `image_size` (or, with `grid="aspect"`, to the aspect grid) and
+    `normalize_per_channel` with CLIP's FIXED statistics (`clip.IMAGE_MEAN`, `clip.IMAGE_STD`, times 255; no eps, no
+    clipping) -- batch statistics would break the alignment with the text side.  The checkpoints' own pipeline differs:
+    it resizes the SHORTER side to `image_size` bicubically and crops the centre square, so it sees no squashed and no
+    border content.  `forward` takes any float32 input a caller preprocessed themselves."""
+
+    def __init__(
+        self,
+        preset: str | clip.CLIPConfig = "ViT-B/16",
+        *,
+        state_dict: dict[str, Tensor] | None = None,
+        act: str = "quick_gelu",
+        seed: int = 0,
+        max_images_per_pass: int = 1024,
+        output: str = "cls",
+        grid: str = "fixed",
+        max_patches: int | None = None,
+    ) -> None:
+        if isinstance(preset, clip.CLIPConfig):
+            cfg = preset
+        elif preset in clip.PRESETS:
+            cfg = clip.PRESETS[preset]
+        else:
+            raise ValueError(f"preset must be one of {sorted(clip.PRESETS)} or a clip.CLIPConfig, got {preset!r}")
+        if output != "cls":
+            raise ValueError(f'CLIPEmbedder has no output={output!r}: only the projected class token ("cls") lives in '
+                             "the text tower's space")
+        cfg = clip.with_act(cfg, act)
+        sd = state_dict if state_dict is not None else clip.make_state_dict(cfg, seed=seed)
+        super().__init__(config=cfg.vision, state_dict=clip.tower(sd, "visual"), seed=seed,
+                         max_images_per_pass=max_images_per_pass, output=output, grid=grid, max_patches=max_patches)
+        self.clip_config = cfg
+        self._text = clip.prepare_text(clip.tower(sd, "text"), cfg.text)
+        self.hparams.update(act=act, embed_dim=cfg.embed_dim)
+        if isinstance(preset, str):
+            self.hparams.update(preset=preset)
+        self._stats: dict[torch.device, tuple[Tensor, Tensor]] = {}
+
+    def _move(self, device: torch.device) -> None:
+        super()._move(device)
+        self._text = self._text.to(device)
+
+    def preprocess(self, images: Tensor) -> Tensor:
+        images = self._resized(images)
+        if images.ndim != 4 or images.shape[1] != 3:
+            raise ValueError(f"images must have shape [B, 3, H, W], got {tuple(images.shape)}")
+        if images.device not in self._stats:
+            self._stats[images.device] = tuple(
+                (torch.tensor(v, device=images.device) * 255.0).reshape(1, 3, 1, 1) for v in (clip.IMAGE_MEAN, clip.IMAGE_STD))
+        mean, std = self._stats[images.device]
+        return normalize_per_channel(images, channel_means=mean, channel_stds=std, eps=0.0)
+
+    def encode_text(self, ids: Tensor, *, normalize: bool = True, validate: bool = True) -> Tensor:
+        """int64 / int32 `[Q, T <= context]` token ids (on the module's device, or on the CPU: copied over) -> float32
+        `[Q, E]` on the device, unit norm unless `normalize=False`.  `validate` (`clip.forward_text`): ids outside the
+        vocabulary raise ValueError after one host read; without it the call makes none."""
+        clip.check_ids(ids, self.clip_config.text)
+        if self.device.type != "cuda":
+            raise _lib.HipLibraryError("the module is on the CPU; call .to() first: imagescry_amd runs on HIP devices only")
+        if ids.device.type == "cpu":
+            ids = ids.to(self.device)
+        elif ids.device != self.device:
+            raise ValueError(f"module is on {self.device} but ids are on {ids.device}")
+        q = clip.forward_text(self._text, ids, validate=validate)
+        return l2_normalize_channels(q[:, :, None, None]).reshape(q.shape) if normalize and q.shape[0] else q

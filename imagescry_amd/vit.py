@@ -38,6 +38,9 @@ class ViTConfig:
     registers: int = 0  # register tokens between the class token and the patches (no position embedding)
     layerscale: bool = False  # per-channel scale (`ls1.gamma`, `ls2.gamma`) on the attention and the MLP branch
     pos_antialias: bool = False  # resample the position table with antialiasing (the register checkpoints)
+    pre_norm: bool = False  # a LayerNorm (`norm_pre.*`) between the token assembly and the first block (CLIP)
+    act: str = "gelu"  # the MLP activation: "gelu" (erf form) or "quick_gelu" (x * sigmoid(1.702 x), OpenAI CLIP)
+    embed_dim: int = 0  # > 0: a bias-free projection `head.weight` [embed_dim, dim] behind the class token's norm (CLIP)
 
     @property
     def grid(self) -> int:
@@ -95,7 +98,8 @@ def make_state_dict(cfg: ViTConfig = VIT_B16, *, seed: int = 0, randomize_affine
     """Seeded random parameters (CPU float32): truncated-normal(std 0.02) weights / tokens, zero biases and identity
     LayerNorms -- or, with `randomize_affine`, random biases and LayerNorm affines so that every term is exercised.
     Register tokens and LayerScale factors (ones; with `randomize_affine` log-uniform in [1e-5, 1], the range trained
-    checkpoints cover) are drawn after everything else: a seed gives the other keys the same tensors with or without."""
+    checkpoints cover) are drawn after everything else: a seed gives the other keys the same tensors with or without;
+    `norm_pre.*` and the bias-free `head.weight` of a config with `pre_norm` / `embed_dim` follow them."""
     g = torch.Generator().manual_seed(seed)
 
     def tn(*shape: int) -> Tensor:
@@ -130,6 +134,10 @@ def make_state_dict(cfg: ViTConfig = VIT_B16, *, seed: int = 0, randomize_affine
             for name in ("ls1", "ls2"):
                 sd[f"blocks.{i}.{name}.gamma"] = (10.0 ** (-5.0 * torch.rand(d, generator=g)) if randomize_affine
                                                   else torch.ones(d))
+    if cfg.pre_norm:
+        sd["norm_pre.weight"], sd["norm_pre.bias"] = gamma(d), bias(d)
+    if cfg.embed_dim:
+        sd["head.weight"] = tn(cfg.embed_dim, d)
     return sd
 
 
@@ -165,7 +173,7 @@ def packed_elems(rows: int, cols: int) -> int:
 @dataclass
 class Linear:
     weight: Tensor  # fp16, PACKED [out, in] (pack_rows of the torch.nn.Linear weight)
-    bias: Tensor  # float32 [out]
+    bias: Tensor | None  # float32 [out]; None: no bias (the CLIP projections)
     out_features: int = 0
     in_features: int = 0
 
@@ -174,7 +182,8 @@ class Linear:
             raise ValueError("Linear needs its logical shape")
 
     def to(self, device: torch.device) -> "Linear":
-        return Linear(self.weight.to(device), self.bias.to(device), self.out_features, self.in_features)
+        return Linear(self.weight.to(device), None if self.bias is None else self.bias.to(device), self.out_features,
+                      self.in_features)
 
 
 @dataclass
@@ -211,6 +220,8 @@ class PreparedViT:
     blocks: list[Block] = field(default_factory=list)
     norm: Norm | None = None
     reg_tokens: Tensor | None = None  # float32 [registers, D]
+    norm_pre: Norm | None = None  # cfg.pre_norm
+    head: Linear | None = None  # cfg.embed_dim: [embed_dim, D], no bias
     # resampled position tables, (h, w) -> float32 [1 + h * w, D] on pos_embed's device; belongs to THIS prepared net
     # (`to` starts an empty one), bounded by POS_CACHE_MAX
     pos_cache: dict[tuple[int, int], Tensor] = field(default_factory=dict, repr=False, compare=False)
@@ -218,7 +229,33 @@ class PreparedViT:
     def to(self, device: torch.device) -> "PreparedViT":
         return PreparedViT(self.cfg, self.cls_token.to(device), self.pos_embed.to(device), self.patch.to(device),
                            [b.to(device) for b in self.blocks], self.norm.to(device),
-                           None if self.reg_tokens is None else self.reg_tokens.to(device))
+                           None if self.reg_tokens is None else self.reg_tokens.to(device),
+                           None if self.norm_pre is None else self.norm_pre.to(device),
+                           None if self.head is None else self.head.to(device))
+
+
+ACTIVATIONS = {"gelu": _lib.ISC_ACT_GELU, "quick_gelu": _lib.ISC_ACT_QUICK_GELU}
+
+
+def prepare_linear(sd: dict[str, Tensor], name: str, pad_to: int = 0, bias: bool = True) -> Linear:
+    """`name.weight` (any trailing shape, flattened to `[out, in]`) cast to fp16, its inner dimension zero-padded to
+    `pad_to`, packed; `name.bias` in float32, or no bias."""
+    w = sd[f"{name}.weight"]
+    w2 = w.reshape(w.shape[0], -1).to(torch.float16)
+    if pad_to > w2.shape[1]:
+        w2 = torch.nn.functional.pad(w2, (0, pad_to - w2.shape[1]))
+    return Linear(pack_rows(w2), sd[f"{name}.bias"].float().contiguous() if bias else None, w2.shape[0], w2.shape[1])
+
+
+def prepare_norm(sd: dict[str, Tensor], name: str) -> Norm:
+    return Norm(sd[f"{name}.weight"].float().contiguous(), sd[f"{name}.bias"].float().contiguous())
+
+
+def prepare_block(sd: dict[str, Tensor], p: str, ls1: Tensor | None = None, ls2: Tensor | None = None) -> Block:
+    """The pre-LN block `p` = "blocks.i" of a state dict under this module's names."""
+    return Block(prepare_norm(sd, f"{p}.norm1"), prepare_linear(sd, f"{p}.attn.qkv"), prepare_linear(sd, f"{p}.attn.proj"),
+                 prepare_norm(sd, f"{p}.norm2"), prepare_linear(sd, f"{p}.mlp.fc1"), prepare_linear(sd, f"{p}.mlp.fc2"),
+                 ls1, ls2)
 
 
 def prepare(sd: dict[str, Tensor], cfg: ViTConfig = VIT_B16) -> PreparedViT:
@@ -226,12 +263,17 @@ def prepare(sd: dict[str, Tensor], cfg: ViTConfig = VIT_B16) -> PreparedViT:
     biases / LayerNorm / LayerScale / tokens in float32.  The patch weight's inner dimension is zero-padded to whole K
     steps of 64 (`cfg.patch_kdim`: 588 -> 640 for a patch size of 14).  LayerScale stays a float32 vector for the GEMM
     epilogue: trained values go down to 1e-5, and folded into the weights they would land in fp16 subnormals.
-    `register_tokens` may be spelled `reg_token` (timm); `mask_token` is ignored."""
+    `register_tokens` may be spelled `reg_token` (timm); `mask_token` is ignored.  `cfg.pre_norm` asks for `norm_pre.*`,
+    `cfg.embed_dim` for a `head.weight` of shape `[embed_dim, dim]` (no bias)."""
     d = cfg.dim
     if cfg.dim % 64 or cfg.mlp_dim % 64 or cfg.dim // cfg.heads != 64:
         raise ValueError("this build supports head size 64 and GEMM inner dimensions that are multiples of 64")
     if cfg.patch_size % 2:
         raise ValueError(f"this build supports even patch sizes, got {cfg.patch_size}")
+    if cfg.act not in ACTIVATIONS:
+        raise ValueError(f"act must be one of {sorted(ACTIVATIONS)}, got {cfg.act!r}")
+    if cfg.embed_dim < 0 or cfg.embed_dim % 4:
+        raise ValueError(f"embed_dim must be a non-negative multiple of 4, got {cfg.embed_dim}")
     rows = 1 + cfg.grid**2
     if tuple(sd["pos_embed"].shape) != (1, rows, d):
         raise ValueError(f"pos_embed has shape {tuple(sd['pos_embed'].shape)}, expected (1, {rows}, {d})")
@@ -241,21 +283,12 @@ def prepare(sd: dict[str, Tensor], cfg: ViTConfig = VIT_B16) -> PreparedViT:
             raise ValueError(f"the config asks for {what}, but the state dict has no `{key}`")
         return sd[key]
 
-    def lin(name: str, pad_to: int = 0) -> Linear:
-        w = sd[f"{name}.weight"]
-        w2 = w.reshape(w.shape[0], -1).to(torch.float16)
-        if pad_to > w2.shape[1]:
-            w2 = torch.nn.functional.pad(w2, (0, pad_to - w2.shape[1]))
-        return Linear(pack_rows(w2), sd[f"{name}.bias"].float().contiguous(), w2.shape[0], w2.shape[1])
-
     def scale(key: str) -> Tensor | None:
         return need(key, "LayerScale").reshape(d).float().contiguous() if cfg.layerscale else None
 
-    def norm(name: str) -> Norm:
-        return Norm(sd[f"{name}.weight"].float().contiguous(), sd[f"{name}.bias"].float().contiguous())
-
     net = PreparedViT(cfg, sd["cls_token"].reshape(d).float().contiguous(),
-                      sd["pos_embed"].reshape(rows, d).float().contiguous(), lin("patch_embed.proj", cfg.patch_kdim))
+                      sd["pos_embed"].reshape(rows, d).float().contiguous(),
+                      prepare_linear(sd, "patch_embed.proj", cfg.patch_kdim))
     if cfg.registers:
         key = "register_tokens" if "register_tokens" in sd or "reg_token" not in sd else "reg_token"
         reg = need(key, f"{cfg.registers} register tokens")
@@ -264,10 +297,16 @@ def prepare(sd: dict[str, Tensor], cfg: ViTConfig = VIT_B16) -> PreparedViT:
         net.reg_tokens = reg.reshape(cfg.registers, d).float().contiguous()
     for i in range(cfg.depth):
         p = f"blocks.{i}"
-        net.blocks.append(Block(norm(f"{p}.norm1"), lin(f"{p}.attn.qkv"), lin(f"{p}.attn.proj"), norm(f"{p}.norm2"),
-                                lin(f"{p}.mlp.fc1"), lin(f"{p}.mlp.fc2"), scale(f"{p}.ls1.gamma"),
-                                scale(f"{p}.ls2.gamma")))
-    net.norm = norm("norm")
+        net.blocks.append(prepare_block(sd, p, scale(f"{p}.ls1.gamma"), scale(f"{p}.ls2.gamma")))
+    net.norm = prepare_norm(sd, "norm")
+    if cfg.pre_norm:
+        need("norm_pre.weight", "a LayerNorm in front of the blocks")
+        net.norm_pre = prepare_norm(sd, "norm_pre")
+    if cfg.embed_dim:
+        head = need("head.weight", f"a projection to {cfg.embed_dim} dimensions")
+        if tuple(head.shape) != (cfg.embed_dim, d):
+            raise ValueError(f"head.weight has shape {tuple(head.shape)}, expected ({cfg.embed_dim}, {d})")
+        net.head = prepare_linear(sd, "head", bias=False)
     return net
 
 
@@ -316,12 +355,12 @@ def _gemm(a: Tensor, m: int, lin: Linear, out: Tensor, *, act: int = _lib.ISC_AC
     flags = _lib.ISC_GEMM_A_PACKED | _lib.ISC_GEMM_W_PACKED | (_lib.ISC_GEMM_OUT_PACKED if f16 else 0)
     if scale is not None:
         st = _lib.load().isc_gemm_f16_scaled(a.data_ptr(), m, lin.in_features, lin.weight.data_ptr(), lin.out_features,
-                                             lin.bias.data_ptr(), scale.data_ptr(), _lib.ptr(residual), act,
+                                             _lib.ptr(lin.bias), scale.data_ptr(), _lib.ptr(residual), act,
                                              out.data_ptr(), _lib.ISC_F16 if f16 else _lib.ISC_F32, flags, stream)
         _lib.check(st, "isc_gemm_f16_scaled")
         return out
     st = _lib.load().isc_gemm_f16(a.data_ptr(), m, lin.in_features, lin.weight.data_ptr(), lin.out_features,
-                                  lin.bias.data_ptr(), _lib.ptr(residual), act, out.data_ptr(),
+                                  _lib.ptr(lin.bias), _lib.ptr(residual), act, out.data_ptr(),
                                   _lib.ISC_F16 if f16 else _lib.ISC_F32, flags, stream)
     _lib.check(st, "isc_gemm_f16")
     return out
@@ -409,19 +448,42 @@ def _encode(net: PreparedViT, x: Tensor, grid: tuple[int, int]) -> Tensor:
         _lib.check(lib.isc_vit_assemble(pe.data_ptr(), net.cls_token.data_ptr(), pos.data_ptr(), b, t, d,
                                         xa.data_ptr(), stream), "isc_vit_assemble")
     del pe
-    hbuf, qkv, att, mlp = packed(m, d), packed(m, 3 * d), packed(m, d), packed(m, cfg.mlp_dim)
-    for blk in net.blocks:
-        _layernorm_packed(xa, m, blk.norm1, cfg.ln_eps, hbuf, stream)
+    if cfg.pre_norm:  # float32 -> float32 into the other residual buffer
+        _lib.check(lib.isc_layernorm(xa.data_ptr(), m, d, d, net.norm_pre.weight.data_ptr(), net.norm_pre.bias.data_ptr(),
+                                     cfg.ln_eps, xb.data_ptr(), _lib.ISC_F32, d, 0, stream), "isc_layernorm")
+        xa, xb = xb, xa
+    return run_blocks(net.blocks, xa, xb, b, t, heads=cfg.heads, mlp_dim=cfg.mlp_dim, ln_eps=cfg.ln_eps, act=cfg.act)
+
+
+def run_blocks(blocks: list[Block], xa: Tensor, xb: Tensor, b: int, t: int, *, heads: int, mlp_dim: int, ln_eps: float,
+               act: str = "gelu", causal: bool = False) -> Tensor:
+    """The pre-LN transformer blocks over the float32 residual stream `xa` `[b * t, D]` (`xb`: a second buffer of that
+    shape); returns `xa`, which holds the stream after the last block.  `causal`: `isc_attention_f16_causal` (a text
+    tower, `t <= 128`) in place of the bidirectional kernels."""
+    m, d = xa.shape
+    dev = xa.device
+    lib = _lib.load()
+    stream = _lib.stream_handle(dev)
+
+    def packed(rows: int, cols: int) -> Tensor:  # as in `_encode`: left uninitialised
+        return torch.empty(packed_elems(rows, cols), dtype=torch.float16, device=dev)
+
+    hbuf, qkv, att, mlp = packed(m, d), packed(m, 3 * d), packed(m, d), packed(m, mlp_dim)
+    for blk in blocks:
+        _layernorm_packed(xa, m, blk.norm1, ln_eps, hbuf, stream)
         _gemm(hbuf, m, blk.qkv, qkv, stream=stream)
-        if t <= ONE_SHOT_TOKENS:
-            _lib.check(lib.isc_attention_f16(qkv.data_ptr(), b, t, cfg.heads, d // cfg.heads, att.data_ptr(), 1, stream),
+        if causal:
+            _lib.check(lib.isc_attention_f16_causal(qkv.data_ptr(), b, t, heads, d // heads, att.data_ptr(), 1, stream),
+                       "isc_attention_f16_causal")
+        elif t <= ONE_SHOT_TOKENS:
+            _lib.check(lib.isc_attention_f16(qkv.data_ptr(), b, t, heads, d // heads, att.data_ptr(), 1, stream),
                        "isc_attention_f16")
         else:  # the keys of a head no longer fit in LDS: the streaming kernel
-            _lib.check(lib.isc_attention_f16_stream(qkv.data_ptr(), b, t, cfg.heads, d // cfg.heads, att.data_ptr(), 1,
-                                                    stream), "isc_attention_f16_stream")
+            _lib.check(lib.isc_attention_f16_stream(qkv.data_ptr(), b, t, heads, d // heads, att.data_ptr(), 1, stream),
+                       "isc_attention_f16_stream")
         _gemm(att, m, blk.proj, xb, residual=xa, scale=blk.ls1, stream=stream)
-        _layernorm_packed(xb, m, blk.norm2, cfg.ln_eps, hbuf, stream)
-        _gemm(hbuf, m, blk.fc1, mlp, act=_lib.ISC_ACT_GELU, stream=stream)
+        _layernorm_packed(xb, m, blk.norm2, ln_eps, hbuf, stream)
+        _gemm(hbuf, m, blk.fc1, mlp, act=ACTIVATIONS[act], stream=stream)
         _gemm(mlp, m, blk.fc2, xa, residual=xb, scale=blk.ls2, stream=stream)
     return xa
 
@@ -446,6 +508,14 @@ def forward_cls(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = None
     _check_grid(net, x, grid, max_patches)
     b, d, t = x.shape[0], cfg.dim, grid[0] * grid[1] + cfg.num_prefix
     xa = _encode(net, x, grid)
+    if net.head is not None:  # LayerNorm of the class rows into a packed fp16 operand, then the projection: [B, E]
+        stream = _lib.stream_handle(x.device)
+        cls = torch.empty(packed_elems(b, d), dtype=torch.float16, device=x.device)
+        st = _lib.load().isc_layernorm(xa.data_ptr(), b, d, t * d, net.norm.weight.data_ptr(), net.norm.bias.data_ptr(),
+                                       cfg.ln_eps, cls.data_ptr(), _lib.ISC_F16, d, 1, stream)
+        _lib.check(st, "isc_layernorm")
+        return _gemm(cls, b, net.head, torch.empty((b, net.head.out_features), dtype=torch.float32, device=x.device),
+                     stream=stream)
     out = torch.empty((b, d), dtype=torch.float32, device=x.device)
     st = _lib.load().isc_layernorm(xa.data_ptr(), b, d, t * d, net.norm.weight.data_ptr(), net.norm.bias.data_ptr(),
                                    cfg.ln_eps, out.data_ptr(), _lib.ISC_F32, d, 0,
@@ -482,6 +552,7 @@ def forward_tokens(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = N
     return out
 
 
-__all__ = ["DINOV2_B14", "DINOV2_B14_REG", "DINOV2_L14", "DINOV2_L14_REG", "DINOV2_S14", "DINOV2_S14_REG", "MAX_PATCHES",
+__all__ = ["ACTIVATIONS", "DINOV2_B14", "DINOV2_B14_REG", "DINOV2_L14", "DINOV2_L14_REG", "DINOV2_S14", "DINOV2_S14_REG", "MAX_PATCHES",
            "VIT_B16", "ViTConfig", "forward_cls", "forward_tokens", "from_transformers_state_dict", "gemm_flops",
-           "images_per_pass", "make_state_dict", "pack_rows", "position_table", "prepare", "token_grid", "unpack_rows"]
+           "images_per_pass", "make_state_dict", "pack_rows", "position_table", "prepare", "prepare_block", "prepare_linear",
+           "prepare_norm", "run_blocks", "token_grid", "unpack_rows"]

@@ -59,6 +59,7 @@ extern "C" {
 #define ISC_ACT_GELU 2 /* exact erf form */
 #define ISC_ACT_SILU 3    /* x * sigmoid(x) */
 #define ISC_ACT_SIGMOID 4
+#define ISC_ACT_QUICK_GELU 5 /* x * sigmoid(1.702 x), the OpenAI CLIP checkpoints' activation (isc_gemm_f16 only) */
 #define ISC_ACT_RESIDUAL_AFTER 0x100 /* OR into `act`: out = act(conv + bias) + residual (default: residual inside act) */
 
 int isc_abi_version(void);
@@ -353,9 +354,16 @@ int isc_pool_linear_l2norm(const float* x, int B, int H, int W, int C, const flo
                                  N % 256 == 0: 256 x 256 tiles on the search kernel's LDS-DMA ring loop, the default) */
 
 /* out[M,N] = act(a[M,K] . w[N,K]^T + bias[N]) + residual[M,N].   a, w fp16, row-major (w in torch.nn.Linear layout)
- * or packed per `flags`; bias, residual float32 row-major (either may be NULL); act ISC_ACT_NONE or ISC_ACT_GELU
- * (0.5 x (1 + erf(x / sqrt 2)), erf by the Abramowitz-Stegun 7.1.26 polynomial, |error| <= 1.5e-7);
- * out fp16 or float32 (`out_dtype`).  K % 64 == 0, N % 4 == 0, all pointers 16-byte aligned. */
+ * or packed per `flags`; bias, residual float32 row-major (either may be NULL); out fp16 or float32 (`out_dtype`).
+ * K % 64 == 0, N % 4 == 0, all pointers 16-byte aligned.  `act`, applied in float32:
+ *   ISC_ACT_NONE
+ *   ISC_ACT_GELU        0.5 x (1 + erf(x / sqrt 2)), erf by the Abramowitz-Stegun 7.1.26 polynomial, |error| <= 1.5e-7
+ *   ISC_ACT_QUICK_GELU  exactly  v * rcp(1 + exp2(v * c)),  c = fl(-1.702 * log2(e)) = -2.4554670f:  one product, the
+ *                       hardware exp2, one addition, a reciprocal, one product.  For large |v| exp2 saturates to +inf
+ *                       or 0 and the activation is 0 or v; no finite v gives NaN.  (The zero is -0 out of the
+ *                       activation; the residual addition, which adds 0 when there is none, may make it +0.)
+ * Both activations run on the streaming and on the 128 x 128-tile kernel, with fp16 and with float32 output;
+ * ISC_GEMM_TILE_256 has no activation epilogue (ISC_ERR_UNSUPPORTED).  Any other `act`: ISC_ERR_INVALID_ARG. */
 int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int N, const float* bias, const float* residual,
                  int act, void* out, int out_dtype, int flags, void* stream);
 
@@ -364,7 +372,7 @@ int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int N, const fl
  * the residual is added; bias and residual may be NULL.  Everything else as isc_gemm_f16.  Built for the forms the
  * encoder reaches -- out_dtype == ISC_F32 and act == ISC_ACT_NONE, on the streaming kernel (packed a and w, N % 256
  * == 0) and on the 128 x 128-tile kernel (anything else, or ISC_GEMM_TILE_128).  ISC_ERR_UNSUPPORTED for out_dtype ==
- * ISC_F16 (and so for ISC_GEMM_OUT_PACKED), for act == ISC_ACT_GELU and for ISC_GEMM_TILE_256. */
+ * ISC_F16 (and so for ISC_GEMM_OUT_PACKED), for act == ISC_ACT_GELU or ISC_ACT_QUICK_GELU and for ISC_GEMM_TILE_256. */
 int isc_gemm_f16_scaled(const void* a, int64_t M, int K, const void* w, int N, const float* bias, const float* scale,
                         const float* residual, int act, void* out, int out_dtype, int flags, void* stream);
 
@@ -389,6 +397,30 @@ int isc_attention_f16_stream(const void* qkv, int B, int T, int heads, int head_
 /* The two constants of isc_attention_f16_stream: a workgroup owns `query_block` queries of one (image, head) and walks
  * the keys in chunks of `key_chunk` (a multiple of 32) -- the sequence lengths at which its code paths change. */
 int isc_attention_stream_geometry(int* query_block, int* key_chunk);
+
+/* CAUSAL attention for short sequences (the CLIP text tower): query i sees keys 0 .. i.  Operands, layouts, alignment and
+ * argument order of isc_attention_f16, and its arithmetic (exact 1/8 scaling of the query, the exponent one fma feeding
+ * exp2, probabilities rounded to fp16 in registers, float32 statistics).  One workgroup per (sequence, head), one wave
+ * per block of 16 queries; the wave of block qb computes key blocks 0 .. qb only.  head_dim == 64 and 1 <= T <= 128,
+ * else ISC_ERR_UNSUPPORTED.  No workspace, no host synchronisation, capturable. */
+int isc_attention_f16_causal(const void* qkv, int B, int T, int heads, int head_dim, void* out, int packed, void* stream);
+
+/* The residual stream of a text tower: tokens[b * T + t] = table[ids[b * T + t]] + pos[t] -- one float32 addition per
+ * element.  ids int64 [B, T]; table float32 [vocab, D]; pos float32 [>= T, D]; tokens float32 [B * T, D]; D % 4 == 0,
+ * table / pos / tokens 16-byte aligned, ids 8-byte aligned.  An id outside [0, vocab) never reaches the table: its row is
+ * written as zeros, and when `bad_count` (a device int32, may be NULL; the caller zeroes it) is given the number of such
+ * ids is added to it. */
+int isc_text_embed(const int64_t* ids, int B, int T, int vocab, int D, const float* table, const float* pos,
+                   float* tokens, int32_t* bad_count, void* stream);
+
+/* The pooling head of a text tower: for every sequence b the row tokens[b * T + t*], t* = the first t with
+ * ids[b][t] == eos_id -- or, when eos_id < 0 or no id equals it, the first t at which ids[b] takes its maximum --, goes
+ * through LayerNorm as isc_layernorm computes it (biased variance, two passes, float32 statistics) into row b of `out`
+ * [B, D]: float32, fp16 row-major, or fp16 packed (out_packed != 0, D % 64 == 0).  tokens float32 [B * T, D], ids int64
+ * [B, T].  The limits of isc_layernorm: D % 4 == 0, D <= 2048, 16-byte aligned pointers (ids: 8). */
+int isc_text_pool_layernorm(const float* tokens, const int64_t* ids, int B, int T, int D, int64_t eos_id,
+                            const float* gamma, const float* beta, float eps, void* out, int out_dtype, int out_packed,
+                            void* stream);
 
 /* non-overlapping patches of an NCHW float32 image batch as fp16 GEMM rows (row-major or packed):
  * patches[(b, ph, pw)][c * P * P + r * P + s] = x[b][c][ph * P + r][pw * P + s]   (torch Conv2d(kernel=stride=P) weight
