@@ -4,6 +4,7 @@ Public surface (same names as the reference where the reference has them):
 
 * `ImageBatch`, `EmbeddingBatch`                 -- reference src/imagescry/data.py:29-144
 * `resize`, `normalize_per_channel`, `to_4d`     -- reference src/imagescry/image/transforms.py
+* `resize_antialias`, `resize_center_crop`       -- the checkpoints' own preprocessing: antialiased bicubic + centre crop (new)
 * `EmbeddingModule`, `EfficientNetEmbedder`,
   `ResNet50Embedder`, `ViTB16Embedder`,
   `DINOv2Embedder`, `CLIPEmbedder`               -- reference src/imagescry/models/embedding.py:27-183
@@ -32,7 +33,7 @@ from imagescry_amd.embedding import (
 )
 from imagescry_amd.pipelines import EmbeddingPCAPipeline, EmbedSearchPipeline, SearchResult
 from imagescry_amd.search import EmbeddingBank, RangeResult, RowFilter, SearchHandle, shard_bounds
-from imagescry_amd.transforms import normalize_per_channel, resize, to_4d
+from imagescry_amd.transforms import normalize_per_channel, resize, resize_antialias, resize_center_crop, to_4d
 
 __all__ = [
     "CLIPEmbedder",
@@ -58,6 +59,8 @@ __all__ = [
     "SimilarShapeBatcher",
     "normalize_per_channel",
     "resize",
+    "resize_antialias",
+    "resize_center_crop",
     "shard_bounds",
     "to_4d",
 ]

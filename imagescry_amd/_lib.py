@@ -70,6 +70,14 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
          c_void_p],
     ),
     "isc_resize_bilinear": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "isc_resize_aa_workspace_bytes": (
+        c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]
+    ),
+    "isc_resize_aa": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+         c_int, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
     "isc_l2norm_channels": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "isc_bank_packed_bytes": (c_int, [c_int, c_int64, c_int, POINTER(c_size_t)]),
     "isc_bank_permutation": (c_int, [c_int64, POINTER(c_int64), POINTER(c_int64)]),

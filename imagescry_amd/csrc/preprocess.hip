@@ -2,6 +2,7 @@
 // All three are HBM-bound byte/float streams; they are written for coalesced 16-byte lanes,
 // not for the matrix cores.  Reference arithmetic: src/imagescry/image/transforms.py:58-126 and
 // src/imagescry/models/embedding.py:74.
+#include "aa_filter.h"
 #include "isc_common.h"
 
 namespace {
@@ -561,6 +562,374 @@ extern "C" int isc_l2norm_channels(const float* x, int B, int E, int S, float ep
         if (B > 65535) return ISC_ERR_UNSUPPORTED;
         hipLaunchKernelGGL(k_l2norm_spatial, dim3(isc_ceil_div(S, 64), B), dim3(256), 0, isc_stream(stream), x, E, S,
                            eps, y);
+    }
+    return isc_launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// isc_resize_aa: antialiased bicubic resize (the filter of aa_filter.h with each axis' own input size) of the crop
+// rectangle only, the quantisation and the per-channel normalisation fused into the store.
+//
+// Two launches.  k_resize_aa_tables writes, per output row and column of the CROP, the first tap, the tap count and the
+// normalised weights (a thread per index; the index is the absolute one in the resized image, so a weight does not
+// know the crop).  k_resize_aa then gives a workgroup `band` output rows x `tw` output columns of one plane.  The input
+// rows of the band's vertical support pass through LDS 64 at a time:
+//   1  staging: a wave copies a row's segment (the tile's horizontal support, nothing else) as it is -- uint8 rows as
+//      the row's own aligned 4-byte words, the ragged first and last one put together byte by byte; four rows' loads are
+//      issued before the first is stored;
+//   2  horizontal pass, lane = INPUT ROW, wave = output column (four columns in flight): the taps and weights of a
+//      column are the same for every lane, so they are scalar loads from the table, and the lanes read the same
+//      offset of 64 different lines, whose pitch is an odd number of words: no two on one bank at any scale.  Taps in
+//      ASCENDING order, one fmaf each from 0, into line [row][column] of LDS (pitch tw + 1);
+//   3  after the last chunk a wave per output row combines the lines vertically, taps ASCENDING, one fmaf each from 0,
+//      the weights scalar loads again, and stores tw consecutive floats per instruction.
+// (Lane = output column in the horizontal pass, the obvious map, makes lanes read words `scale` apart: at 3000 x 2000
+// -> 224 that ran 1.9 ms against this form's time in DESIGN.md, bound by LDS bank conflicts.)
+// The order of the two sums is torch's (the horizontal pass first), and a pixel's bits depend on its own taps and
+// weights only: not on the crop, the plane, or the band and tile it falls in.
+// The host picks tw in {64, 32, 16, 8} and band <= 32 so that the lines fit in LDS at the call's scale.
+namespace {
+
+constexpr int kAaThreads = 256;
+constexpr int kAaWaves = kAaThreads / ISC_WAVE;
+constexpr int kAaInFlight = 8;               // rows whose loads a wave issues before it stores the first
+constexpr int kAaTapBlock = 8;               // taps are taken in whole blocks: the tables pad a row with zero weights
+constexpr int kAaPre = 2;                    // 4-byte pieces (floats: pixels) of a row a lane holds meanwhile
+constexpr float kAaMaxScale = 64.f;          // downscale factor per axis: at most 258 taps
+constexpr int kAaLdsTarget = 48 * 1024;      // three workgroups per CU
+constexpr int kAaLdsLimit = 64 * 1024;
+constexpr int kAaMaxPlanesPerLaunch = 65535;
+constexpr size_t kAaMaxBlocks = (size_t)1 << 23;  // tiles of one plane; a launch stays below 2^32 threads
+
+struct AaArgs {
+    int H1, W1, Hc, Wc, C;
+    int taps_y, taps_x;      // table pitch = the most taps an output of that axis can have
+    int band, tw, tiles_x;   // output rows and columns of a workgroup; column tiles per band
+    int chunk;               // input rows filtered at a time, one a lane: 64, fewer where 64 staged rows do not fit
+    int rows_cap, span_cap;  // filtered lines, and staged pixels per row, the launch was sized for
+    int hb, sp;              // pitch of a filtered line (floats) and of a staged row (input elements)
+    int stage_offset;        // bytes from the start of LDS to the staged rows
+    int quantize;
+    const int* meta;         // lo_y[Hc], n_y[Hc], lo_x[Wc], n_x[Wc]
+    const float* wy;         // [Hc][taps_y]
+    const float* wx;         // [Wc][taps_x]
+    const float* mean;
+    const float* stdev;
+};
+
+// the most taps AaTaps gives an output at this scale: the window is 4 max(s, 1) wide, plus its two roundings; whole blocks
+inline int aa_tap_bound(float scale) {
+    return isc_ceil_div((int)(4.f * fmaxf(scale, 1.f)) + 2, kAaTapBlock) * kAaTapBlock;
+}
+
+__global__ __launch_bounds__(256) void k_resize_aa_tables(int H1, int top, int Hc, float scale_h, int taps_y, int W1,
+                                                          int left, int Wc, float scale_w, int taps_x,
+                                                          int* __restrict__ meta, float* __restrict__ wy,
+                                                          float* __restrict__ wx) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (unsigned)Hc + (unsigned)Wc) return;
+    const bool col = i >= (unsigned)Hc;
+    const int idx = col ? (int)(i - (unsigned)Hc) : (int)i;
+    const int pitch = col ? taps_x : taps_y;
+    const AaTaps t(col ? left + idx : top + idx, col ? scale_w : scale_h, col ? W1 : H1);
+    const int n = min(t.n, pitch);
+    int* lo = meta + (col ? 2 * (size_t)Hc : 0);
+    lo[idx] = t.lo;
+    lo[(size_t)(col ? Wc : Hc) + idx] = n;
+    float* w = (col ? wx : wy) + (size_t)idx * pitch;
+    for (int j = 0; j < n; ++j) w[j] = t.weight(j);
+    // the tap loops run in whole blocks: a zero weight leaves a sum as it is (fmaf(0, finite, acc) == acc)
+    for (int j = n; j < (n + kAaTapBlock - 1) / kAaTapBlock * kAaTapBlock; ++j) w[j] = 0.f;
+}
+
+// bytes [off, total) from the 4-byte aligned `pa`, four at q: the word itself, or its bytes inside the segment
+__device__ __forceinline__ unsigned aa_load_piece(const uint8_t* pa, int q, int off, int total) {
+    if (q >= off && q + 4 <= total) return *reinterpret_cast<const unsigned*>(pa + q);
+    // four independent loads from addresses clamped into the segment (a guarded load each would wait for the one before)
+    unsigned w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const unsigned v = pa[min(max(q + j, off), total - 1)];
+        w |= (q + j >= off && q + j < total ? v : 0u) << (8 * j);
+    }
+    return w;
+}
+
+// where a row's first pixel sits in its staged line: uint8 lines start at the row's 4-byte boundary
+__device__ __forceinline__ int aa_line_offset(const uint8_t* p) { return (int)(reinterpret_cast<uintptr_t>(p) & 3u); }
+__device__ __forceinline__ int aa_line_offset(const float*) { return 0; }
+
+// One wave copies `len` pixels of rows wave, wave + 4, ... < nrows (W1 apart from `first`) to their lines.
+__device__ __forceinline__ void aa_stage_rows(const uint8_t* first, int W1, int nrows, int len, uint8_t* stage, int sp,
+                                              int wave, int lane) {
+    for (int r = wave; r < nrows; r += kAaWaves * kAaInFlight) {
+        unsigned pre[kAaInFlight][kAaPre];
+#pragma unroll
+        for (int i = 0; i < kAaInFlight; ++i) {
+            const int rr = r + kAaWaves * i;
+            if (rr >= nrows) break;
+            const uint8_t* p = first + (size_t)rr * W1;
+            const int off = aa_line_offset(p), total = off + len;
+#pragma unroll
+            for (int j = 0; j < kAaPre; ++j) {
+                const int q = 4 * (lane + ISC_WAVE * j);
+                pre[i][j] = q < total ? aa_load_piece(p - off, q, off, total) : 0u;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kAaInFlight; ++i) {
+            const int rr = r + kAaWaves * i;
+            if (rr >= nrows) break;
+            const uint8_t* p = first + (size_t)rr * W1;
+            const int off = aa_line_offset(p), total = off + len;
+            uint8_t* line = stage + rr * sp;  // sp % 4 == 0
+#pragma unroll
+            for (int j = 0; j < kAaPre; ++j) {
+                const int q = 4 * (lane + ISC_WAVE * j);
+                if (q < total) *reinterpret_cast<unsigned*>(line + q) = pre[i][j];
+            }
+            for (int q = 4 * (lane + ISC_WAVE * kAaPre); q < total; q += 4 * ISC_WAVE)
+                *reinterpret_cast<unsigned*>(line + q) = aa_load_piece(p - off, q, off, total);
+            if (lane < kAaTapBlock - 1) line[((total + 3) & ~3) + lane] = 0;  // what the last block's zero weights meet
+        }
+    }
+}
+
+__device__ __forceinline__ void aa_stage_rows(const float* first, int W1, int nrows, int len, float* stage, int sp,
+                                              int wave, int lane) {
+    for (int r = wave; r < nrows; r += kAaWaves * kAaInFlight) {
+        float pre[kAaInFlight][kAaPre];
+#pragma unroll
+        for (int i = 0; i < kAaInFlight; ++i) {
+            const int rr = r + kAaWaves * i;
+            if (rr >= nrows) break;
+            const float* p = first + (size_t)rr * W1;
+#pragma unroll
+            for (int j = 0; j < kAaPre; ++j) {
+                const int q = lane + ISC_WAVE * j;
+                pre[i][j] = q < len ? p[q] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kAaInFlight; ++i) {
+            const int rr = r + kAaWaves * i;
+            if (rr >= nrows) break;
+            const float* p = first + (size_t)rr * W1;
+            float* line = stage + rr * sp;
+#pragma unroll
+            for (int j = 0; j < kAaPre; ++j) {
+                const int q = lane + ISC_WAVE * j;
+                if (q < len) line[q] = pre[i][j];
+            }
+            for (int q = lane + ISC_WAVE * kAaPre; q < len; q += ISC_WAVE) line[q] = p[q];
+            if (lane < kAaTapBlock - 1) line[len + lane] = 0.f;  // what the last block's zero weights meet: finite
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kAaThreads) void k_resize_aa(const T* __restrict__ x, AaArgs a, size_t plane0,
+                                                          float* __restrict__ y) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char aa_lds[];
+    const int tid = threadIdx.x, lane = tid & (ISC_WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid / ISC_WAVE);  // uniform: the weights are scalar loads
+    const int tile = blockIdx.x % a.tiles_x, bandi = blockIdx.x / a.tiles_x;
+    const size_t plane = plane0 + blockIdx.z;
+    const int c0 = tile * a.tw, i0 = bandi * a.band;
+    const int ncol = min(a.tw, a.Wc - c0), nrow = min(a.band, a.Hc - i0);
+    const int* lo_y = a.meta;
+    const int* n_y = lo_y + a.Hc;
+    const int* lo_x = n_y + a.Hc;
+    const int* n_x = lo_x + a.Wc;
+    float* hbuf = reinterpret_cast<float*>(aa_lds);          // [rows_cap][hb]
+    T* stage = reinterpret_cast<T*>(aa_lds + a.stage_offset);  // [chunk][sp]
+
+    // the input rows and columns this tile reads (first taps and ends are non-decreasing along an axis)
+    const int rbase = lo_y[i0];
+    const int R = min(lo_y[i0 + nrow - 1] + n_y[i0 + nrow - 1] - rbase, a.rows_cap);
+    const int xlo = lo_x[c0];
+    const int len = min(lo_x[c0 + ncol - 1] + n_x[c0 + ncol - 1] - xlo, a.span_cap);
+
+    const T* xp = x + plane * ((size_t)a.H1 * a.W1) + (size_t)rbase * a.W1 + xlo;
+    for (int r0 = 0; r0 < R; r0 += a.chunk) {
+        const int nrows = min(a.chunk, R - r0);
+        const T* first = xp + (size_t)r0 * a.W1;
+        aa_stage_rows(first, a.W1, nrows, len, stage, a.sp, wave, lane);
+        __syncthreads();
+        // lanes past the chunk's rows read a line of an earlier chunk, or unwritten LDS, and store nothing
+        const T* line = stage + (lane < a.chunk ? lane : 0) * a.sp +
+                        (lane < nrows ? aa_line_offset(first + (size_t)lane * a.W1) : 0);
+        for (int c = wave; c < ncol; c += kAaWaves) {
+            const int lo = lo_x[c0 + c] - xlo;
+            const int n = min(n_x[c0 + c], len - lo);
+            const float* w = a.wx + (size_t)(c0 + c) * a.taps_x;
+            const T* px = line + lo;
+            float acc = 0.f;
+            for (int b = 0; b < n; b += kAaTapBlock) {
+#pragma unroll
+                for (int j = 0; j < kAaTapBlock; ++j) acc = fmaf(w[b + j], (float)px[b + j], acc);
+            }
+            if (lane < nrows) hbuf[(r0 + lane) * a.hb + c] = acc;
+        }
+        __syncthreads();
+    }
+
+    // the lines the last block's zero weights meet
+    for (int e = tid; e < (kAaTapBlock - 1) * a.hb; e += kAaThreads) hbuf[R * a.hb + e] = 0.f;
+    __syncthreads();
+
+    float mu = 0.f, sd = 1.f;
+    if (a.mean) {
+        const int c = (int)(plane % (size_t)a.C);
+        mu = a.mean[c];
+        sd = a.stdev[c];
+    }
+    for (int i = wave; i < nrow; i += kAaWaves) {
+        const int gi = i0 + i;
+        const int lo = lo_y[gi] - rbase;
+        const int n = min(n_y[gi], R - lo);
+        if (lane >= ncol) continue;
+        const float* wrow = a.wy + (size_t)gi * a.taps_y;
+        const float* h = hbuf + lo * a.hb + lane;
+        float v = 0.f;
+        for (int k = 0; k < n; k += kAaTapBlock) {
+#pragma unroll
+            for (int j = 0; j < kAaTapBlock; ++j) v = fmaf(wrow[k + j], h[(k + j) * a.hb], v);
+        }
+        if (a.quantize) v = rintf(fminf(fmaxf(v, 0.f), 255.f));
+        if (a.mean) v = __fdiv_rn(v - mu, sd);
+        y[(plane * a.Hc + gi) * a.Wc + c0 + lane] = v;
+    }
+}
+
+// LDS bytes of a (band, tw) geometry for input elements of `elem` bytes; fills the capacities and pitches it implies
+size_t aa_lds_bytes(AaArgs& a, float scale_h, float scale_w, int band, int tw, int chunk, int elem) {
+    // first taps of outputs k apart differ by at most s k + 1 (+ 1: the float roundings of the centres)
+    const long long rows = (long long)ceilf(scale_h * (float)(band - 1)) + 2 + a.taps_y;
+    const long long span = (long long)ceilf(scale_w * (float)(tw - 1)) + 2 + a.taps_x;
+    a.band = band;
+    a.tw = tw;
+    a.chunk = chunk;
+    a.rows_cap = (int)(rows < a.H1 ? rows : a.H1);
+    a.span_cap = (int)(span < a.W1 ? span : a.W1);
+    a.hb = tw + 1;  // odd: the horizontal pass writes a column of it, a lane a line
+    // a staged row: whole words, an ODD number of them, so that the lines' equal offsets fall on different banks;
+    // a uint8 line starts up to three bytes before the segment
+    // ... and ends with the kAaTapBlock - 1 zeros the last block of taps may reach
+    int words = elem == 1 ? (a.span_cap + 3 + 3) / 4 + kAaTapBlock / 4 : a.span_cap + kAaTapBlock - 1;
+    words |= 1;
+    a.sp = elem == 1 ? 4 * words : words;
+    a.stage_offset = (int)isc_align_up(sizeof(float) * (size_t)(a.rows_cap + kAaTapBlock - 1) * a.hb, 16);
+    return (size_t)a.stage_offset + (size_t)chunk * words * 4;
+}
+
+// The geometry of a call, or ISC_ERR_UNSUPPORTED.  Needs a.H1, a.W1, a.Hc, a.Wc.  Among the geometries that fit, the
+// one with the fewest lane slots of the horizontal pass per output row (64 a chunk of rows, used or not); a narrower tile only
+// where it saves a tenth.
+int aa_plan(AaArgs& a, int H2, int W2, int elem, float& scale_h, float& scale_w, size_t& lds) {
+    if ((size_t)a.H1 * a.W1 > 0x7fffffffu || (size_t)a.Hc * a.Wc > 0x7fffffffu) return ISC_ERR_UNSUPPORTED;
+    scale_h = (float)a.H1 / (float)H2;
+    scale_w = (float)a.W1 / (float)W2;
+    if (scale_h > kAaMaxScale || scale_w > kAaMaxScale) return ISC_ERR_UNSUPPORTED;
+    a.taps_y = aa_tap_bound(scale_h);
+    a.taps_x = aa_tap_bound(scale_w);
+    for (const int limit : {kAaLdsTarget, kAaLdsLimit}) {
+        int best_tw = 0, best_band = 0, best_chunk = 0;
+        float best = 0.f;
+        for (const int tw : {64, 32, 16, 8})
+            for (const int chunk : {64, 32, 16})
+                for (int band = 32; band >= 1; --band) {
+                    if (aa_lds_bytes(a, scale_h, scale_w, band, tw, chunk, elem) > (size_t)limit) continue;
+                    const float cost = (float)(isc_ceil_div(a.rows_cap, chunk) * ISC_WAVE) / (float)band;
+                    if (best_tw == 0 || cost < (tw == best_tw ? best : 0.9f * best))
+                        best_tw = tw, best_band = band, best_chunk = chunk, best = cost;
+                }
+        if (best_tw == 0) continue;
+        lds = aa_lds_bytes(a, scale_h, scale_w, best_band, best_tw, best_chunk, elem);
+        a.tiles_x = isc_ceil_div(a.Wc, best_tw);
+        if ((size_t)a.tiles_x * isc_ceil_div(a.Hc, best_band) > kAaMaxBlocks) return ISC_ERR_UNSUPPORTED;
+        return ISC_OK;
+    }
+    return ISC_ERR_UNSUPPORTED;
+}
+
+struct AaWorkspace {
+    size_t meta, wy, wx, bytes;  // byte offsets
+};
+
+AaWorkspace aa_workspace(const AaArgs& a) {
+    AaWorkspace w;
+    w.meta = 0;
+    w.wy = isc_align_up(sizeof(int) * 2 * ((size_t)a.Hc + a.Wc), 16);
+    w.wx = w.wy + isc_align_up(sizeof(float) * (size_t)a.Hc * a.taps_y, 16);
+    w.bytes = isc_align_up(w.wx + sizeof(float) * (size_t)a.Wc * a.taps_x, 256);
+    return w;
+}
+
+int aa_check_shape(int H1, int W1, int H2, int W2, int top, int left, int Hc, int Wc) {
+    ISC_REQUIRE(H1 > 0 && W1 > 0 && H2 > 0 && W2 > 0 && Hc > 0 && Wc > 0 && top >= 0 && left >= 0);
+    ISC_REQUIRE((long long)top + Hc <= H2 && (long long)left + Wc <= W2);
+    return ISC_OK;
+}
+
+}  // namespace
+
+extern "C" int isc_resize_aa_workspace_bytes(int H1, int W1, int H2, int W2, int top, int left, int Hc, int Wc,
+                                             size_t* bytes) {
+    ISC_REQUIRE(bytes);
+    int st = aa_check_shape(H1, W1, H2, W2, top, left, Hc, Wc);
+    if (st != ISC_OK) return st;
+    AaArgs a = {};
+    a.H1 = H1, a.W1 = W1, a.Hc = Hc, a.Wc = Wc;
+    float sh, sw;
+    size_t lds;
+    st = aa_plan(a, H2, W2, 4, sh, sw, lds);  // the limits are those of float input, the tables the same for both
+    if (st != ISC_OK) return st;
+    *bytes = aa_workspace(a).bytes;
+    return ISC_OK;
+}
+
+extern "C" int isc_resize_aa(const void* x, int dtype, int B, int C, int H1, int W1, int H2, int W2, int top, int left,
+                             int Hc, int Wc, const float* mean, const float* stdev, int quantize, float* y,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    ISC_REQUIRE(x && y && B > 0 && C > 0);
+    ISC_REQUIRE(dtype == ISC_U8 || dtype == ISC_F32);
+    ISC_REQUIRE((mean == nullptr) == (stdev == nullptr));
+    int st = aa_check_shape(H1, W1, H2, W2, top, left, Hc, Wc);
+    if (st != ISC_OK) return st;
+    AaArgs a = {};
+    a.H1 = H1, a.W1 = W1, a.Hc = Hc, a.Wc = Wc, a.C = C;
+    float scale_h, scale_w;
+    size_t lds;
+    st = aa_plan(a, H2, W2, 4, scale_h, scale_w, lds);  // what the workspace query refuses, the call refuses
+    if (st == ISC_OK && dtype == ISC_U8) st = aa_plan(a, H2, W2, 1, scale_h, scale_w, lds);
+    if (st != ISC_OK) return st;
+    if (!isc_aligned(y, 4) || !isc_aligned(mean, 4) || !isc_aligned(stdev, 4) || !isc_aligned(workspace, 16) ||
+        (dtype == ISC_F32 && !isc_aligned(x, 4)))
+        return ISC_ERR_ALIGNMENT;
+    const AaWorkspace w = aa_workspace(a);
+    if (!workspace || workspace_bytes < w.bytes) return ISC_ERR_WORKSPACE;
+    char* ws = static_cast<char*>(workspace);
+    int* meta = reinterpret_cast<int*>(ws + w.meta);
+    float* wy = reinterpret_cast<float*>(ws + w.wy);
+    float* wx = reinterpret_cast<float*>(ws + w.wx);
+    a.meta = meta, a.wy = wy, a.wx = wx, a.mean = mean, a.stdev = stdev, a.quantize = quantize != 0;
+    hipStream_t s = isc_stream(stream);
+    const unsigned entries = (unsigned)Hc + (unsigned)Wc;
+    hipLaunchKernelGGL(k_resize_aa_tables, dim3(isc_ceil_div(entries, 256u)), dim3(256), 0, s, H1, top, Hc, scale_h,
+                       a.taps_y, W1, left, Wc, scale_w, a.taps_x, meta, wy, wx);
+    const size_t planes = (size_t)B * C;
+    const unsigned blocks = (unsigned)((size_t)a.tiles_x * isc_ceil_div(Hc, a.band));
+    size_t per_launch = (((size_t)1 << 24) - 1) / blocks;  // blocks * z * 256 < 2^32
+    if (per_launch > (size_t)kAaMaxPlanesPerLaunch) per_launch = kAaMaxPlanesPerLaunch;
+    for (size_t p0 = 0; p0 < planes; p0 += per_launch) {
+        const unsigned z = (unsigned)(planes - p0 < per_launch ? planes - p0 : per_launch);
+        if (dtype == ISC_U8)
+            hipLaunchKernelGGL(k_resize_aa<uint8_t>, dim3(blocks, 1, z), dim3(kAaThreads), lds, s,
+                               static_cast<const uint8_t*>(x), a, p0, y);
+        else
+            hipLaunchKernelGGL(k_resize_aa<float>, dim3(blocks, 1, z), dim3(kAaThreads), lds, s,
+                               static_cast<const float*>(x), a, p0, y);
     }
     return isc_launch_status();
 }

@@ -1,6 +1,7 @@
 // Patch-token output of the ViT encoder (include/imagescry_hip.h: isc_vit_pos_resample, isc_vit_pos_resample_aa,
 // isc_vit_tokens_out, isc_vit_tokens_out_skip): the position table of an h x w token grid, and the head that turns the residual stream into the channels-first
 // embedding map [B, D, h, w] every other embedder returns.
+#include "aa_filter.h"
 #include "isc_common.h"
 
 namespace {
@@ -56,34 +57,8 @@ __global__ __launch_bounds__(256) void k_vit_pos_resample(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// The ANTIALIASED form (torch _upsample_bicubic2d_aa, align_corners = False): a separable filter whose support grows
-// with the downscaling factor.  Per axis, s = g / h: centre = s (dst + 0.5), support = 2 max(s, 1), taps
-// [max(0, int(centre - support + 0.5)), min(g, int(centre + support + 0.5))), weight of tap j
-// cubic((j - centre + 0.5) / max(s, 1)) with A = -0.5, divided by the sum over the taps that fall inside the table.
-__device__ __forceinline__ float cubic_aa(float x) {
-    constexpr float A = -0.5f;
-    x = fabsf(x);
-    if (x < 1.f) return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
-    if (x < 2.f) return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
-    return 0.f;
-}
-
-struct AaTaps {
-    int lo, n;
-    float centre, inv, total;
-    __device__ __forceinline__ AaTaps(int dst, float scale, int g) {
-        centre = scale * ((float)dst + 0.5f);
-        const float support = 2.f * fmaxf(scale, 1.f);
-        inv = 1.f / fmaxf(scale, 1.f);
-        lo = max((int)(centre - support + 0.5f), 0);
-        n = min((int)(centre + support + 0.5f), g) - lo;
-        total = 0.f;
-        for (int j = 0; j < n; ++j) total += raw(j);
-    }
-    __device__ __forceinline__ float raw(int j) const { return cubic_aa(((float)(j + lo) - centre + 0.5f) * inv); }
-    __device__ __forceinline__ float weight(int j) const { return raw(j) / total; }
-};
-
+// The ANTIALIASED form (torch _upsample_bicubic2d_aa, align_corners = False): the filter of aa_filter.h (cubic_aa, AaTaps)
+// on both axes of the table.
 // One thread per (output row, four channels), rows of the source first (as the separable passes of torch go), runs
 // once per grid: up to g x g taps a thread.
 __global__ __launch_bounds__(256) void k_vit_pos_resample_aa(const float* __restrict__ pos, int g, int h, int w, int D,

@@ -17,7 +17,7 @@ from torch import Tensor
 
 from imagescry_amd import _lib, clip, efficientnet, resnet50, vit
 from imagescry_amd.data import EmbeddingBatch, ImageBatch
-from imagescry_amd.transforms import normalize_per_channel, resize
+from imagescry_amd.transforms import normalize_per_channel, resize, resize_center_crop
 
 __all__ = ["CLIPEmbedder", "DINOv2Embedder", "EfficientNetEmbedder", "EmbeddingModule", "ResNet50Embedder", "ViTB16Embedder", "l2_normalize_channels"]
 
@@ -550,7 +550,52 @@ DINOV2_PRESETS: dict[tuple[str, bool], vit.ViTConfig] = {
 }
 
 
-class DINOv2Embedder(ViTB16Embedder):
+class _CheckpointPreprocess:
+    """The `preprocess="checkpoint"` mode of the embedders that load published checkpoints: the pipeline those were
+    evaluated behind -- shorter side to `resize_size` by antialiased bicubic interpolation, centre crop of `crop_size`,
+    rounding to uint8 levels, fixed per-channel statistics -- as one `resize_center_crop` call.  "Faithful" means the
+    float arithmetic of torch / torchvision's antialiased TENSOR resize with the result rounded to uint8 levels; PIL's
+    own resize rounds to uint8 after each of its two passes with fixed-point weights and can differ from it by one level
+    on some pixels, which is not emulated."""
+
+    def _init_preprocess(self, mode: str, crop_size: int | None, resize_size: int | None, default_crop: int,
+                         default_resize, mean: tuple[float, ...], std: tuple[float, ...]) -> None:
+        if mode not in ("squash", "checkpoint"):
+            raise ValueError(f'preprocess must be "squash" or "checkpoint", got {mode!r}')
+        self.preprocess_mode = mode
+        self.crop_size = self.resize_size = None
+        if mode == "squash":
+            if crop_size is not None or resize_size is not None:
+                raise ValueError('crop_size and resize_size need preprocess="checkpoint"')
+            return
+        for name, v in (("crop_size", crop_size), ("resize_size", resize_size)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v <= 0):
+                raise ValueError(f"{name} must be a positive int, got {v!r}")
+        crop = default_crop if crop_size is None else crop_size
+        size = default_resize(crop) if resize_size is None else resize_size
+        if size < crop:
+            raise ValueError(f"resize_size {size} is smaller than crop_size {crop}: the crop would need padding")
+        # the crop has to be a shape `forward` takes
+        self._token_grid_of(torch.empty((1, 3, crop, crop), dtype=torch.float32, device="meta"))
+        self.crop_size, self.resize_size = crop, size
+        self._checkpoint_stats = (tuple(255.0 * v for v in mean), tuple(255.0 * v for v in std))
+        self._checkpoint_stats_on: dict[torch.device, tuple[Tensor, Tensor]] = {}
+        self.hparams.update(preprocess=mode, crop_size=crop, resize_size=size)
+
+    def _checkpoint_preprocess(self, images: Tensor) -> Tensor:
+        if not isinstance(images, Tensor) or images.dtype != torch.uint8:
+            raise TypeError("images must be a uint8 tensor")
+        if images.ndim != 4 or images.shape[1] != 3:
+            raise ValueError(f"images must have shape [B, 3, H, W], got {tuple(images.shape)}")
+        if images.device not in self._checkpoint_stats_on:
+            self._checkpoint_stats_on[images.device] = tuple(
+                torch.tensor(v, dtype=torch.float32, device=images.device) for v in self._checkpoint_stats)
+        mean, std = self._checkpoint_stats_on[images.device]
+        return resize_center_crop(images, self.resize_size, self.crop_size, channel_means=mean, channel_stds=std,
+                                  quantize=True)
+
+
+class DINOv2Embedder(_CheckpointPreprocess, ViTB16Embedder):
     """DINOv2 ViT-S/B/L with a patch size of 14 -> 384 / 768 / 1024-d embeddings: `ViTB16Embedder` on one of the
     `vit.DINOV2_*` configurations (LayerScale; with `registers` four register tokens, which the patch map leaves out
     like the class token, and the antialiased position resampling of those checkpoints).
@@ -558,9 +603,16 @@ class DINOv2Embedder(ViTB16Embedder):
     `state_dict` takes a `dinov2_vit{s,b,l}14[_reg]` checkpoint under its facebookresearch/dinov2 or timm names, or a
     Hugging Face one through `vit.from_transformers_state_dict`; without it the weights are seeded random ones.  The
     checkpoints' native grid is 37 x 37 (518 pixels); `output="patches", grid="aspect", max_patches=256` turns a square
-    image into a 16 x 16 map.  Preprocessing is this package's (`resize` + `normalize_per_channel`), and a grid other
-    than the native one resamples the position table by its size (`transformers.Dinov2Model`), not with the hub models'
-    `+ 0.1` offset."""
+    image into a 16 x 16 map.  A grid other than the native one resamples the position table by its size
+    (`transformers.Dinov2Model`), not with the hub models' `+ 0.1` offset.
+
+    `preprocess="squash"` (the default) is this package's preprocessing (`resize` to the mode's size without regard to
+    the aspect ratio + batch-statistics `normalize_per_channel`).  `preprocess="checkpoint"` is the published evaluation
+    transform: the shorter side to `resize_size` by antialiased bicubic interpolation, a centre crop of `crop_size`,
+    rounding to uint8 levels and the ImageNet statistics (`vit.IMAGENET_MEAN`, `vit.IMAGENET_STD`, times 255), in one
+    kernel (`resize_center_crop`; what "faithful" means: `_CheckpointPreprocess`).  `crop_size` defaults to
+    `config.image_size` with `grid="fixed"` and to 224 otherwise, `resize_size` to `round(crop_size * 8 / 7)` (the
+    256 / 224 of that transform); the crop must be a shape `forward` takes."""
 
     def __init__(
         self,
@@ -573,6 +625,9 @@ class DINOv2Embedder(ViTB16Embedder):
         output: str = "cls",
         grid: str = "fixed",
         max_patches: int | None = None,
+        preprocess: str = "squash",
+        crop_size: int | None = None,
+        resize_size: int | None = None,
     ) -> None:
         if not isinstance(registers, bool):
             raise TypeError(f"registers must be a bool, got {registers!r}")
@@ -581,9 +636,16 @@ class DINOv2Embedder(ViTB16Embedder):
         super().__init__(config=DINOV2_PRESETS[variant, registers], state_dict=state_dict, seed=seed,
                          max_images_per_pass=max_images_per_pass, output=output, grid=grid, max_patches=max_patches)
         self.hparams.update(variant=variant, registers=registers)
+        self._init_preprocess(preprocess, crop_size, resize_size, self.config.image_size if grid == "fixed" else 224,
+                              lambda crop: round(crop * 8 / 7), vit.IMAGENET_MEAN, vit.IMAGENET_STD)
+
+    def preprocess(self, images: Tensor) -> Tensor:
+        if self.preprocess_mode == "checkpoint":
+            return self._checkpoint_preprocess(images)
+        return super().preprocess(images)
 
 
-class CLIPEmbedder(ViTB16Embedder):
+class CLIPEmbedder(_CheckpointPreprocess, ViTB16Embedder):
     """CLIP: images and texts in one space.  The vision tower is `ViTB16Embedder` on a `clip.PRESETS` configuration
     ("ViT-B/32", "ViT-B/16", "ViT-L/14", "ViT-L/14@336": a LayerNorm in front of the blocks and a bias-free projection
     to E = 512 / 768 dimensions behind the class token) and yields `[B, E, 1, 1]` rows for an `EmbeddingBank`;
@@ -594,11 +656,14 @@ class CLIPEmbedder(ViTB16Embedder):
     "quick_gelu" for OpenAI's, "gelu" for open_clip / LAION ones.  `preset` may also be a `clip.CLIPConfig`.
     `output="patches"` is refused: a projected patch map is not what the checkpoints were trained to align with text.
 
-    `preprocess` is this package's squash-`resize` to `image_size` (or, with `grid="aspect"`, to the aspect grid) and
-    `normalize_per_channel` with CLIP's FIXED statistics (`clip.IMAGE_MEAN`, `clip.IMAGE_STD`, times 255; no eps, no
-    clipping) -- batch statistics would break the alignment with the text side.  The checkpoints' own pipeline differs:
-    it resizes the SHORTER side to `image_size` bicubically and crops the centre square, so it sees no squashed and no
-    border content.  `forward` takes any float32 input a caller preprocessed themselves."""
+    `preprocess="squash"` (the default) is this package's squash-`resize` to `image_size` (or, with `grid="aspect"`, to
+    the aspect grid) and `normalize_per_channel` with CLIP's FIXED statistics (`clip.IMAGE_MEAN`, `clip.IMAGE_STD`,
+    times 255; no eps, no clipping) -- batch statistics would break the alignment with the text side.
+    `preprocess="checkpoint"` is the checkpoints' own pipeline: the SHORTER side to `resize_size` by antialiased bicubic
+    interpolation, the centre square of `crop_size`, rounding to uint8 levels and the same statistics, in one kernel
+    (`resize_center_crop`; what "faithful" means: `_CheckpointPreprocess`), so the tower sees no squashed and no border
+    content.  `crop_size` defaults to `image_size` and `resize_size` to `crop_size`; the crop must be a shape `forward`
+    takes.  `forward` takes any float32 input a caller preprocessed themselves."""
 
     def __init__(
         self,
@@ -611,6 +676,9 @@ class CLIPEmbedder(ViTB16Embedder):
         output: str = "cls",
         grid: str = "fixed",
         max_patches: int | None = None,
+        preprocess: str = "squash",
+        crop_size: int | None = None,
+        resize_size: int | None = None,
     ) -> None:
         if isinstance(preset, clip.CLIPConfig):
             cfg = preset
@@ -631,12 +699,16 @@ class CLIPEmbedder(ViTB16Embedder):
         if isinstance(preset, str):
             self.hparams.update(preset=preset)
         self._stats: dict[torch.device, tuple[Tensor, Tensor]] = {}
+        self._init_preprocess(preprocess, crop_size, resize_size, self.config.image_size, lambda crop: crop,
+                              clip.IMAGE_MEAN, clip.IMAGE_STD)
 
     def _move(self, device: torch.device) -> None:
         super()._move(device)
         self._text = self._text.to(device)
 
     def preprocess(self, images: Tensor) -> Tensor:
+        if self.preprocess_mode == "checkpoint":
+            return self._checkpoint_preprocess(images)
         images = self._resized(images)
         if images.ndim != 4 or images.shape[1] != 3:
             raise ValueError(f"images must have shape [B, 3, H, W], got {tuple(images.shape)}")

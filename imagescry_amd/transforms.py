@@ -1,9 +1,13 @@
-"""Image transforms on MI355X: bilinear resize and batch-statistics normalisation.
+"""Image transforms on MI355X: bilinear resize, antialiased bicubic resize + crop, and per-channel normalisation.
 
 Same names, arguments and error behaviour as the reference module
 (src/imagescry/image/transforms.py:16-197); the arithmetic runs in the HIP kernels of
 `csrc/preprocess.hip` through the C ABI (`isc_channel_stats`, `isc_normalize_clip`,
 `isc_resize_bilinear`).  Inputs must live on a HIP device -- there is no CPU path.
+
+`resize_antialias` and `resize_center_crop` are not the reference's: they are the preprocessing the published ViT
+checkpoints were evaluated behind (torchvision's `Resize(size, BICUBIC, antialias=True)` + `CenterCrop` on a tensor,
+rounded to uint8 levels, then `Normalize`), in one kernel (`isc_resize_aa`).
 """
 
 from __future__ import annotations
@@ -16,7 +20,7 @@ from torch import Tensor
 
 from imagescry_amd import _lib
 
-__all__ = ["normalize_per_channel", "resize", "to_4d"]
+__all__ = ["center_crop_geometry", "normalize_per_channel", "resize", "resize_antialias", "resize_center_crop", "to_4d"]
 
 SideRef = Literal["height", "width", "long", "short"]
 
@@ -171,3 +175,111 @@ def normalize_per_channel(
         )
     _lib.check(st, "isc_normalize_clip")
     return y
+
+
+def _channel_stat(t: Tensor | None, name: str, c: int, device: torch.device) -> Tensor | None:
+    """A fixed `[1, C, 1, 1]` or `[C]` statistic as a float32 `[C]` device tensor."""
+    if t is None:
+        return None
+    if not isinstance(t, Tensor) or not t.dtype.is_floating_point:
+        raise TypeError(f"{name} must be a floating point tensor")
+    if tuple(t.shape) not in ((c,), (1, c, 1, 1)):
+        raise ValueError(f"{name} must have shape [{c}] or [1, {c}, 1, 1], got {tuple(t.shape)}")
+    return t.to(device=device, dtype=torch.float32).reshape(-1).contiguous()
+
+
+def resize_antialias(
+    image_tensor: Tensor,
+    output_size: tuple[int, int],
+    *,
+    crop: tuple[int, int, int, int] | None = None,
+    channel_means: Tensor | None = None,
+    channel_stds: Tensor | None = None,
+    quantize: bool = False,
+) -> Tensor:
+    """Antialiased bicubic resize to `output_size = (H2, W2)` as float32: the arithmetic of
+    `F.interpolate(x.float(), output_size, mode="bicubic", antialias=True, align_corners=False)`.
+
+    `crop = (top, left, height, width)` returns that rectangle of the resized image, and only it is computed (bit for
+    bit the slice of the full result).  `quantize` rounds to uint8 levels, `rint(clamp(v, 0, 255))`, as a pipeline that
+    resizes to a uint8 image does.  `channel_means` / `channel_stds` (`[C]` or `[1, C, 1, 1]` floats in the units of the
+    input, both or neither) then give `(v - mean_c) / std_c`, bit for bit `normalize_per_channel(..., eps=0.0)` of the
+    unnormalised result.  Input handling as `resize`."""
+    if not isinstance(image_tensor, Tensor):
+        raise TypeError(f"image_tensor must be a torch.Tensor, got {type(image_tensor).__name__}")
+    if image_tensor.ndim < 2 or image_tensor.ndim > 4:
+        raise ValueError(f"Invalid image tensor shape: {image_tensor.shape}")
+    squeeze = 4 - image_tensor.ndim
+    x = _kernel_input(to_4d(image_tensor), "image_tensor")
+    b, c, h1, w1 = x.shape
+    h2, w2 = (int(v) for v in output_size)
+    if h2 <= 0 or w2 <= 0:
+        raise ValueError(f"Input and output sizes should be greater than 0, got output ({h2}, {w2})")
+    top, left, hc, wc = (0, 0, h2, w2) if crop is None else (int(v) for v in crop)
+    if top < 0 or left < 0 or hc <= 0 or wc <= 0 or top + hc > h2 or left + wc > w2:
+        raise ValueError(f"crop {(top, left, hc, wc)} does not lie inside the resized image ({h2}, {w2})")
+    if (channel_means is None) != (channel_stds is None):
+        raise ValueError("channel_means and channel_stds go together: give both or neither")
+    mean = _channel_stat(channel_means, "channel_means", c, x.device)
+    std = _channel_stat(channel_stds, "channel_stds", c, x.device)
+    y = torch.empty((b, c, hc, wc), dtype=torch.float32, device=x.device)
+    if b * c > 0:
+        if h1 <= 0 or w1 <= 0:
+            raise ValueError(f"Input and output sizes should be greater than 0, got input ({h1}, {w1})")
+        lib = _lib.load()
+        need = _lib.c_size_t()
+        _lib.check(lib.isc_resize_aa_workspace_bytes(h1, w1, h2, w2, top, left, hc, wc, need),
+                   "isc_resize_aa_workspace_bytes")
+        ws = torch.empty(need.value, dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            st = lib.isc_resize_aa(
+                x.data_ptr(), _lib.dtype_code(x.dtype), b, c, h1, w1, h2, w2, top, left, hc, wc, _lib.ptr(mean),
+                _lib.ptr(std), int(bool(quantize)), y.data_ptr(), ws.data_ptr(), need.value, _lib.stream_handle(x.device),
+            )
+        _lib.check(st, "isc_resize_aa")
+    for _ in range(squeeze):
+        y = y.squeeze(0)
+    return y
+
+
+def center_crop_geometry(height: int, width: int, size: int,
+                         crop_size: int | tuple[int, int] | None = None) -> tuple[tuple[int, int], tuple[int, int, int, int]]:
+    """`((H2, W2), (top, left, Hc, Wc))` of torchvision's `Resize(size)` + `CenterCrop(crop_size)` on a `height` x
+    `width` image: the shorter side becomes `size` and the longer `int(size * long / short)`; the crop offsets are
+    `int(round((H2 - Hc) / 2.0))` (round half to even, so margins of 1, 3 and 5 pixels start at 0, 2 and 2).
+    `crop_size` defaults to `size`; a crop larger than the resized image raises ValueError (no padding)."""
+    if height <= 0 or width <= 0 or size <= 0:
+        raise ValueError(f"sizes must be positive, got image ({height}, {width}) and size {size}")
+    if height <= width:
+        h2, w2 = size, int(size * width / height)
+    else:
+        h2, w2 = int(size * height / width), size
+    if crop_size is None:
+        crop_size = size
+    hc, wc = (crop_size, crop_size) if isinstance(crop_size, int) else (int(v) for v in crop_size)
+    if hc <= 0 or wc <= 0:
+        raise ValueError(f"crop_size must be positive, got ({hc}, {wc})")
+    if hc > h2 or wc > w2:
+        raise ValueError(f"crop ({hc}, {wc}) is larger than the resized image ({h2}, {w2}); there is no padding")
+    return (h2, w2), (int(round((h2 - hc) / 2.0)), int(round((w2 - wc) / 2.0)), hc, wc)
+
+
+def resize_center_crop(
+    image_tensor: Tensor,
+    size: int,
+    crop_size: int | tuple[int, int] | None = None,
+    *,
+    channel_means: Tensor | None = None,
+    channel_stds: Tensor | None = None,
+    quantize: bool = False,
+) -> Tensor:
+    """`resize_antialias` with the geometry of `center_crop_geometry`: shorter side to `size`, centre crop of
+    `crop_size` (default `size`) -- what torchvision's `Resize(size, BICUBIC)` + `CenterCrop(crop_size)` (+
+    `Normalize` with the statistics) compute on a tensor."""
+    if not isinstance(image_tensor, Tensor):
+        raise TypeError(f"image_tensor must be a torch.Tensor, got {type(image_tensor).__name__}")
+    if image_tensor.ndim < 2 or image_tensor.ndim > 4:
+        raise ValueError(f"Invalid image tensor shape: {image_tensor.shape}")
+    output_size, crop = center_crop_geometry(image_tensor.shape[-2], image_tensor.shape[-1], int(size), crop_size)
+    return resize_antialias(image_tensor, output_size, crop=crop, channel_means=channel_means,
+                            channel_stds=channel_stds, quantize=quantize)

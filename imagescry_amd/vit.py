@@ -70,6 +70,9 @@ DINOV2_L14 = ViTConfig(image_size=518, patch_size=14, dim=1024, depth=24, heads=
 DINOV2_S14_REG = replace(DINOV2_S14, registers=4, pos_antialias=True)
 DINOV2_B14_REG = replace(DINOV2_B14, registers=4, pos_antialias=True)
 DINOV2_L14_REG = replace(DINOV2_L14, registers=4, pos_antialias=True)
+# the ImageNet statistics of the DINOv2 evaluation transform (fractions of 255), as `clip.IMAGE_MEAN` / `clip.IMAGE_STD`
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
 MAX_PATCHES = 4096  # the largest token grid an embedder may ask for: 64 x 64 patches, 1024 x 1024 pixels
 ONE_SHOT_TOKENS = 224  # isc_attention_f16 holds a head's keys whole up to here; longer sequences stream them
 PASS_ROWS = 1024 * 197  # token rows of the default configuration's largest pass (1024 images x 197 tokens)
@@ -552,7 +555,8 @@ def forward_tokens(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = N
     return out
 
 
-__all__ = ["ACTIVATIONS", "DINOV2_B14", "DINOV2_B14_REG", "DINOV2_L14", "DINOV2_L14_REG", "DINOV2_S14", "DINOV2_S14_REG", "MAX_PATCHES",
+__all__ = ["ACTIVATIONS", "DINOV2_B14", "DINOV2_B14_REG", "DINOV2_L14", "DINOV2_L14_REG", "DINOV2_S14", "DINOV2_S14_REG", "IMAGENET_MEAN", "IMAGENET_STD",
+           "MAX_PATCHES",
            "VIT_B16", "ViTConfig", "forward_cls", "forward_tokens", "from_transformers_state_dict", "gemm_flops",
            "images_per_pass", "make_state_dict", "pack_rows", "position_table", "prepare", "prepare_block", "prepare_linear",
            "prepare_norm", "run_blocks", "token_grid", "unpack_rows"]

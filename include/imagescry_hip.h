@@ -119,6 +119,29 @@ int isc_normalize_clip_nhwc4(const void* x, int dtype, int B, int C, int H, int 
  *   x [planes,H1,W1] of `dtype` (ISC_U8 or ISC_F32); y float [planes,H2,W2]; planes = B*C. */
 int isc_resize_bilinear(const void* x, int dtype, int planes, int H1, int W1, int H2, int W2, float* y, void* stream);
 
+/* Antialiased bicubic resize of an NCHW batch to H2 x W2, of which only the crop rectangle [top, top + Hc) x
+ * [left, left + Wc) is computed, with the uint8 rounding and the per-channel normalisation of a checkpoint's pipeline
+ * fused into the store.  R = torch.nn.functional.interpolate(x.float(), (H2, W2), mode="bicubic", antialias=True,
+ * align_corners=False): per axis, s = in / out, centre s (i + 0.5), support 2 max(s, 1), taps
+ * [max(0, int(centre - support + 0.5)), min(in, int(centre + support + 0.5))), weight
+ * cubic((j - centre + 0.5) / max(s, 1)) with A = -0.5 divided by the sum over the taps inside the image -- the filter of
+ * isc_vit_pos_resample_aa with each axis' own input size.  Then, with v = R[b, c, top + i, left + j]:
+ *   quantize != 0     v = rintf(min(max(v, 0), 255)) (a pipeline that resizes to a uint8 image; no clamp otherwise)
+ *   mean and stdev    y = (v - mean[c]) / stdev[c], correctly rounded: isc_normalize_clip at eps = 0 without clipping
+ *                     (float [C] each, in the units of x; both or both NULL: y = v)
+ *   x [B,C,H1,W1] of `dtype` (ISC_U8 or ISC_F32), contiguous; y float [B,C,Hc,Wc].
+ * A value is the sum over its rows, ascending, of the sums over its columns, ascending, one fused multiply-add a tap
+ * from 0 (the order of torch's separable passes, horizontal first): its bits depend on its own taps only, not on the
+ * crop rectangle, B, the image's place in the batch or the kernel's tiling.  No input row or column outside the
+ * support of the crop rectangle is read.  The workspace holds the two per-axis tap tables and does not grow with B.
+ * Limits: in / out <= 64 per axis (258 taps; any upscale), H1 * W1 < 2^31, Hc * Wc < 2^31, any B * C
+ * (ISC_ERR_UNSUPPORTED beyond them); a crop rectangle outside H2 x W2 is ISC_ERR_INVALID_ARG.  y, mean, stdev and a
+ * float x are 4-byte aligned, the workspace 16-byte; a uint8 x needs no alignment. */
+int isc_resize_aa_workspace_bytes(int H1, int W1, int H2, int W2, int top, int left, int Hc, int Wc, size_t* bytes);
+int isc_resize_aa(const void* x, int dtype, int B, int C, int H1, int W1, int H2, int W2, int top, int left, int Hc,
+                  int Wc, const float* mean, const float* stdev, int quantize, float* y, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 /* y[b,:,s] = x[b,:,s] / max(||x[b,:,s]||_2, eps) for x float [B,E,S] (S = H*W; channel dimension normalised).
  * Replaces `nn.functional.normalize(x, p=2, dim=1)` in reference src/imagescry/models/embedding.py:74. */
 int isc_l2norm_channels(const float* x, int B, int E, int S, float eps, float* y, void* stream);
