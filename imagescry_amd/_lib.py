@@ -28,6 +28,7 @@ ISC_TOPK_MAX_K = 120
 ISC_TOPK_LARGE_MAX_K = 4096  # isc_cosine_topk_large / isc_cosine_topk_exhaustive_large
 ISC_SEARCH_MAX_D = 8192
 ISC_SEARCH_PASS_QUERIES = 1024  # queries per pass of isc_cosine_topk (the workspace is sized for one pass)
+ISC_FARTHEST_MAX_PICKS = 1 << 20  # isc_bank_farthest
 ISC_ABI_VERSION = 4
 ISC_BUILD_ABLATION = 1
 ISC_GEMM_A_PACKED, ISC_GEMM_W_PACKED, ISC_GEMM_OUT_PACKED, ISC_GEMM_TILE_256, ISC_GEMM_TILE_128 = 1, 2, 4, 8, 16
@@ -319,6 +320,12 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "isc_bank_group_sums": (
         c_int,
         [c_void_p, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+         c_void_p, c_size_t, c_void_p],
+    ),
+    "isc_bank_farthest_workspace_bytes": (c_int, [c_int, c_int64, c_int, POINTER(c_size_t)]),
+    "isc_bank_farthest": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p, c_size_t, c_void_p],
     ),
     "isc_bank_gram_chunk_rows": (c_int, []),

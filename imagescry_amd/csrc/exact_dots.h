@@ -4,7 +4,7 @@
 // forms compute E; each is a fixed sequence of IEEE operations (fma, add, divide, sqrt are deterministic), so two kernels
 // that call the same form return the same bits for the same (query, row).  The query is rounded to the bank type T first.
 //
-//   STAGED form (k_exact, k_exact_collapse, k_lr_sweep, k_row_scores, k_assign_exact): lane l of a wave holds the 16-byte
+//   STAGED form (k_exact, k_exact_collapse, k_lr_sweep, k_row_scores, k_assign_exact, k_farthest_pass): lane l holds the 16-byte
 //   chunk l & 7 of every K step of bank row l >> 3; the queries sit in LDS as float64, zero beyond d.
 //     1. per lane, acc = 0, then acc = fma(q[e], a[e], acc) over the K steps in order and the chunk's elements in order
 //        (isc_row_step; the zero padding contributes fma(0, x, acc));

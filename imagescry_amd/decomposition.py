@@ -279,8 +279,9 @@ class KMeans:
         num_clusters: C >= 1.
         max_iter: most iterations (assignments) `fit` runs; the last one does not move the centroids.
         tol: `fit` stops when an update raises the objective by less than this.
-        init: `"sample"` (C distinct live rows, drawn with a CPU generator seeded by `seed`) or a `[C, D]` tensor that is
-            used as given.
+        init: `"sample"` (C distinct live rows, drawn with a CPU generator seeded by `seed`), `"farthest"` (the rows of
+            `bank.farthest_points(C, mask=...)`: spread out, deterministic, `seed` is ignored) or a `[C, D]` tensor that
+            is used as given.
         seed: seed of the `"sample"` draw.
 
     After `fit`: `cluster_centers` (`[C, D]` float32 on the bank's device), `labels` (int32 `[len]`, -1 for removed or
@@ -297,11 +298,11 @@ class KMeans:
         if not tol >= 0.0:
             raise ValueError(f"tol must be >= 0, got {tol!r}")
         if isinstance(init, str):
-            if init != "sample":
-                raise ValueError(f"init must be 'sample' or a [num_clusters, D] tensor, got {init!r}")
+            if init not in ("sample", "farthest"):
+                raise ValueError(f"init must be 'sample', 'farthest' or a [num_clusters, D] tensor, got {init!r}")
         elif not (isinstance(init, Tensor) and init.dtype.is_floating_point and init.ndim == 2
                   and init.shape[0] == num_clusters):
-            raise ValueError(f"init must be 'sample' or a floating [{num_clusters}, D] tensor")
+            raise ValueError(f"init must be 'sample', 'farthest' or a floating [{num_clusters}, D] tensor")
         self.num_clusters = num_clusters
         self.max_iter = max_iter
         self.tol = float(tol)
@@ -316,12 +317,14 @@ class KMeans:
     def __repr__(self) -> str:
         return f"{type(self).__name__}(num_clusters={self.num_clusters}, num_iter={self.num_iter})"
 
-    def _initial_centers(self, bank, live: Tensor, num_live: int) -> Tensor:
+    def _initial_centers(self, bank, live: Tensor, num_live: int, rf=None) -> Tensor:
         c = self.num_clusters
         if isinstance(self.init, Tensor):
             if self.init.shape[1] != bank.dim:
                 raise ValueError(f"init must have shape [{c}, {bank.dim}], got {tuple(self.init.shape)}")
             return self.init.detach().to(device=bank.device, dtype=torch.float32).clone()
+        if self.init == "farthest":  # (`fit` has checked that C live rows exist: every pick is a row)
+            return bank.rows(bank.farthest_points(c, mask=rf)[0]).float()
         gen = torch.Generator().manual_seed(self.seed)
         pick = torch.randperm(num_live, generator=gen)[:c]  # distinct positions among the live rows
         rows = live.nonzero().squeeze(1).cpu()[pick] + bank.index_base
@@ -341,7 +344,7 @@ class KMeans:
         num_live = int(live.sum())
         if num_live < c:
             raise ValueError(f"{c} clusters need at least {c} live rows, the bank has {num_live}")
-        centers = self._initial_centers(bank, live, num_live)
+        centers = self._initial_centers(bank, live, num_live, rf)
         self.objective = []
         labels = None
         for it in range(self.max_iter):

@@ -1540,6 +1540,72 @@ class EmbeddingBank:
         self._group_sums(order.contiguous(), offsets.contiguous(), sums, counts)
         return sums, counts
 
+    # ------------------------------------------------------------------ farthest-point selection
+    _farthest_ws: Tensor | None = None  # the workspace of `_farthest_rows`, grown on demand like `_assign_ws`
+
+    def _farthest_rows(self, start: Tensor, m: int, mask: RowFilter | None, out_rows: Tensor, out_cover: Tensor,
+                       out_near: Tensor | None) -> None:
+        """`isc_bank_farthest`: `out_rows` (int64 `[m]`, LOCAL rows, -1 past the last candidate) and `out_cover` (float32
+        `[m]`) receive `m > 0` greedy picks after the centres `start` (int64 LOCAL rows on the device, possibly empty);
+        `mask` (None: every live row) says which rows may be picked, the fill bitmap which are live.  `out_near`, unless
+        None, is float32 `[capacity]` in ORIGINAL row order.  On the current stream, no host read.  A device hook."""
+        lib = _lib.load()
+        dev = self.device
+        n = self.capacity
+        code = _lib.dtype_code(self.dtype)
+        need = _lib.c_size_t()
+        _lib.check(lib.isc_bank_farthest_workspace_bytes(code, n, self.dim, need), "isc_bank_farthest_workspace_bytes")
+        if self._farthest_ws is None or self._farthest_ws.numel() < need.value:
+            self._farthest_ws = None
+            self._farthest_ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        ws = self._farthest_ws
+        rm = None if mask is None or mask.packed is self._fill else mask.packed.data_ptr()
+        with torch.cuda.device(dev):
+            st = lib.isc_bank_farthest(
+                self._bank.data_ptr(), code, n, self.dim, start.data_ptr() if start.numel() else None, start.numel(), m,
+                _lib.ptr(self._fill), rm, out_rows.data_ptr(), out_cover.data_ptr(), _lib.ptr(out_near), ws.data_ptr(),
+                ws.numel(), _lib.stream_handle(dev),
+            )
+        _lib.check(st, "isc_bank_farthest")
+
+    def farthest_points(self, m: int, *, start: "Tensor | Sequence[int] | None" = None,
+                        mask: "RowFilter | Tensor | None" = None, return_near: bool = False) -> tuple[Tensor, ...]:
+        """`m` rows that are as unlike each other as greedy farthest-point selection (k-center greedy) finds them: `idx`
+        int64 `[m]` (global rows) and `cover` float32 `[m]`, and with `return_near` also `near` float32 `[len]`.
+
+        `S(c, r)` is the score of stored row c as a query against stored row r (`scores(rows([c]), [r])` bit for bit) and
+        `near(r)` the best `S(c, r)` over the centres so far, -inf with none; "best" is `search`'s order (score
+        descending, NaN below every number, -0.0 equal to +0.0) and a tie keeps the earlier value.  Every live row of
+        `start` (global rows; range-checked on the host like `rows`; may lie outside `mask`), in order, becomes a centre;
+        a removed one is skipped.  Then, `m` times, the pick is the candidate -- a live row `mask` (`RowFilter` or bool
+        `[N]`) allows that is neither picked nor in `start` -- whose `near` is LAST in that order, ties to the lower row;
+        `cover[t]` is its `near` at that moment (the running worst-case similarity of the rows to the selection), and it
+        becomes a centre.  When no candidate is left the remaining entries are `(-inf, -1)`.  Without `start` the first
+        pick is the lowest allowed live row with cover -inf, and the answer to `m` is a prefix of the answer to any
+        larger `m`.  `near` covers all centres, the last pick included, in row order; a removed row reads -inf.
+
+        One float64 pass over the packed bank per centre (`isc_bank_farthest`), on the caller's current stream with no
+        host read past the index check, so the call can be captured.  `m == 0` returns empty `idx` and `cover` without a
+        launch (`near`, if asked for, is then -inf: no centre was scored).  A sharded bank cannot select."""
+        self._refuse_sharded("select farthest points", self._ROWS_ON_ONE_RANK)
+        if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= _lib.ISC_FARTHEST_MAX_PICKS:
+            raise ValueError(f"m must be an int in [0, {_lib.ISC_FARTHEST_MAX_PICKS}], got {m!r}")
+        index = self._local_index(start if start is not None else [], "start")
+        rf = self._as_filter(mask)
+        dev = self.device
+        n = self.num_local_rows
+        near = torch.full((self.capacity,), -math.inf, dtype=torch.float32, device=dev) if return_near else None
+        if m == 0 or n == 0:
+            idx = torch.full((m,), -1, dtype=torch.int64, device=dev)
+            cover = torch.full((m,), -math.inf, dtype=torch.float32, device=dev)
+        else:
+            idx = torch.empty(m, dtype=torch.int64, device=dev)
+            cover = torch.empty(m, dtype=torch.float32, device=dev)
+            self._farthest_rows(index, m, rf, idx, cover, near)
+            if self.index_base:
+                idx = torch.where(idx >= 0, idx + self.index_base, idx)
+        return (idx, cover, near[:n]) if return_near else (idx, cover)
+
     # ------------------------------------------------------------------ PCA on the packed image
     _gram_ws: Tensor | None = None  # the workspace of `_gram_rows`, grown on demand
 

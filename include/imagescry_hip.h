@@ -823,6 +823,32 @@ int isc_bank_group_sums(const void* bank, int dtype, int64_t N, int D, const int
                         const int64_t* offsets, int64_t G, const uint32_t* fill_mask, double* sums, int64_t ld,
                         int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Greedy farthest-point selection (k-center greedy): M rows of the image laid out for N rows that are as unlike each other
+ * as the greedy rule finds them.  S(c, r) = the score of stored row c as a query against stored row r, with the bits of
+ * isc_cosine_scores for that pair; near(r) = the best S(c, r) over the centres c so far, -inf with none -- best in
+ * isc_cosine_topk's order (score descending, NaN below every number, -0.0 equal to +0.0), the earlier value staying on a
+ * tie.  Every live row of start[0 .. S), in order, becomes a centre (a dead one is skipped, duplicates are harmless).  Then,
+ * M times: the pick is the candidate whose near is LAST in that order (lowest score, NaN before every number), ties to the
+ * lower row; out_cover[t] = its near at that moment, out_rows[t] = its ORIGINAL row, and it becomes a centre.  A candidate is
+ * a live row that row_mask allows and that is neither picked nor listed in `start`.  When none is left the remaining
+ * entries are (-inf, -1).  The answer to M is a prefix of the answer to any larger M.
+ *   bank, dtype, N, D   as isc_bank_assign                      start       device int64_t [S] original rows, or NULL (S = 0)
+ *   fill_mask   the bank's fill bitmap: which rows are live (centres and, with row_mask, candidates); NULL: all of [0, N).
+ *               A dead row is never dereferenced
+ *   row_mask    a packed row filter (isc_row_mask_pack): which rows may be picked; NULL: every live row
+ *   out_rows    int64_t [M]        out_cover   float [M]
+ *   out_near    float [N] or NULL: near of every row against ALL centres, the last pick included, in ORIGINAL row order,
+ *               -inf for a dead row (costs one more pass over the bank)
+ * One float64 pass over the bank per centre: 1 + max(S, 1) + M launches in stream order, each pass reducing the per-workgroup
+ * keys of the pass before; no atomics, two calls give the same bits; no host synchronisation (capturable); the workspace's
+ * contents on entry do not matter.  M == 0 returns ISC_OK without a launch; M > 0 needs 0 < N <= 2^31 - 2.
+ * D <= ISC_SEARCH_MAX_D, M <= ISC_FARTHEST_MAX_PICKS.  The workspace depends on N only. */
+#define ISC_FARTHEST_MAX_PICKS (1 << 20)
+int isc_bank_farthest_workspace_bytes(int dtype, int64_t N, int D, size_t* bytes);
+int isc_bank_farthest(const void* bank, int dtype, int64_t N, int D, const int64_t* start, int64_t S, int64_t M,
+                      const uint32_t* fill_mask, const uint32_t* row_mask, int64_t* out_rows, float* out_cover,
+                      float* out_near /* [N] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* PCA on a packed bank.  In both calls the centred row is a_r = float32(b_r) - mean: the stored value widened exactly, then
  * one float32 subtraction; a row is LIVE iff its bit in row_mask is set -- the bank's fill bitmap or a packed row filter
  * (isc_row_mask_pack), NULL: every row of [0, N) -- and a dead row is never dereferenced.  The products run on the f32
