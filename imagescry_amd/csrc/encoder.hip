@@ -1375,7 +1375,7 @@ extern "C" int isc_pool_linear_l2norm(const float* x, int B, int H, int W, int C
                                       int normalize, float eps, float* out, void* stream) {
     ISC_REQUIRE(x && w && out && B > 0 && H > 0 && W > 0 && C > 0 && E > 0);
     if (C % 4 != 0) return ISC_ERR_UNSUPPORTED;
-    if (!isc_aligned(w, 16)) return ISC_ERR_ALIGNMENT;
+    if (!isc_aligned(x, 16) || !isc_aligned(w, 16)) return ISC_ERR_ALIGNMENT;  // both are read 16 bytes at a time
     const size_t lds = (size_t)HEAD_IMG * ((size_t)C + E) * sizeof(float);
     if (lds > 64 * 1024) return ISC_ERR_UNSUPPORTED;  // C + E <= 8192
     hipLaunchKernelGGL(k_pool_linear_l2norm, dim3(isc_ceil_div(B, HEAD_IMG)), dim3(HEAD_THREADS), lds, isc_stream(stream), x,

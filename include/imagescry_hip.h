@@ -354,7 +354,8 @@ int isc_global_avgpool_nhwc(const float* x, int B, int H, int W, int C, float* y
 /* The tail of a pooled encoder in ONE launch: out[b] = linear(mean over (H, W) of x[b]) [/ max(||.||_2, eps) when
  * `normalize`]: global average pool, projection and the `F.normalize(x, p=2, dim=1)` of the reference's predict_step
  * (src/imagescry/models/embedding.py:70-76) for an embedder whose output map is [B, E, 1, 1].  x float NHWC
- * [B, H, W, C], w float [E, C] (16-byte aligned), bias float [E] or NULL, out float [B, E]; C % 4 == 0, C + E <= 8192.
+ * [B, H, W, C] and w float [E, C] (both 16-byte aligned, else ISC_ERR_ALIGNMENT), bias float [E] or NULL, out float
+ * [B, E]; C % 4 == 0, C + E <= 8192.
  * The pool and the normalisation reproduce isc_global_avgpool_nhwc and isc_l2norm_channels bit for bit. */
 int isc_pool_linear_l2norm(const float* x, int B, int H, int W, int C, const float* w, const float* bias, int E,
                            int normalize, float eps, float* out, void* stream);

@@ -6,8 +6,8 @@ The operand the kernel multiplies is `x * gate` (or `x - mean`) formed as ONE fl
 float32 operand on the CPU and take its float64 product with the weights as `want`.  R x R filters go through
 `torch.nn.functional.unfold` of that operand (pure data movement, padding taps stay zero).
 
-Activations.  ReLU is 1-Lipschitz, so the activation is applied to `want` and the bound kept.  For SiLU, GELU and
-sigmoid `want` is the float64 activation of the float64 pre-activation, and the bound is
+Activations (`expected`, shared through tests/conv_reference.py).  ReLU is 1-Lipschitz, so the activation is applied to
+`want` and the bound kept.  For SiLU, GELU and sigmoid `want` is the float64 activation of the float64 pre-activation, and the bound is
 
     1.13 * (pre-activation bound) + 2^-21 * (1 + |value|)
 
@@ -35,12 +35,9 @@ import torch.nn.functional as F
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 import matmul_bound as mb  # noqa: E402
+from conv_reference import ACT_NONE, ACT_RELU, ACT_GELU, ACT_SILU, ACT_SIGMOID, RES_AFTER, _activate, expected  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-ACT_NONE, ACT_RELU, ACT_GELU, ACT_SILU, ACT_SIGMOID, RES_AFTER = 0, 1, 2, 3, 4, 0x100
-ACT_SLACK = 2.0**-21
-ACT_SLOPE = 1.13
 
 # (B, H, W, Cin, Cout, R, stride, pad)
 GATED_CASES = (
@@ -53,31 +50,6 @@ GATED_CASES = (
     (3, 9, 9, 96, 196, 1, 1, 0),  # 128 x 128 tiles: two pixel tiles, the seam inside image 1; 2nd channel tile 68 wide
 )
 WAYS = ("bias", "bias_residual", "silu_residual_after")
-
-
-def _activate(pre: torch.Tensor, act: int) -> torch.Tensor:
-    if act == ACT_RELU:
-        return pre.clamp_min(0.0)
-    if act == ACT_GELU:
-        return F.gelu(pre)  # exact erf form, float64
-    if act == ACT_SILU:
-        return F.silu(pre)
-    if act == ACT_SIGMOID:
-        return torch.sigmoid(pre)
-    return pre
-
-
-def expected(pre: torch.Tensor, pre_bound: torch.Tensor, act: int, residual_after: torch.Tensor | None = None):
-    """(want, bound) of act(pre) [+ residual_after] by the rule of the module docstring."""
-    want = _activate(pre, act)
-    if act in (ACT_NONE, ACT_RELU):
-        assert residual_after is None
-        return want, pre_bound
-    size = want.abs()
-    if residual_after is not None:
-        size = size + residual_after.abs()
-        want = want + residual_after
-    return want, ACT_SLOPE * pre_bound + ACT_SLACK * (1 + size)
 
 
 @functools.lru_cache(maxsize=None)

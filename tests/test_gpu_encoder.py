@@ -41,16 +41,18 @@ def _rel_err(got: torch.Tensor, exp: torch.Tensor) -> float:
         (1, 10, 10, 32, 100, 5, 1, 2),  # Cout not a tile multiple, 5x5
         (2, 13, 12, 64, 24, 1, 1, 0),  # Cout <= 32: the 32-channel tile, eight channels of it past Cout
         (3, 17, 17, 32, 32, 3, 1, 1),  # ... all 32 used, ragged pixel tile
-        # large 1 x 1 layers with short K loops: ragged last pixel tile, 1 / 2 / 4 channel blocks of 256
+        # large 1 x 1 layers with short K loops (half tiles of 128 x 64 throughout, up to 14 per workgroup): ragged last
+        # pixel tile, 2 / 4 / 8 channel tiles
         (8, 130, 130, 64, 256, 1, 1, 0),  # ResNet layer1 expand: two K steps per tile
         (4, 129, 129, 256, 512, 1, 1, 0),
         (2, 200, 200, 32, 1024, 1, 1, 0),  # ONE K step per tile
-        # more tiles than resident workgroups (two per CU): every workgroup walks several tiles, staging the next
-        # tile's first K step under the last one of the current tile -- odd and even K-step counts, all three tile shapes
-        (8, 150, 150, 32, 64, 1, 1, 0),  # 64 x 256 tiles, one K step
+        # more tiles than resident workgroups: every workgroup walks several tiles, staging the next tile's first K step
+        # under the last one of the current tile.  Which kernel each shape runs on 256 CUs is worked out by
+        # tests/conv_paths.py; the full 64 x 256 and 128 x 128 tiles walking are in tests/test_gpu_conv_dma.py
+        (8, 150, 150, 32, 64, 1, 1, 0),  # at most 8 K steps: 1 408 half tiles of 64 x 128 on 768 workgroups, one K step
         (8, 150, 150, 96, 64, 1, 1, 0),  # ... three
-        (8, 150, 150, 64, 24, 1, 1, 0),  # 32 x 256 tiles, two K steps
-        (6, 75, 75, 32, 128, 3, 1, 1),  # 128 x 128 tiles, nine K steps, padding taps
+        (8, 150, 150, 64, 24, 1, 1, 0),  # 32 x 256 tiles, two K steps, 704 tiles on 512 workgroups
+        (6, 75, 75, 32, 128, 3, 1, 1),  # nine K steps, padding taps: 264 tiles are no whole round, so 528 half tiles of 128 x 64
         # long tiles (>= 16 K steps) with a thin last round: whole rounds in one launch, the remainder as half tiles
         (5, 120, 120, 64, 128, 3, 1, 1),  # 563 tiles of 128 x 128 on 512 resident workgroups: 512 + 51 -> 102 halves
         (5, 170, 170, 64, 64, 3, 1, 1),  # 565 tiles of 64 x 256: 512 + 53 -> 106 halves of 64 x 128, ragged last half
@@ -89,10 +91,10 @@ def test_conv2d_nhwc(b, h, w, cin, cout, k, stride, pad, epilogue, device: torch
 @pytest.mark.parametrize(
     "b,h,w,cin,cin2,cout,stride2",
     [
-        (3, 56, 56, 64, 64, 256, 1),  # ResNet-50 layer1.0: conv3 + projection shortcut at one resolution, 64 x 256 ... tiles
+        (3, 56, 56, 64, 64, 256, 1),  # ResNet-50 layer1.0: conv3 + projection shortcut at one resolution, 148 tiles of 128 x 128
         (8, 130, 130, 64, 64, 256, 1),  # more tiles than resident workgroups, ragged last pixel tile
         (2, 28, 28, 128, 256, 512, 2),  # layer2.0: the shortcut reads every second pixel of the 56 x 56 map
-        (1, 9, 7, 32, 96, 36, 3),  # one + three K steps, stride 3, Cout not a tile multiple, odd sizes
+        (1, 9, 7, 32, 96, 36, 3),  # one + three K steps, stride 3, Cout not a tile multiple, odd sizes (the one 64 x 256 case)
     ],
 )
 def test_conv1x1_dual_input(b, h, w, cin, cin2, cout, stride2, device: torch.device) -> None:
@@ -183,24 +185,23 @@ def test_conv2d_stem_mode(b, h, w, cout, k, stride, pad, device: torch.device) -
 @pytest.mark.parametrize(
     "b,h,w,cin,cout,k,stride,pad",
     [
-        (2, 31, 29, 24, 24, 3, 1, 1),  # EfficientNetV2-S stage 1 (6 chunks per tap: K steps straddle taps)
-        (2, 30, 30, 24, 96, 3, 2, 1),  # stage 2 expand
+        (2, 31, 29, 24, 24, 3, 1, 1),  # EfficientNetV2-S stage 1 (6 chunks per tap; the halo-tile kernel, ragged both ways)
+        (2, 30, 30, 24, 96, 3, 2, 1),  # stage 2 expand (packed-K half tiles of 128 x 64)
         (2, 17, 19, 48, 192, 3, 1, 1),  # 48 channels: 12 chunks per tap
         (3, 20, 20, 96, 48, 1, 1, 0),  # Cin % 32 == 0 but Cout = 48: the plain mode, unpadded output
         (3, 20, 20, 48, 64, 1, 1, 0),  # 1 x 1 packed-K: 1.5 K steps, tail zero-padded
         (2, 9, 9, 80, 160, 1, 1, 0),  # EfficientNetV2-M: 80 = 2.5 K steps
         (2, 9, 9, 8, 132, 5, 2, 2),  # 2 chunks per tap, Cout over one 128 tile
         (4, 1, 1, 40, 960, 1, 1, 0),  # squeeze-excitation fc2 from an unpadded squeeze width
-        (8, 150, 150, 24, 24, 3, 1, 1),  # packed-K over more tiles than resident workgroups (32 x 256 tiles)
-        (8, 150, 150, 8, 48, 3, 2, 1),  # ... 64 x 256 tiles would need Cout > 32: 48 -> 64 x 256, stride 2
-        # the halo-tile kernel (conv_halo.hip: Cin <= 24, Cout <= 64, square odd filter, "same" padding): image smaller than
-        # one 16 x 16 tile, ragged tiles in both directions, 5 x 5 and 7 x 7 windows, stride 2 on odd sizes, 1 - 6 chunks per
-        # pixel, Cout of one / two / three / four 16-channel blocks, more tiles than resident workgroups
-        (1, 5, 7, 24, 24, 3, 1, 1),
-        (3, 33, 47, 12, 40, 5, 1, 2),
-        (2, 45, 31, 20, 64, 7, 2, 3),
-        (2, 64, 64, 16, 4, 3, 2, 1),
-        (5, 200, 208, 24, 24, 3, 1, 1),
+        # the halo-tile kernel (conv_halo.hip: Cin <= 24, Cout <= 64, square odd filter, "same" padding, weights + halo
+        # tile within 78 KiB of LDS) takes these two; packed-K tiles walking are in tests/test_gpu_conv_dma.py
+        (8, 150, 150, 24, 24, 3, 1, 1),  # halo<2>: 800 tiles of 16 x 16 on 512 workgroups
+        (8, 150, 150, 8, 48, 3, 2, 1),  # halo<4>: 200 tiles, stride 2
+        (1, 5, 7, 24, 24, 3, 1, 1),  # halo<2>: image smaller than one 16 x 16 tile (the first case of this list runs halo<2> too)
+        (3, 33, 47, 12, 40, 5, 1, 2),  # NOT the halo kernel (98 304 bytes of LDS): packed-K half tiles of 64 x 128, 5 x 5
+        (2, 45, 31, 20, 64, 7, 2, 3),  # NOT the halo kernel (about 280 000 bytes): packed-K half tiles of 64 x 128, 7 x 7, stride 2
+        (2, 64, 64, 16, 4, 3, 2, 1),  # NOT the halo kernel (92 160 bytes): 32 x 256 packed-K tiles, stride 2
+        (5, 200, 208, 24, 24, 3, 1, 1),  # halo<2>: 845 tiles, more than resident workgroups, ragged in one direction
     ],
 )
 @pytest.mark.parametrize("epilogue", ["bias_silu", "bias_silu_then_res"])
