@@ -523,6 +523,9 @@ constexpr int A_TILE_BYTES = TM * 128;  // 32 KiB: one K step of one bank tile
 #ifndef ISC_HM_B1U
 #define ISC_HM_B1U 2  // ... first unit under which the second half's query fragments are fetched
 #endif
+#ifndef ISC_HM_ZERO_C
+#define ISC_HM_ZERO_C 1  // ... a tile's first K step takes the constant zero as C (0: the tile end clears the accumulators)
+#endif
 
 // One workgroup = one query tile x one chunk of consecutive 256-row bank tiles.
 //
@@ -539,7 +542,8 @@ constexpr int A_TILE_BYTES = TM * 128;  // 32 KiB: one K step of one bank tile
 // workgroups stream the same chunk).  The other values exist only in -DISC_ABLATION builds (wrong results by design):
 // 2 = no staging after the prologue, 3 = staging but no MFMAs, 41 / 43 = the query operand ablations, 7 = like 2 without LDS fragment reads, 11 = no
 // half-row-block stagger of the wm = 1 waves, 15 = DMA issued but never waited for, 17 = DMA and MFMAs but no LDS
-// fragment reads.
+// fragment reads, 49 = 12 without the tile end (no masks, thresholds, maxima, ballots: `kt = 0; ++tile` alone), the
+// ceiling of whatever is done to the tile end.
 //
 // RowMask: empty, or the row filter of a masked search (isc_row_mask_pack; search_common.h): the rows it disallows become
 // -inf where the rows past the end do, so they are never a candidate and never count towards a bound.  Or the IscGroups
@@ -560,7 +564,8 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
     typedef typename Mma<T>::Acc Acc;
     constexpr bool MASK = sizeof...(RowMask) > 0 && !I8;
     constexpr bool GROUP = isc_grouped<RowMask...>();  // (MASK as well; its bitmap may then be NULL)
-    static_assert(!I8 || (TNQ == 256 && DBG == 12 && !SAMPLE && sizeof...(RowMask) == 1), "the int8 filter is one kernel");
+    static_assert(!I8 || (TNQ == 256 && (DBG == 12 || DBG == 49) && !SAMPLE && sizeof...(RowMask) == 1),
+                  "the int8 filter is one kernel (49: its ablation-build twin without a tile end)");
     // DBG 20 / 32 / 33 are the REDO instantiations of 0 / 12 / 13 (k_final2's feeder: the whole bank against the fixed
     // thresholds of the listed queries).  They are kernels of their own so that a profile lists them apart from the
     // search's streaming launches; `active` counts the listed query slots -- normally zero, and the launch ends here.
@@ -587,8 +592,12 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
     // fetched under the first units), and the bank fragments run three units ahead through four registers.
     // It is the form of every launch with several query tiles (MODE 12); MODE 48 (ablation builds) = the row-block-major
     // form it replaced (+1.6 %, scripts/ab.sh: ab_hm), which the stamped build (22) and the operand ablations (41, 43) still run.
-    constexpr bool HM = MODE == 12 && TNQ == 256 && !SAMPLE;
-    constexpr bool NOSPLIT_FORM = MODE == 12 || MODE == 22 || MODE == 41 || MODE == 43 || MODE == 48;
+    constexpr bool HM = (MODE == 12 || MODE == 49) && TNQ == 256 && !SAMPLE;
+    // ZERO_C: a tile's first K step takes the constant zero as C and the tile end clears nothing (see the loop).  The int8
+    // instantiation only: there it is -1.4 % per search; the fp16 loop, whose tile is twice as long, measured 0.4 % SLOWER
+    // with it in every one of three interleaved rounds and keeps the loop it had.
+    constexpr bool ZERO_C = HM && I8 && ISC_HM_ZERO_C;
+    constexpr bool NOSPLIT_FORM = MODE == 12 || MODE == 22 || MODE == 41 || MODE == 43 || MODE == 48 || MODE == 49;
     constexpr int ASYM_LO = NOSPLIT_FORM ? ISC_ASYM_MBLO : MODE == 0 ? ISC_ASYM_SPLIT_MBLO : 8;
     constexpr bool ASYM = TNQ == 256 && !SAMPLE && ASYM_LO != 8;
     constexpr int MBLO = ASYM ? ASYM_LO : MB;        // row blocks of a wm = 0 wave
@@ -874,15 +883,19 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
     [[maybe_unused]] i32x4 tile_codes[MBMAX];
     [[maybe_unused]] float tile_ct = 0.f, tile_et = 0.f, tile_nt = 0.f;  // (I8) IscShadowRec of the current tile
     if constexpr (MODE == 22) st_prev = stamp();
-    for (int step = 0; step < total_steps; ++step) {
+    // One K step: the loads a tile's first step issues for its end (`first`), then the step's reads, LDS-DMA and MFMAs.
+    // first_tag: the ZERO_C loop knows at compile time whether the step is the first of its tile (FIRST below); there
+    // `first` must equal it (the loads and the zero-C copy belong to the same step).  Every other form passes false_type
+    // and the run-time `kt == 0`.
+    auto step_body = [&](int step, auto first_tag, bool first) {
         if constexpr (MASK && !SAMPLE) {
-            if (kt == 0 && use_mask) load_mask(MBE_C{}, SUB_C{}, (r0 >> 8) + tile_begin + tile, tile_mask);
+            if (first && use_mask) load_mask(MBE_C{}, SUB_C{}, (r0 >> 8) + tile_begin + tile, tile_mask);
         }
         if constexpr (GROUP && !SAMPLE && !DEFER) {
-            if (kt == 0) load_codes(MBE_C{}, (r0 >> 8) + tile_begin + tile, tile_codes);
+            if (first) load_codes(MBE_C{}, (r0 >> 8) + tile_begin + tile, tile_codes);
         }
         if constexpr (I8) {  // the tile's record: scalar loads like the row filter's words, consumed at the tile's end
-            if (kt == 0) {
+            if (first) {
                 typedef const __attribute__((address_space(4))) float ConstFloat;
                 ConstFloat* src = (ConstFloat*)((row_mask, ...).recs + ((r0 >> 8) + tile_begin + tile));
                 tile_ct = src[1];
@@ -900,6 +913,13 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
             constexpr int MBW = STAGGER ? MBHI : MBLO;
             constexpr int NU = 2 * MBW;
             static_assert(MBW >= 4, "the second half's query fragments are fetched under four units of the first");
+            // ZERO_C (the int8 instantiation): the step exists twice per loop copy.  FIRST = the first K step of a tile, whose first-half units take the
+            // constant zero as their C operand (Mma<T>::part_first) -- every accumulator of the wave is written there, so
+            // nothing of the tile before survives and the tile end clears nothing.  The loop at the end of main_loop
+            // selects the copy with one scalar branch per step; no MFMA sits behind a condition of its own.  (That branch
+            // also holds the tile's loads above: with them under a condition of their own in front of it, the grouped
+            // instantiations spilled 176 B.)
+            constexpr bool FIRST = decltype(first_tag)::value;
             const int sb = step + DB, sa = step + DA;
             const bool do_b = sb < total_steps;
             const bool do_a = sa < total_steps;
@@ -987,27 +1007,38 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
+            // query blocks N0 .. N1 - 1 of unit u
+            auto mfmas = [&](auto uc, auto n0c, auto n1c) {
+                constexpr int u = decltype(uc)::value, m = u % MBW, kk = u / MBW;
+                constexpr int N0 = decltype(n0c)::value, N1 = decltype(n1c)::value;
+                // (named through the lambda's own parameter, so that the branch is discarded unchecked where Mma<T> has no
+                // part_first: only the int8 traits do)
+                using MmaFirst = Mma<std::conditional_t<(u >= 0), T, decltype(uc)>>;
+                if constexpr (kk == 0 && FIRST) MmaFirst::template part_first<N0, N1>(ar[u % RING], b0, acc[m]);
+                else if constexpr (kk == 0) Mma<T>::template part<N0, N1>(ar[u % RING], b0, acc[m]);
+                else Mma<T>::template part<N0, N1>(ar[u % RING], b1, acc[m]);
+            };
+            using N0_C = std::integral_constant<int, 0>;
+            using N2_C = std::integral_constant<int, 2>;
+            using N4_C = std::integral_constant<int, 4>;
             if constexpr (STAGGER) {
                 // type B: [MFMAs 0-1 of unit u] [overhead, wait for unit u + 1] [MFMAs 2-3 of unit u]
                 asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(ar[0]), "+v"(b0[0]), "+v"(b0[1]), "+v"(b0[2]), "+v"(b0[3]) : "i"(RING - 2));
                 __builtin_amdgcn_sched_barrier(0);
                 auto units = [&](auto self, auto uc) {
-                    constexpr int u = decltype(uc)::value, m = u % MBW, kk = u / MBW;
-                    if constexpr (kk == 0) Mma<T>::template part<0, 2>(ar[u % RING], b0, acc[m]);
-                    else Mma<T>::template part<0, 2>(ar[u % RING], b1, acc[m]);
+                    constexpr int u = decltype(uc)::value;
+                    mfmas(uc, N0_C{}, N2_C{});
                     overhead(uc, std::integral_constant<int, u + 1>{});
-                    if constexpr (kk == 0) Mma<T>::template part<2, 4>(ar[u % RING], b0, acc[m]);
-                    else Mma<T>::template part<2, 4>(ar[u % RING], b1, acc[m]);
+                    mfmas(uc, N2_C{}, N4_C{});
                     if constexpr (u + 1 < NU) self(self, std::integral_constant<int, u + 1>{});
                 };
                 units(units, std::integral_constant<int, 0>{});
             } else {
                 // type A: [overhead, wait for unit u] [MFMAs 0-3 of unit u]
                 auto units = [&](auto self, auto uc) {
-                    constexpr int u = decltype(uc)::value, m = u % MBW, kk = u / MBW;
+                    constexpr int u = decltype(uc)::value;
                     overhead(uc, uc);
-                    if constexpr (kk == 0) Mma<T>::template part<0, 4>(ar[u % RING], b0, acc[m]);
-                    else Mma<T>::template part<0, 4>(ar[u % RING], b1, acc[m]);
+                    mfmas(uc, N0_C{}, N4_C{});
                     if constexpr (u + 1 < NU) self(self, std::integral_constant<int, u + 1>{});
                 };
                 units(units, std::integral_constant<int, 0>{});
@@ -1217,9 +1248,13 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
         }
 
         }
+    };  // step_body
 
-        if constexpr (!SAMPLE) {
-        if (++kt == ksteps) {
+    auto finish_tile = [&]() {
+        if constexpr (MODE == 49) {  // ablation: a tile ends without its end
+            kt = 0;
+            ++tile;
+        } else {
             // ---- tile finished: threshold filter.  C layout of the 16x16 MFMA: column (query) = lane & 15,
             // row (bank row) = 4 * (lane >> 4) + register.  Survivors are rare once tau is warm, so the scan of a
             // query block only runs when some lane of the wave holds one (wave-uniform branch).  The comparison is
@@ -1316,16 +1351,20 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
                 }
             }
             }  // !I8
+            // the ZERO_C loop starts a tile from the constant zero (part_first); the other forms accumulate from here
+            if constexpr (!ZERO_C) {
 #pragma unroll
-            for (int m = 0; m < MBE; ++m)
+                for (int m = 0; m < MBE; ++m)
 #pragma unroll
-                for (int n = 0; n < 4; ++n) acc[m][n] = Acc{0, 0, 0, 0};
+                    for (int n = 0; n < 4; ++n) acc[m][n] = Acc{0, 0, 0, 0};
+            }
             ++tile;
         }
-        }
+    };  // finish_tile
 
-        // retire this wave's DMA for step + 1; the barrier then publishes every wave's pieces and guarantees nobody
-        // still reads the slots refilled next iteration
+    // retire this wave's DMA for step + 1; the barrier then publishes every wave's pieces and guarantees nobody
+    // still reads the slots refilled next iteration
+    auto publish = [&](int step) {
         if constexpr (MODE == 22) {
             const unsigned long long tb = stamp();
             retire_for(step + 1);
@@ -1340,6 +1379,34 @@ __global__ __launch_bounds__(NTHREADS) void k_dots_filter(const unsigned char* _
         retire_for(step + 1);
         __builtin_amdgcn_s_barrier();
         }
+    };
+    if constexpr (ZERO_C) {
+        // kt is wave-uniform: one scalar branch per step selects the copy (a tile's first step may also be its last)
+        for (int step = 0; step < total_steps; ++step) {
+            if (kt == 0) step_body(step, std::true_type{}, true);
+            else step_body(step, std::false_type{}, false);
+            if (++kt == ksteps) finish_tile();
+            publish(step);
+        }
+    } else {
+        for (int step = 0; step < total_steps; ++step) {
+            step_body(step, std::false_type{}, kt == 0);
+            if constexpr (!SAMPLE) {
+                if (++kt == ksteps) finish_tile();
+            }
+            publish(step);
+        }
+    }
+    if constexpr (MODE == 49) {
+        // nothing reads the accumulators in this mode: without a use the compiler drops every MFMA (first build of the
+        // mode: 3.83 ms per search, a loop of reads and DMA alone).  nslots is never negative, which it cannot know.
+        Acc s = acc[0][0];
+#pragma unroll
+        for (int m = 0; m < MBE_C::value; ++m)
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+                if (m + n > 0) s += acc[m][n];
+        if (nslots == -49) my_ent[0] = Cand{(float)(s[0] + s[1] + s[2] + s[3]), 0};
     }
     if constexpr (MODE == 22) {
         if (lane == 0) {
@@ -2250,6 +2317,7 @@ void launch_filter(const Level& l, const Plan& p, const Workspace& w, const Filt
         case 41: ISC_LAUNCH_FILTER(41, false); break;
         case 43: ISC_LAUNCH_FILTER(43, false); break;
         case 48: ISC_LAUNCH_FILTER(48, false); break;
+        case 49: ISC_LAUNCH_FILTER(49, false); break;
 #endif
         case 12: ISC_LAUNCH_FILTER(12, false); break;
         default:
@@ -2350,6 +2418,14 @@ int run(const void* bank, int64_t n, int d, const void* queries, int q_total, in
                 const IscShadowArgs sa{reinterpret_cast<const IscShadowRec*>(sh + isc_shadow_data_bytes(n, d)), w.qrec8};
                 for_each_segment(l, p, [&](const Level& ls) {
                     isc_timing_begin(ISC_KERNEL_DOTS_FILTER, stream);
+#ifdef ISC_ABLATION
+                    if (debug_mode() == 49)  // the tile-end ceiling (wrong results)
+                        hipLaunchKernelGGL((k_dots_filter<signed char, 256, 49, false, IscShadowArgs>),
+                                           dim3(ls.nchunks, p.qtiles), dim3(NTHREADS), 0, stream, sh, ls.r0, ls.r1,
+                                           ls.tiles_per_chunk, ls.ntiles, w.qpacked8, ks8, w.tau, p.qpad, w.seg_ent,
+                                           w.qcount, w.qlist, p.kp, p.nslots, w.qflag, status, (const int32_t*)nullptr, sa);
+                    else
+#endif
                     hipLaunchKernelGGL((k_dots_filter<signed char, 256, 12, false, IscShadowArgs>),
                                        dim3(ls.nchunks, p.qtiles), dim3(NTHREADS), 0, stream, sh, ls.r0, ls.r1,
                                        ls.tiles_per_chunk, ls.ntiles, w.qpacked8, ks8, w.tau, p.qpad, w.seg_ent, w.qcount,

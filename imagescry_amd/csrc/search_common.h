@@ -217,6 +217,15 @@ struct Mma<signed char> {
             acc[n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b[n]),
                                                            acc[n], 0, 0, 0);
     }
+    // `part` as the first instructions of a tile: acc[n] = A . B[n], the C operand being the constant 0 instead of a
+    // register that holds 0 (the same integers, and nobody has to clear the accumulators between tiles)
+    template <int N0, int N1>
+    static __device__ __forceinline__ void part_first(const u32x4& a, const u32x4 (&b)[4], i32x4 (&acc)[4]) {
+#pragma unroll
+        for (int n = N0; n < N1; ++n)
+            acc[n] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b[n]),
+                                                           i32x4{0, 0, 0, 0}, 0, 0, 0);
+    }
 };
 
 // ---- the packed image of a call's queries (k_prep of the searches, k_assign_prep of isc_bank_assign) ----------------

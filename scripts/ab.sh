@@ -18,6 +18,7 @@
 #   ab_noq         ab.sh search -a m12:ablation:ISC_DEBUG_MODE=12 -a m41:ablation:ISC_DEBUG_MODE=41 -a m17:ablation:ISC_DEBUG_MODE=17 -- 10000000x1024
 #   ab_asym        ab.sh search -a sym:sym -a a6:a6 -a a5:a5 -- 10000000x1024      (variants: -DISC_ASYM_MBLO=<n>)
 #   ab_hm          ab.sh search -a hm:hm0:ISC_DEBUG_MODE=46 -a base:hm0:ISC_DEBUG_MODE=12 -- 10000000x1024
+#   ab_tile_end    ab.sh search -r 3 -a m12:zc0:ISC_DEBUG_MODE=12 -a m12inf:zc0:ISC_DEBUG_MODE=12,ISC_THR_INF=1 -a m49:zc0:ISC_DEBUG_MODE=49 -- 10000000x1024      (variant: -DISC_HM_ZERO_C=0)
 #   ab_gemm        ab.sh gemm -r 1 -a d0:ablation:ISC_GEMM_DEBUG=0 -a d1:ablation:ISC_GEMM_DEBUG=1 ...
 #   ab_gemm_split  ab.sh gemm -a split:ablation -a nosplit:ablation:ISC_GEMM_NO_SPLIT=1
 #   ab_gemm_seg    ab.sh gemm -r 1 -a seg0:ablation:ISC_GEMM_SEG=0 -a seg4:ablation:ISC_GEMM_SEG=4
