@@ -29,6 +29,8 @@ ISC_TOPK_LARGE_MAX_K = 4096  # isc_cosine_topk_large / isc_cosine_topk_exhaustiv
 ISC_SEARCH_MAX_D = 8192
 ISC_SEARCH_PASS_QUERIES = 1024  # queries per pass of isc_cosine_topk (the workspace is sized for one pass)
 ISC_FARTHEST_MAX_PICKS = 1 << 20  # isc_bank_farthest
+ISC_ATT_PART_QUERY = 0  # isc_attention_f16_self*: which columns of qkv play query and key
+ISC_ATT_PART_KEY = 1
 ISC_ABI_VERSION = 4
 ISC_BUILD_ABLATION = 1
 ISC_GEMM_A_PACKED, ISC_GEMM_W_PACKED, ISC_GEMM_OUT_PACKED, ISC_GEMM_TILE_256, ISC_GEMM_TILE_128 = 1, 2, 4, 8, 16
@@ -178,6 +180,8 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     ),
     "isc_attention_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "isc_attention_f16_stream": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "isc_attention_f16_self": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "isc_attention_f16_self_stream": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "isc_attention_stream_geometry": (c_int, [POINTER(c_int), POINTER(c_int)]),
     "isc_attention_f16_causal": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "isc_text_embed": (
@@ -205,6 +209,7 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
         c_int,
         [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_float, c_void_p, c_void_p],
     ),
+    "isc_tokens_to_map": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "isc_cosine_topk_workspace_bytes": (c_int, [c_int, c_int64, c_int, c_int, c_int, POINTER(c_size_t)]),
     "isc_cosine_topk": (
         c_int,

@@ -782,8 +782,9 @@ struct AttStaged {
     static constexpr int ROUNDS = (TROWS * 8 + THREADS - 1) / THREADS;
     half8 k[ROUNDS], v[ROUNDS];
 
-    // rows [row0, row0 + T) of head h; token rows at or past T are never read: they are staged as zeros
-    template <bool PACKED>
+    // rows [row0, row0 + T) of head h; token rows at or past T are never read: they are staged as zeros.  KPART: the part
+    // of the row the "key" rows come from (vit_attention.h)
+    template <bool PACKED, int KPART = ATT_PART_KEY>
     __device__ __forceinline__ void load(const _Float16* qkv, long long row0, int T, int D, int h, int tid) {
 #pragma unroll
         for (int r = 0; r < ROUNDS; ++r) {
@@ -792,8 +793,8 @@ struct AttStaged {
             k[r] = half8{0, 0, 0, 0, 0, 0, 0, 0};
             v[r] = k[r];
             if (t < T) {
-                k[r] = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row0 + t, D, h, 1, c));
-                v[r] = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row0 + t, D, h, 2, c));
+                k[r] = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row0 + t, D, h, KPART, c));
+                v[r] = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row0 + t, D, h, ATT_PART_VALUE, c));
             }
         }
     }
@@ -816,7 +817,9 @@ struct AttStaged {
 #ifdef ISC_ABLATION
 __device__ int g_att_abl = 0;  // ISC_ATT_ABL (timing aid, wrong results): 1 = stage keys / values only, 2 = no staging loads
 #endif
-template <bool PACKED, int NKB, bool TAIL>
+// QPART / KPART: the parts of the row the query operand and the staged key rows come from -- (0, 1), or the same part
+// twice for self attention (isc_attention_f16_self)
+template <bool PACKED, int NKB, bool TAIL, int QPART = ATT_PART_QUERY, int KPART = ATT_PART_KEY>
 __global__ __launch_bounds__(ATT_THREADS) void k_attention_f16(const _Float16* __restrict__ qkv, int T, int heads,
                                                                 _Float16* __restrict__ out) {
     static_assert(NKB >= 1 && NKB <= ATT_TMAX / 16, "key blocks");
@@ -829,9 +832,9 @@ __global__ __launch_bounds__(ATT_THREADS) void k_attention_f16(const _Float16* _
     const int tid = threadIdx.x;
     AttStaged<NKB, ATT_THREADS> staged;
 #ifdef ISC_ABLATION
-    staged.template load<PACKED>(qkv, row0, (g_att_abl & 2) ? 0 : T, D, h, tid);
+    staged.template load<PACKED, KPART>(qkv, row0, (g_att_abl & 2) ? 0 : T, D, h, tid);
 #else
-    staged.template load<PACKED>(qkv, row0, T, D, h, tid);
+    staged.template load<PACKED, KPART>(qkv, row0, T, D, h, tid);
 #endif
     staged.store(Ks, Vs, tid);
     __syncthreads();
@@ -848,7 +851,7 @@ __global__ __launch_bounds__(ATT_THREADS) void k_attention_f16(const _Float16* _
         const int tq = qb * 16 + qi;
         const long long row = row0 + min(tq, T - 1);
         half8 qf[2];
-        att_load_query<PACKED>(qf, qkv, row, D, h, g);
+        att_load_query<PACKED, QPART>(qf, qkv, row, D, h, g);
         att_scale_query(qf, qf);
         att_query_block<NKB, TAIL>(Ks, Vs, qf, T, tq, qi, g, att_out_row<PACKED>(out, row, D, h));
     }
@@ -862,7 +865,7 @@ __global__ __launch_bounds__(ATT_THREADS) void k_attention_f16(const _Float16* _
 // arithmetic (att_query_block): bit-identical results (tests/test_gpu_vit_exact.py).
 constexpr int ATT_P_THREADS = 1024;
 constexpr int ATT_P_LDS_BYTES = 2 * ATT_TMAX * 2 * ATT_STRIDE * 2;  // two (K, V) images: 126 KiB
-template <bool PACKED, int NKB, bool TAIL>
+template <bool PACKED, int NKB, bool TAIL, int QPART = ATT_PART_QUERY, int KPART = ATT_PART_KEY>
 __global__ __launch_bounds__(ATT_P_THREADS) void k_attention_f16_p(const _Float16* __restrict__ qkv, int T, int heads,
                                                                     _Float16* __restrict__ out, int total) {
     extern __shared__ __attribute__((aligned(16))) unsigned char att_lds[];
@@ -880,8 +883,8 @@ __global__ __launch_bounds__(ATT_P_THREADS) void k_attention_f16_p(const _Float1
     half8 qn[2];
     auto load_item = [&](int item) {
         const int b = item / heads, h = item - b * heads;
-        staged.template load<PACKED>(qkv, (long long)b * T, T, D, h, tid);
-        if (wave < nqb) att_load_query<PACKED>(qn, qkv, (long long)b * T + min(tq, T - 1), D, h, g);
+        staged.template load<PACKED, KPART>(qkv, (long long)b * T, T, D, h, tid);
+        if (wave < nqb) att_load_query<PACKED, QPART>(qn, qkv, (long long)b * T + min(tq, T - 1), D, h, g);
     };
     auto store_item = [&](int buf) { staged.store(kv + buf * IMG, kv + buf * IMG + ATT_TMAX * ATT_STRIDE, tid); };
     int item = blockIdx.x;
@@ -1189,8 +1192,8 @@ static bool att_p_prepare(const void* fn, unsigned long long* done) {
     return true;
 }
 
-extern "C" int isc_attention_f16(const void* qkv, int B, int T, int heads, int head_dim, void* out, int packed,
-                                 void* stream) {
+template <int QPART, int KPART>
+static int attention_launch(const void* qkv, int B, int T, int heads, int head_dim, void* out, int packed, void* stream) {
     ISC_REQUIRE(qkv && out && B > 0 && T > 0 && heads > 0);
     if (head_dim != 64 || T > ATT_TMAX) return ISC_ERR_UNSUPPORTED;
     if (!isc_aligned(qkv, 16) || !isc_aligned(out, 16)) return ISC_ERR_ALIGNMENT;
@@ -1214,16 +1217,16 @@ extern "C" int isc_attention_f16(const void* qkv, int B, int T, int heads, int h
 #define ISC_ATT_LAUNCH(PK_, NKB_, TAIL_)                                                                              \
     do {                                                                                                              \
         if (persistent) {                                                                                             \
-            auto kern = k_attention_f16_p<PK_, NKB_, TAIL_>;                                                          \
+            auto kern = k_attention_f16_p<PK_, NKB_, TAIL_, QPART, KPART>;                                            \
             static unsigned long long attr_done = 0; /* per device: the dynamic-LDS limit of this instantiation is set */ \
             if (!att_p_prepare(reinterpret_cast<const void*>(kern), &attr_done)) return ISC_ERR_UNSUPPORTED;          \
             hipLaunchKernelGGL(kern, dim3((unsigned)cus), dim3(ATT_P_THREADS), ATT_P_LDS_BYTES, isc_stream(stream),   \
                                reinterpret_cast<const _Float16*>(qkv), T, heads, reinterpret_cast<_Float16*>(out),    \
                                total);                                                                                \
         } else {                                                                                                      \
-            hipLaunchKernelGGL((k_attention_f16<PK_, NKB_, TAIL_>), dim3((unsigned)total), dim3(ATT_THREADS), 0,      \
-                               isc_stream(stream), reinterpret_cast<const _Float16*>(qkv), T, heads,                  \
-                               reinterpret_cast<_Float16*>(out));                                                     \
+            hipLaunchKernelGGL((k_attention_f16<PK_, NKB_, TAIL_, QPART, KPART>), dim3((unsigned)total),              \
+                               dim3(ATT_THREADS), 0, isc_stream(stream), reinterpret_cast<const _Float16*>(qkv), T,   \
+                               heads, reinterpret_cast<_Float16*>(out));                                              \
         }                                                                                                             \
     } while (0)
     // 192 < T <= 208 (ViT-B/16: 197 tokens): thirteen key blocks, only the last one masked; 208 < T: fourteen, likewise;
@@ -1240,6 +1243,20 @@ extern "C" int isc_attention_f16(const void* qkv, int B, int T, int heads, int h
     }
 #undef ISC_ATT_LAUNCH
     return isc_launch_status();
+}
+
+extern "C" int isc_attention_f16(const void* qkv, int B, int T, int heads, int head_dim, void* out, int packed,
+                                 void* stream) {
+    return attention_launch<ATT_PART_QUERY, ATT_PART_KEY>(qkv, B, T, heads, head_dim, out, packed, stream);
+}
+
+extern "C" int isc_attention_f16_self(const void* qkv, int B, int T, int heads, int head_dim, int part, void* out,
+                                      int packed, void* stream) {
+    if (part == ATT_PART_QUERY)
+        return attention_launch<ATT_PART_QUERY, ATT_PART_QUERY>(qkv, B, T, heads, head_dim, out, packed, stream);
+    if (part == ATT_PART_KEY)
+        return attention_launch<ATT_PART_KEY, ATT_PART_KEY>(qkv, B, T, heads, head_dim, out, packed, stream);
+    return ISC_ERR_INVALID_ARG;
 }
 
 extern "C" int isc_patchify_f16(const float* x, int B, int C, int H, int W, int patch, void* patches, int packed,

@@ -31,11 +31,20 @@ __device__ __forceinline__ _Float16* att_out_row(_Float16* out, long long row, i
     return PACKED ? out + pk_offset(row, h * 64, D) : out + (size_t)row * (size_t)D + h * 64;
 }
 
+// The parts of a qkv row.  QPART / KPART of the kernels name the part the "query" operand and the staged "key" rows are
+// read from: (0, 1) is attention; (0, 0) and (1, 1) are SELF attention, softmax(z z^T / 8) v with z the query or the key
+// columns (isc_attention_f16_self*), which never reads the other of the two.
+constexpr int ATT_PART_QUERY = 0;
+constexpr int ATT_PART_KEY = 1;
+constexpr int ATT_PART_VALUE = 2;
+static_assert(ATT_PART_QUERY == ISC_ATT_PART_QUERY && ATT_PART_KEY == ISC_ATT_PART_KEY, "the header's part numbers");
+
 // A lane's two query fragments, the "B" operand of the score MFMAs: chunks g and 4 + g of its query's row ...
-template <bool PACKED>
+template <bool PACKED, int QPART = ATT_PART_QUERY>
 __device__ __forceinline__ void att_load_query(half8 (&q)[2], const _Float16* qkv, long long row, int D, int h, int g) {
+    static_assert(QPART == ATT_PART_QUERY || QPART == ATT_PART_KEY, "the query operand is the q or the k columns");
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) q[kk] = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row, D, h, 0, kk * 4 + g));
+    for (int kk = 0; kk < 2; ++kk) q[kk] = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row, D, h, QPART, kk * 4 + g));
 }
 // ... times 1/sqrt(64): a power of two, so the scaling is exact
 __device__ __forceinline__ void att_scale_query(half8 (&qf)[2], const half8 (&q)[2]) {

@@ -85,8 +85,9 @@ __device__ __forceinline__ void as_chunk(const _Float16* __restrict__ Ks, const 
     }
 }
 
-// pairs = B * heads, nqb = query blocks per pair; the grid is ceil(pairs / 8) * 8 * nqb workgroups
-template <bool PACKED>
+// pairs = B * heads, nqb = query blocks per pair; the grid is ceil(pairs / 8) * 8 * nqb workgroups.  QPART / KPART: the
+// parts of the row the query operand and the staged key rows come from (vit_attention.h).
+template <bool PACKED, int QPART = ATT_PART_QUERY, int KPART = ATT_PART_KEY>
 __global__ __launch_bounds__(AS_THREADS) void k_attention_f16_stream(const _Float16* __restrict__ qkv, int T, int heads,
                                                                        int pairs, int nqb, _Float16* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) _Float16 Kb[2][AS_KC * ATT_STRIDE];
@@ -110,8 +111,8 @@ __global__ __launch_bounds__(AS_THREADS) void k_attention_f16_stream(const _Floa
         kreg = half8{0, 0, 0, 0, 0, 0, 0, 0};
         vreg = kreg;
         if (k0 + st < T) {  // rows at or past T are never read: they are staged as zeros
-            kreg = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row0 + (k0 + st), D, h, 1, sc));
-            vreg = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row0 + (k0 + st), D, h, 2, sc));
+            kreg = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row0 + (k0 + st), D, h, KPART, sc));
+            vreg = *reinterpret_cast<const half8*>(att_qkv_at<PACKED>(qkv, row0 + (k0 + st), D, h, ATT_PART_VALUE, sc));
         }
     };
     auto stage_store = [&](int buf) {
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(AS_THREADS) void k_attention_f16_stream(const _Floa
     const bool active = q0 + wave * 16 < T;  // (wave-uniform) a wave without queries only stages
     stage_load(0);
     half8 qf[2];
-    att_load_query<PACKED>(qf, qkv, row0 + min(tq, T - 1), D, h, g);
+    att_load_query<PACKED, QPART>(qf, qkv, row0 + min(tq, T - 1), D, h, g);
     att_scale_query(qf, qf);
     stage_store(0);
     __syncthreads();
@@ -167,8 +168,10 @@ extern "C" int isc_attention_stream_geometry(int* query_block, int* key_chunk) {
     return ISC_OK;
 }
 
-extern "C" int isc_attention_f16_stream(const void* qkv, int B, int T, int heads, int head_dim, void* out, int packed,
-                                        void* stream) {
+namespace {
+
+template <int QPART, int KPART>
+int attention_stream_launch(const void* qkv, int B, int T, int heads, int head_dim, void* out, int packed, void* stream) {
     ISC_REQUIRE(qkv && out && B > 0 && T > 0 && heads > 0);
     if (head_dim != 64) return ISC_ERR_UNSUPPORTED;
     if (!isc_aligned(qkv, 16) || !isc_aligned(out, 16)) return ISC_ERR_ALIGNMENT;
@@ -178,12 +181,28 @@ extern "C" int isc_attention_f16_stream(const void* qkv, int B, int T, int heads
     const long long grid = (pairs + AS_XCDS - 1) / AS_XCDS * AS_XCDS * nqb;
     if (pairs > 0x7fffffffLL || grid > 0x7fffffffLL) return ISC_ERR_UNSUPPORTED;
     if (packed)
-        hipLaunchKernelGGL(k_attention_f16_stream<true>, dim3((unsigned)grid), dim3(AS_THREADS), 0, isc_stream(stream),
-                           reinterpret_cast<const _Float16*>(qkv), T, heads, (int)pairs, nqb,
+        hipLaunchKernelGGL((k_attention_f16_stream<true, QPART, KPART>), dim3((unsigned)grid), dim3(AS_THREADS), 0,
+                           isc_stream(stream), reinterpret_cast<const _Float16*>(qkv), T, heads, (int)pairs, nqb,
                            reinterpret_cast<_Float16*>(out));
     else
-        hipLaunchKernelGGL(k_attention_f16_stream<false>, dim3((unsigned)grid), dim3(AS_THREADS), 0, isc_stream(stream),
-                           reinterpret_cast<const _Float16*>(qkv), T, heads, (int)pairs, nqb,
+        hipLaunchKernelGGL((k_attention_f16_stream<false, QPART, KPART>), dim3((unsigned)grid), dim3(AS_THREADS), 0,
+                           isc_stream(stream), reinterpret_cast<const _Float16*>(qkv), T, heads, (int)pairs, nqb,
                            reinterpret_cast<_Float16*>(out));
     return isc_launch_status();
+}
+
+}  // namespace
+
+extern "C" int isc_attention_f16_stream(const void* qkv, int B, int T, int heads, int head_dim, void* out, int packed,
+                                        void* stream) {
+    return attention_stream_launch<ATT_PART_QUERY, ATT_PART_KEY>(qkv, B, T, heads, head_dim, out, packed, stream);
+}
+
+extern "C" int isc_attention_f16_self_stream(const void* qkv, int B, int T, int heads, int head_dim, int part, void* out,
+                                             int packed, void* stream) {
+    if (part == ATT_PART_QUERY)
+        return attention_stream_launch<ATT_PART_QUERY, ATT_PART_QUERY>(qkv, B, T, heads, head_dim, out, packed, stream);
+    if (part == ATT_PART_KEY)
+        return attention_stream_launch<ATT_PART_KEY, ATT_PART_KEY>(qkv, B, T, heads, head_dim, out, packed, stream);
+    return ISC_ERR_INVALID_ARG;
 }

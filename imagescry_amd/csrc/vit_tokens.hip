@@ -1,5 +1,5 @@
 // Patch-token output of the ViT encoder (include/imagescry_hip.h: isc_vit_pos_resample, isc_vit_pos_resample_aa,
-// isc_vit_tokens_out, isc_vit_tokens_out_skip): the position table of an h x w token grid, and the head that turns the residual stream into the channels-first
+// isc_vit_tokens_out, isc_vit_tokens_out_skip, isc_tokens_to_map): the position table of an h x w token grid, and the head that turns the residual stream into the channels-first
 // embedding map [B, D, h, w] every other embedder returns.
 #include "aa_filter.h"
 #include "isc_common.h"
@@ -93,7 +93,8 @@ __global__ __launch_bounds__(256) void k_vit_pos_resample_aa(const float* __rest
 //   phase 1  LayerNorm, one wave per token (k_layernorm's arithmetic: the same lane -> channel map, the same two passes
 //            over registers), four tokens per wave, all their loads requested before the first is used; the result goes
 //            to LDS as [channel / 4][cell][4] -- a lane's four channels are one 16-byte store, rows padded by 16 bytes so
-//            that the eight lanes of a store group (528 bytes apart) fall on eight different slots;
+//            that the eight lanes of a store group (528 bytes apart) fall on eight different slots; without LN
+//            (isc_tokens_to_map: rows that are final already, a projection's output) the loaded row goes to LDS as it is;
 //   phase 2  (normalize) the arithmetic of k_l2norm_spatial, bit for bit: per cell four partial sums of squares over the
 //            channels e = g, g + 4, ... in ascending order, denominator max(sqrt(r0 + r1 + r2 + r3), eps);
 //   phase 3  the transposed store: a 32-lane half of a wave reads four channels of 32 consecutive cells (one 16-byte LDS
@@ -107,7 +108,7 @@ constexpr int TO_PITCH = TO_CELLS * 4 + 4;      // floats per LDS row (four chan
 constexpr int TO_MAX_D = 1024;
 constexpr int TO_MAX_LDS = (TO_MAX_D / 4) * TO_PITCH * 4 + TO_CELLS * 4;
 
-template <int NV>
+template <int NV, bool LN = true>
 __global__ __launch_bounds__(TO_THREADS) void k_vit_tokens_out(const float* __restrict__ tokens, int T, int D,
                                                                const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float eps, int normalize,
@@ -142,6 +143,14 @@ __global__ __launch_bounds__(TO_THREADS) void k_vit_tokens_out(const float* __re
     for (int k = 0; k < TO_TOKENS; ++k) {
         const int j = wave + TO_WAVES * k;
         if (j >= ncell) continue;  // wave-uniform
+        if (!LN) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int c = lane + 64 * i;
+                if (c < nvec) *reinterpret_cast<f32x4*>(tile + c * TO_PITCH + j * 4) = v[k][i];
+            }
+            continue;
+        }
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) s += (v[k][i][0] + v[k][i][1]) + (v[k][i][2] + v[k][i][3]);
@@ -248,20 +257,22 @@ extern "C" int isc_vit_pos_resample_aa(const float* pos_embed, int g, int h, int
     return isc_launch_status();
 }
 
-extern "C" int isc_vit_tokens_out_skip(const float* tokens, int B, int T, int skip, int D, const float* gamma,
-                                       const float* beta, float eps, int normalize, float l2_eps, float* out,
-                                       void* stream) {
-    ISC_REQUIRE(tokens && gamma && beta && out && B > 0 && skip >= 1 && T > skip && D > 0 && eps >= 0.f && l2_eps >= 0.f);
+// LN: gamma / beta / eps are LayerNorm's; without it they are not looked at (nullptr, nullptr, 0)
+template <bool LN>
+static int tokens_out_launch(const float* tokens, int B, int T, int skip, int D, const float* gamma, const float* beta,
+                             float eps, int normalize, float l2_eps, float* out, void* stream) {
+    ISC_REQUIRE(tokens && out && B > 0 && skip >= 1 && T > skip && D > 0 && l2_eps >= 0.f);
+    if (LN) ISC_REQUIRE(gamma && beta && eps >= 0.f);
     if (D % 4 != 0 || D > TO_MAX_D) return ISC_ERR_UNSUPPORTED;
-    if (!isc_aligned(tokens, 16) || !isc_aligned(gamma, 16) || !isc_aligned(beta, 16) || !isc_aligned(out, 16))
-        return ISC_ERR_ALIGNMENT;
+    if (!isc_aligned(tokens, 16) || !isc_aligned(out, 16)) return ISC_ERR_ALIGNMENT;
+    if (LN && (!isc_aligned(gamma, 16) || !isc_aligned(beta, 16))) return ISC_ERR_ALIGNMENT;
     const int tiles = isc_ceil_div(T - skip, TO_CELLS);
     if ((long long)B * tiles > 0x7fffffffLL) return ISC_ERR_UNSUPPORTED;
     const int nv = (D / 4 + 63) / 64;
     const size_t lds = (size_t)(D / 4) * TO_PITCH * 4 + TO_CELLS * 4;
 #define ISC_TO_LAUNCH(NV_)                                                                                          \
     do {                                                                                                            \
-        auto kern = k_vit_tokens_out<NV_>;                                                                          \
+        auto kern = k_vit_tokens_out<NV_, LN>;                                                                      \
         static unsigned long long attr_done = 0;                                                                    \
         if (!tokens_out_prepare(reinterpret_cast<const void*>(kern), &attr_done)) return ISC_ERR_UNSUPPORTED;       \
         hipLaunchKernelGGL(kern, dim3((unsigned)(B * tiles)), dim3(TO_THREADS), lds, isc_stream(stream), tokens, T, D, \
@@ -273,6 +284,17 @@ extern "C" int isc_vit_tokens_out_skip(const float* tokens, int B, int T, int sk
     else ISC_TO_LAUNCH(4);
 #undef ISC_TO_LAUNCH
     return isc_launch_status();
+}
+
+extern "C" int isc_vit_tokens_out_skip(const float* tokens, int B, int T, int skip, int D, const float* gamma,
+                                       const float* beta, float eps, int normalize, float l2_eps, float* out,
+                                       void* stream) {
+    return tokens_out_launch<true>(tokens, B, T, skip, D, gamma, beta, eps, normalize, l2_eps, out, stream);
+}
+
+extern "C" int isc_tokens_to_map(const float* tokens, int B, int T, int skip, int D, int normalize, float l2_eps,
+                                 float* out, void* stream) {
+    return tokens_out_launch<false>(tokens, B, T, skip, D, nullptr, nullptr, 0.f, normalize, l2_eps, out, stream);
 }
 
 extern "C" int isc_vit_tokens_out(const float* tokens, int B, int T, int D, const float* gamma, const float* beta,

@@ -501,6 +501,15 @@ class ViTB16Embedder(EmbeddingModule):
     def forward(self, x: Tensor) -> Tensor:
         return self._forward(x, normalized=False)
 
+    # the patch map of one pass, written into `out`: the tokens behind the final LayerNorm, `config.dim` channels
+    # (`CLIPEmbedder` with `dense=` puts its projected map here)
+    @property
+    def _patch_map_dim(self) -> int:
+        return self.config.dim
+
+    def _patch_map(self, x: Tensor, grid: tuple[int, int], normalized: bool, out: Tensor, cap: int | None) -> None:
+        vit.forward_tokens(self._net, x, grid, normalize=normalized, out=out, max_patches=cap)
+
     def _forward(self, x: Tensor, normalized: bool) -> Tensor:
         if not isinstance(x, Tensor) or x.dtype != torch.float32:
             raise TypeError("x must be a float32 tensor")
@@ -513,11 +522,10 @@ class ViTB16Embedder(EmbeddingModule):
         step = vit.images_per_pass(grid[0] * grid[1] + self.config.num_prefix, self.max_images_per_pass)
         cap = self._patch_cap if self.grid == "aspect" else None
         if self.output == "patches":
-            out = torch.empty((b, self.config.dim, *grid), dtype=torch.float32, device=x.device)
+            out = torch.empty((b, self._patch_map_dim, *grid), dtype=torch.float32, device=x.device)
             with torch.cuda.device(x.device):
                 for b0 in range(0, b, step):
-                    vit.forward_tokens(self._net, x[b0 : b0 + step], grid, normalize=normalized, out=out[b0 : b0 + step],
-                                       max_patches=cap)
+                    self._patch_map(x[b0 : b0 + step], grid, normalized, out[b0 : b0 + step], cap)
             return out
         out = torch.empty((b, self.embedding_dim), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
@@ -654,7 +662,17 @@ class CLIPEmbedder(_CheckpointPreprocess, ViTB16Embedder):
     `state_dict` holds both towers under `clip`'s names (`clip.from_openai_state_dict`, `clip.from_transformers_state_dict`,
     `clip.make_state_dict`); without it the weights are seeded random ones.  `act` is a property of the checkpoint:
     "quick_gelu" for OpenAI's, "gelu" for open_clip / LAION ones.  `preset` may also be a `clip.CLIPConfig`.
-    `output="patches"` is refused: a projected patch map is not what the checkpoints were trained to align with text.
+
+    `output="patches"` needs `dense=`: the raw patch tokens, projected, are not what the checkpoints were trained to align
+    with text, and without `dense` the mode is refused.  `dense="value"` (MaskCLIP), `"kk"` or `"qq"` (SCLIP / ClearCLIP
+    self-self attention) is the standard training-free remedy, a change of the LAST block only (`vit.forward_dense` has
+    the arithmetic): no residual and no MLP there, and in place of query-key attention the value path alone, or
+    `softmax(K K^T / 8) V` / `softmax(Q Q^T / 8) V`; every token then goes through the final LayerNorm and the
+    projection.  The result is the `[B, E, h, w]` map of the other patch embedders -- cell `(i, j)` = patch token
+    `1 + i w + j`, `forward` unnormalised, `predict_step` L2-normalised by the head kernel (`isc_tokens_to_map`) -- in
+    the TEXT tower's space: a bank of its rows with `row_groups` = the image index answers `bank.search_groups(
+    model.encode_text(ids), k)`, "which images contain this, and where".  `grid="aspect"`, `max_patches` (above 224
+    tokens the streaming kernels) and `preprocess="checkpoint"` work as for `ViTB16Embedder` / `DINOv2Embedder`.
 
     `preprocess="squash"` (the default) is this package's squash-`resize` to `image_size` (or, with `grid="aspect"`, to
     the aspect grid) and `normalize_per_channel` with CLIP's FIXED statistics (`clip.IMAGE_MEAN`, `clip.IMAGE_STD`,
@@ -679,6 +697,7 @@ class CLIPEmbedder(_CheckpointPreprocess, ViTB16Embedder):
         preprocess: str = "squash",
         crop_size: int | None = None,
         resize_size: int | None = None,
+        dense: str | None = None,
     ) -> None:
         if isinstance(preset, clip.CLIPConfig):
             cfg = preset
@@ -686,16 +705,29 @@ class CLIPEmbedder(_CheckpointPreprocess, ViTB16Embedder):
             cfg = clip.PRESETS[preset]
         else:
             raise ValueError(f"preset must be one of {sorted(clip.PRESETS)} or a clip.CLIPConfig, got {preset!r}")
-        if output != "cls":
-            raise ValueError(f'CLIPEmbedder has no output={output!r}: only the projected class token ("cls") lives in '
-                             "the text tower's space")
+        if dense is not None and dense not in vit.DENSE_MODES:
+            raise ValueError(f"dense must be None or one of {vit.DENSE_MODES}, got {dense!r}")
+        if output == "patches" and dense is None:
+            raise ValueError('CLIPEmbedder has no output="patches" without dense=: the projected raw patch tokens do not '
+                             'live in the text tower\'s space; dense="value", "kk" or "qq" gives a patch map that does')
+        if output not in ("cls", "patches"):
+            raise ValueError(f'CLIPEmbedder has no output={output!r}: "cls" (the projected class token) or "patches" '
+                             "(with dense=)")
+        if dense is not None and output != "patches":
+            raise ValueError(f'dense={dense!r} needs output="patches": the class token has no dense form')
         cfg = clip.with_act(cfg, act)
         sd = state_dict if state_dict is not None else clip.make_state_dict(cfg, seed=seed)
         super().__init__(config=cfg.vision, state_dict=clip.tower(sd, "visual"), seed=seed,
                          max_images_per_pass=max_images_per_pass, output=output, grid=grid, max_patches=max_patches)
         self.clip_config = cfg
+        self.dense = dense
+        # the value third of the last block's qkv projection, only where it is the whole of that block's attention
+        self._dense_value = (vit.prepare_value_linear(clip.tower(sd, "visual"), f"blocks.{cfg.vision.depth - 1}")
+                             if dense == "value" else None)
         self._text = clip.prepare_text(clip.tower(sd, "text"), cfg.text)
         self.hparams.update(act=act, embed_dim=cfg.embed_dim)
+        if dense is not None:
+            self.hparams.update(dense=dense)
         if isinstance(preset, str):
             self.hparams.update(preset=preset)
         self._stats: dict[torch.device, tuple[Tensor, Tensor]] = {}
@@ -705,6 +737,16 @@ class CLIPEmbedder(_CheckpointPreprocess, ViTB16Embedder):
     def _move(self, device: torch.device) -> None:
         super()._move(device)
         self._text = self._text.to(device)
+        if self._dense_value is not None:
+            self._dense_value = self._dense_value.to(device)
+
+    @property
+    def _patch_map_dim(self) -> int:
+        return self.embedding_dim
+
+    def _patch_map(self, x: Tensor, grid: tuple[int, int], normalized: bool, out: Tensor, cap: int | None) -> None:
+        vit.forward_dense(self._net, x, self.dense, grid, normalize=normalized, out=out, max_patches=cap,
+                          value=self._dense_value)
 
     def preprocess(self, images: Tensor) -> Tensor:
         if self.preprocess_mode == "checkpoint":

@@ -406,9 +406,10 @@ def position_table(net: PreparedViT, grid: tuple[int, int]) -> Tensor:
     return table
 
 
-def _encode(net: PreparedViT, x: Tensor, grid: tuple[int, int]) -> Tensor:
+def _encode(net: PreparedViT, x: Tensor, grid: tuple[int, int], blocks: list[Block] | None = None) -> Tensor:
     """float32 `[B, 3, P h, P w]` (already preprocessed) on a HIP device -> the float32 residual stream `[B * T, D]`
-    after the last block, `T = h w + cfg.num_prefix` (the final LayerNorm is the caller's).
+    after the last block, `T = h w + cfg.num_prefix` (the final LayerNorm is the caller's).  `blocks`: the blocks to
+    run, all of `net.blocks` by default (`forward_dense` leaves the last one out).
 
     Every fp16 activation (patches, LayerNorm outputs, qkv, attention output, MLP hidden) lives in the packed layout;
     the float32 residual stream is row-major."""
@@ -455,7 +456,8 @@ def _encode(net: PreparedViT, x: Tensor, grid: tuple[int, int]) -> Tensor:
         _lib.check(lib.isc_layernorm(xa.data_ptr(), m, d, d, net.norm_pre.weight.data_ptr(), net.norm_pre.bias.data_ptr(),
                                      cfg.ln_eps, xb.data_ptr(), _lib.ISC_F32, d, 0, stream), "isc_layernorm")
         xa, xb = xb, xa
-    return run_blocks(net.blocks, xa, xb, b, t, heads=cfg.heads, mlp_dim=cfg.mlp_dim, ln_eps=cfg.ln_eps, act=cfg.act)
+    return run_blocks(net.blocks if blocks is None else blocks, xa, xb, b, t, heads=cfg.heads, mlp_dim=cfg.mlp_dim,
+                      ln_eps=cfg.ln_eps, act=cfg.act)
 
 
 def run_blocks(blocks: list[Block], xa: Tensor, xb: Tensor, b: int, t: int, *, heads: int, mlp_dim: int, ln_eps: float,
@@ -555,7 +557,76 @@ def forward_tokens(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = N
     return out
 
 
-__all__ = ["ACTIVATIONS", "DINOV2_B14", "DINOV2_B14_REG", "DINOV2_L14", "DINOV2_L14_REG", "DINOV2_S14", "DINOV2_S14_REG", "IMAGENET_MEAN", "IMAGENET_STD",
+DENSE_MODES = ("value", "kk", "qq")
+
+
+def prepare_value_linear(sd: dict[str, Tensor], p: str) -> Linear:
+    """The value projection of block `p` = "blocks.i" on its own: rows `2 D : 3 D` of the fused `attn.qkv` weight and
+    bias, stored as `prepare_linear` stores a weight (`forward_dense(mode="value")` multiplies nothing else of it)."""
+    w, b = sd[f"{p}.attn.qkv.weight"], sd[f"{p}.attn.qkv.bias"]
+    d = w.shape[0] // 3
+    return prepare_linear({"v.weight": w[2 * d :], "v.bias": b[2 * d :]}, "v")
+
+
+def forward_dense(net: PreparedViT, x: Tensor, mode: str, grid: tuple[int, int] | None = None, normalize: bool = False,
+                  out: Tensor | None = None, max_patches: int | None = None, value: Linear | None = None) -> Tensor:
+    """float32 `[B, 3, P h, P w]` -> the float32 DENSE patch map `[B, E, h, w]` of a tower with a projection head
+    (`cfg.embed_dim`, CLIP): per-token features in the space the class token is projected into, by the training-free
+    change of the LAST block that MaskCLIP (`mode="value"`) and SCLIP / ClearCLIP ("kk", "qq") describe.  Blocks
+    `0 .. depth - 2` run as they are; with `x` the residual stream behind them and `h = LN1(x)` of the last block,
+
+        a = v_proj(h)                        "value": no attention, every token keeps its own value vector (`value`, the
+                                             Linear of `prepare_value_linear`: a third of the qkv product)
+        a = softmax(K K^T / 8) V per head    "kk", over all T tokens, the class token included (`isc_attention_f16_self`,
+                                             above 224 tokens `isc_attention_f16_self_stream`); "qq": Q in place of K
+        y = out_proj(a) + bias               NO residual and NO MLP
+        e = LN_post(y) . head.weight^T       no bias; `isc_layernorm` into a packed fp16 operand, then the GEMM
+
+    and the rows of the patch tokens go, transposed and (`normalize`) divided by `max(||cell||_2, 1e-12)`, into `out`
+    (`isc_tokens_to_map`): cell `(i, j)` is token `1 + i w + j`.  No workspace, no host synchronisation."""
+    cfg = net.cfg
+    if mode not in DENSE_MODES:
+        raise ValueError(f"mode must be one of {DENSE_MODES}, got {mode!r}")
+    if net.head is None or cfg.registers or cfg.layerscale or not net.blocks:
+        raise ValueError("a dense map needs a tower with a projection head (embed_dim), at least one block, no register "
+                         "tokens and no LayerScale")
+    if mode == "value" and (value is None or (value.out_features, value.in_features) != (cfg.dim, cfg.dim)):
+        raise ValueError('mode="value" needs the value Linear of the last block (prepare_value_linear)')
+    grid = (cfg.grid, cfg.grid) if grid is None else grid
+    _check_grid(net, x, grid, max_patches)
+    h, w = grid
+    b, d, e, t = x.shape[0], cfg.dim, net.head.out_features, h * w + 1
+    m = b * t
+    dev = x.device
+    if out is None:
+        out = torch.empty((b, e, h, w), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (b, e, h, w) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous float32 [{b}, {e}, {h}, {w}] tensor on {dev}")
+    xa = _encode(net, x, grid, net.blocks[:-1])
+    lib = _lib.load()
+    stream = _lib.stream_handle(dev)
+    blk = net.blocks[-1]
+    hbuf = torch.empty(packed_elems(m, d), dtype=torch.float16, device=dev)
+    att = torch.empty_like(hbuf)
+    _layernorm_packed(xa, m, blk.norm1, cfg.ln_eps, hbuf, stream)
+    if mode == "value":
+        _gemm(hbuf, m, value, att, stream=stream)
+    else:
+        qkv = torch.empty(packed_elems(m, 3 * d), dtype=torch.float16, device=dev)
+        _gemm(hbuf, m, blk.qkv, qkv, stream=stream)
+        part = _lib.ISC_ATT_PART_KEY if mode == "kk" else _lib.ISC_ATT_PART_QUERY
+        name = "isc_attention_f16_self" if t <= ONE_SHOT_TOKENS else "isc_attention_f16_self_stream"
+        _lib.check(getattr(lib, name)(qkv.data_ptr(), b, t, cfg.heads, d // cfg.heads, part, att.data_ptr(), 1, stream), name)
+        del qkv
+    y = _gemm(att, m, blk.proj, torch.empty((m, d), dtype=torch.float32, device=dev), stream=stream)
+    _layernorm_packed(y, m, net.norm, cfg.ln_eps, hbuf, stream)
+    tokens = _gemm(hbuf, m, net.head, torch.empty((m, e), dtype=torch.float32, device=dev), stream=stream)
+    _lib.check(lib.isc_tokens_to_map(tokens.data_ptr(), b, t, 1, e, int(normalize), 1e-12, out.data_ptr(), stream),
+               "isc_tokens_to_map")
+    return out
+
+
+__all__ = ["ACTIVATIONS", "DENSE_MODES", "DINOV2_B14", "DINOV2_B14_REG", "DINOV2_L14", "DINOV2_L14_REG", "DINOV2_S14", "DINOV2_S14_REG", "IMAGENET_MEAN", "IMAGENET_STD",
            "MAX_PATCHES",
            "VIT_B16", "ViTConfig", "forward_cls", "forward_tokens", "from_transformers_state_dict", "gemm_flops",
            "images_per_pass", "make_state_dict", "pack_rows", "position_table", "prepare", "prepare_block", "prepare_linear",

@@ -418,6 +418,24 @@ int isc_attention_f16(const void* qkv, int B, int T, int heads, int head_dim, vo
 int isc_attention_f16_stream(const void* qkv, int B, int T, int heads, int head_dim, void* out, int packed,
                              void* stream);
 
+/* SELF attention: softmax(z z^T / sqrt(head_dim)) v per (image, head), with z the QUERY columns (part ==
+ * ISC_ATT_PART_QUERY) or the KEY columns (ISC_ATT_PART_KEY) of the same fused qkv operand -- the last block of a dense
+ * CLIP forward (keys against keys, or queries against queries, in place of query-key attention).  It is
+ * isc_attention_f16 with the "query" operand and the staged "key" rows both read from part `part`: the same kernels
+ * (the part is a template parameter of theirs), operands, layouts, alignment, limits (head_dim == 64, T <= 224), error
+ * codes, dispatch and arithmetic, so the result has the bits of isc_attention_f16 on a copy of qkv whose query columns
+ * were overwritten with part `part`.  The OTHER of the two parts is never read.  Any other `part`:
+ * ISC_ERR_INVALID_ARG. */
+#define ISC_ATT_PART_QUERY 0
+#define ISC_ATT_PART_KEY 1
+int isc_attention_f16_self(const void* qkv, int B, int T, int heads, int head_dim, int part, void* out, int packed,
+                           void* stream);
+
+/* The same for any T >= 1: isc_attention_f16_stream with both operands read from part `part` (its bits on the
+ * rewritten operand, its limits, no workspace, no host synchronisation, capturable). */
+int isc_attention_f16_self_stream(const void* qkv, int B, int T, int heads, int head_dim, int part, void* out, int packed,
+                                  void* stream);
+
 /* The two constants of isc_attention_f16_stream: a workgroup owns `query_block` queries of one (image, head) and walks
  * the keys in chunks of `key_chunk` (a multiple of 32) -- the sequence lengths at which its code paths change. */
 int isc_attention_stream_geometry(int* query_block, int* key_chunk);
@@ -488,6 +506,16 @@ int isc_vit_tokens_out(const float* tokens, int B, int T, int D, const float* ga
  * skip == 1 is isc_vit_tokens_out bit for bit (one kernel serves both). */
 int isc_vit_tokens_out_skip(const float* tokens, int B, int T, int skip, int D, const float* gamma, const float* beta,
                             float eps, int normalize, float l2_eps, float* out, void* stream);
+
+/* The head without the LayerNorm, for rows that are final already (a projection's output: the dense CLIP patch map,
+ * ln_post -> projection -> this): out[b][e][t - skip] = tokens[b][t][e] for t = skip .. T - 1, each cell divided by
+ * max(||cell||_2, l2_eps) when normalize != 0 -- the transposition is exact and the division has the bits of
+ * isc_l2norm_channels on the unnormalised map (a zero cell stays zero).  The kernel of isc_vit_tokens_out_skip with its
+ * first phase a copy.  tokens float32 [B * T, D] row-major (D: the embedding width), out float32 [B, D, T - skip].
+ * 1 <= skip < T, else ISC_ERR_INVALID_ARG; D % 4 == 0 and D <= 1024, else ISC_ERR_UNSUPPORTED; both pointers 16-byte
+ * aligned.  One launch, no workspace, capturable. */
+int isc_tokens_to_map(const float* tokens, int B, int T, int skip, int D, int normalize, float l2_eps, float* out,
+                      void* stream);
 
 /* isc_vit_pos_resample with antialiasing (torch.nn.functional.interpolate(mode="bicubic", align_corners=False,
  * antialias=True)): cubic with A = -0.5; per axis, with s = g / h, the taps of output index i are the source indices
