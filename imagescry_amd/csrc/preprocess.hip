@@ -108,8 +108,14 @@ __global__ __launch_bounds__(kStatsThreads) void k_stats_partial_f32(const float
 }
 
 // One workgroup per channel: fixed-order sum of the partials, then mean and unbiased std in float64.
+// `integer_data` (the u8 path): a = sum x and q = sum x^2 are exact integers, and q - a * a / n would cancel once a * a
+// passes 2^53 (a near-constant batch: std 17 float32 ulp off at 8 x 224 x 224 pixels of 255 and one of 254).  The sums
+// are therefore shifted by the integer m0 = rint(a / n) first: S1 = sum (x - m0) = a - n m0 and S2 = sum (x - m0)^2 =
+// q - m0 (a + S1) are again exact integers in float64 (n < 2^36), |S1| <= n / 2, and S2 >= |S1| >= 2 S1^2 / n for
+// integer deviations, so S2 - S1^2 / n loses at most one bit.  The float32 path keeps the plain formula: its partial
+// sums are not integers, and its error is bounded in tests/preprocess_exact.py instead.
 __global__ __launch_bounds__(kStatsThreads) void k_stats_final(const StatPartial* __restrict__ part, int items_per_channel,
-                                                               double n, float* __restrict__ mean,
+                                                               double n, int integer_data, float* __restrict__ mean,
                                                                float* __restrict__ stdev) {
     const int c = blockIdx.x;
     double s = 0.0, ss = 0.0;
@@ -133,6 +139,12 @@ __global__ __launch_bounds__(kStatsThreads) void k_stats_final(const StatPartial
             q += red[1][w];
         }
         const double m = a / n;
+        if (integer_data) {
+            const double m0 = rint(m);
+            const double s1 = a - n * m0;
+            q -= m0 * (a + s1);
+            a = s1;
+        }
         double var = (q - a * a / n) / (n - 1.0);  // n == 1 -> NaN, as torch's unbiased std
         if (var < 0.0) var = 0.0;
         mean[c] = (float)m;
@@ -275,7 +287,9 @@ __global__ __launch_bounds__(256) void k_normalize_nhwc4(const T* __restrict__ x
 // torch upsample_bilinear2d (align_corners=False): src = scale * (dst + 0.5) - 0.5, clamped at 0;
 // i0 = min(int(src), in - 1); i1 = min(i0 + 1, in - 1); l1 = clamp(src - i0, 0, 1); l0 = 1 - l1.
 __device__ __forceinline__ void bilinear_tap(int dst, float scale, int in_size, int& i0, int& i1, float& l0, float& l1) {
-    float src = scale * ((float)dst + 0.5f) - 0.5f;
+    // one rounding, written out: the two-rounding form misses torch by 0.017 at 3001 -> 1000 (an ulp of 1500 in src), and which
+    // of the two `scale * (dst + 0.5f) - 0.5f` compiles to is the contraction default's choice
+    float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
     if (src < 0.f) src = 0.f;
     i0 = min((int)src, in_size - 1);
     i1 = min(i0 + 1, in_size - 1);
@@ -390,7 +404,7 @@ extern "C" int isc_channel_stats(const void* x, int dtype, int B, int C, int H, 
                            static_cast<const float*>(x), C, HW, chunks, part, items, vec_ok);
     }
     hipLaunchKernelGGL(k_stats_final, dim3(C), dim3(kStatsThreads), 0, isc_stream(stream), part, items,
-                       (double)B * (double)HW, mean, stdev);
+                       (double)B * (double)HW, dtype == ISC_U8 ? 1 : 0, mean, stdev);
     return isc_launch_status();
 }
 
