@@ -18,7 +18,7 @@ All arithmetic runs in hand-written HIP kernels behind the C ABI of include/imag
 PyTorch is used for device memory, streams and `torch.distributed` only.
 """
 
-from imagescry_amd import clip
+from imagescry_amd import clip, siglip
 from imagescry_amd.batching import ImageTensorDataset, SimilarShapeBatcher
 from imagescry_amd.data import EmbeddingBatch, ImageBatch
 from imagescry_amd.decomposition import PCA, KMeans
@@ -28,6 +28,7 @@ from imagescry_amd.embedding import (
     EfficientNetEmbedder,
     EmbeddingModule,
     ResNet50Embedder,
+    SigLIPEmbedder,
     ViTB16Embedder,
     l2_normalize_channels,
 )
@@ -51,8 +52,10 @@ __all__ = [
     "RangeResult",
     "RowFilter",
     "ResNet50Embedder",
+    "SigLIPEmbedder",
     "ViTB16Embedder",
     "clip",
+    "siglip",
     "l2_normalize_channels",
     "ImageBatch",
     "ImageTensorDataset",

@@ -23,6 +23,7 @@ LIB_PATH = Path(os.environ.get("ISC_LIB") or Path(__file__).resolve().parent / L
 
 ISC_U8, ISC_F16, ISC_F32 = 0, 1, 2
 ISC_ACT_NONE, ISC_ACT_RELU, ISC_ACT_GELU, ISC_ACT_SILU, ISC_ACT_SIGMOID, ISC_ACT_QUICK_GELU = 0, 1, 2, 3, 4, 5
+ISC_ACT_GELU_TANH = 6
 ISC_ACT_RESIDUAL_AFTER = 0x100
 ISC_TOPK_MAX_K = 120
 ISC_TOPK_LARGE_MAX_K = 4096  # isc_cosine_topk_large / isc_cosine_topk_exhaustive_large
@@ -35,6 +36,7 @@ ISC_ABI_VERSION = 4
 ISC_BUILD_ABLATION = 1
 ISC_GEMM_A_PACKED, ISC_GEMM_W_PACKED, ISC_GEMM_OUT_PACKED, ISC_GEMM_TILE_256, ISC_GEMM_TILE_128 = 1, 2, 4, 8, 16
 ISC_KERNEL_DOTS_FILTER, ISC_KERNEL_CONV, ISC_KERNEL_GEMM_F16 = 0, 1, 2
+ISC_KERNEL_ATTENTION_PROBE = 3
 
 ISC_OK = 0
 ISC_ERR_INVALID_ARG = -1
@@ -169,6 +171,10 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
         c_int,
         [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p],
     ),
+    "isc_gemm_f16_act": (
+        c_int,
+        [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p],
+    ),
     "isc_gemm_f16_scaled": (
         c_int,
         [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
@@ -184,6 +190,8 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "isc_attention_f16_self_stream": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "isc_attention_stream_geometry": (c_int, [POINTER(c_int), POINTER(c_int)]),
     "isc_attention_f16_causal": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "isc_attention_f16_probe": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "isc_vit_assemble_plain": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "isc_text_embed": (
         c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     ),

@@ -54,7 +54,8 @@ constexpr int NA = 4, NB = 4;   // LDS-DMA instructions per thread per K step an
 // EPI_F32_SCALED: EPI_F32 with a per-feature float32 scale between the bias and the residual (LayerScale,
 // isc_gemm_f16_scaled): out = residual + scale[n] * (a . w^T + bias[n])
 // EPI_F16_QGELU: EPI_F16_GELU with isc_quick_gelu (ISC_ACT_QUICK_GELU) in place of the erf form
-enum { EPI_F16 = 0, EPI_F16_GELU = 1, EPI_F32 = 2, EPI_F32_SCALED = 3, EPI_F16_QGELU = 4 };
+// EPI_F16_TGELU: the same with isc_gelu_tanh (ISC_ACT_GELU_TANH)
+enum { EPI_F16 = 0, EPI_F16_GELU = 1, EPI_F32 = 2, EPI_F32_SCALED = 3, EPI_F16_QGELU = 4, EPI_F16_TGELU = 5 };
 constexpr bool epi_f32(int epi) { return epi == EPI_F32 || epi == EPI_F32_SCALED; }
 
 struct StreamGemmParams {
@@ -267,6 +268,11 @@ __global__ __launch_bounds__(GTHREADS) void k_gemm_f16_stream(const StreamGemmPa
             for (int n = 0; n < 4; ++n)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) c[n][r] = isc_quick_gelu(c[n][r]);
+        } else if constexpr (EPI == EPI_F16_TGELU) {
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) c[n][r] = isc_gelu_tanh(c[n][r]);
         }
         if constexpr (DBG == 1 || DBG == 3) {
             if (c[0][0] + c[1][1] + c[2][2] + c[3][3] == 123.456f) reinterpret_cast<float*>(p.out)[0] = 1.f;
@@ -507,7 +513,7 @@ static constexpr int gemm_seg_tiles() { return 0; }
 
 // Called by isc_gemm_f16 for packed operands with N a multiple of 256.  epi: 0 = fp16 out, 1 = fp16 out with GELU,
 // 2 = float32 out (+ optional float32 residual), 3 = 2 with `scale` (float32 [N]) applied before the residual, 4 = fp16
-// out with QuickGELU.
+// out with QuickGELU, 5 = fp16 out with the tanh GELU.
 int isc_gemm_f16_stream_launch(const void* a, long long M, int K, const void* w, int N, const float* bias,
                                const float* scale, const float* residual, int epi, void* out, int out_packed,
                                hipStream_t stream) {
@@ -549,6 +555,8 @@ int isc_gemm_f16_stream_launch(const void* a, long long M, int K, const void* w,
             hipLaunchKernelGGL((k_gemm_f16_stream<EPI_F32_SCALED, DBG_, SPLIT_>), grid, block, 0, stream, p);           \
         else if (epi == EPI_F16_QGELU)                                                                                  \
             hipLaunchKernelGGL((k_gemm_f16_stream<EPI_F16_QGELU, DBG_, SPLIT_>), grid, block, 0, stream, p);            \
+        else if (epi == EPI_F16_TGELU)                                                                                  \
+            hipLaunchKernelGGL((k_gemm_f16_stream<EPI_F16_TGELU, DBG_, SPLIT_>), grid, block, 0, stream, p);            \
         else hipLaunchKernelGGL((k_gemm_f16_stream<EPI_F32, DBG_, SPLIT_>), grid, block, 0, stream, p);                 \
     } while (0)
 #ifdef ISC_ABLATION

@@ -55,6 +55,15 @@ __device__ __forceinline__ float isc_quick_gelu(float v) {
     return v * __frcp_rn(1.f + e);
 }
 
+// ISC_ACT_GELU_TANH, 0.5 v (1 + tanh(u)) with u = sqrt(2 / pi) (v + 0.044715 v^3), as v * sigmoid(2 u) in the form
+// include/imagescry_hip.h states: a square, one fma, two products, v_exp_f32, one addition, a reciprocal, one product.
+// v^2 overflows to +inf for |v| > 1.8e19 and exp2 saturates long before that (|v| > 11): the result is -0 or v.
+__device__ __forceinline__ float isc_gelu_tanh(float v) {
+    const float w = v * fmaf(v * v, 0.044715f, 1.f);                   // v + 0.044715 v^3
+    const float e = __builtin_amdgcn_exp2f(w * -2.3022081851959229f);  // exp(-2 u)
+    return v * __frcp_rn(1.f + e);
+}
+
 // ---- wave-level reductions (64 lanes) ---------------------------------------------------------
 __device__ __forceinline__ float isc_wave_sum(float v) {
 #pragma unroll

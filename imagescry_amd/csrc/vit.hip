@@ -98,8 +98,9 @@ __device__ __forceinline__ bool gemm_tile(const GemmParams& p, long long& m0, in
 // DBG (ISC_GEMM_DEBUG, bring-up only, wrong results): 1 = no DMA after the prologue, 2 = no fragment reads, 3 = no MFMAs,
 // 4 = no epilogue (nothing stored).
 // SCALED (isc_gemm_f16_scaled, LayerScale): out = residual + scale[n] * (product + bias[n]), float32 out, no activation.
-// QGELU (ISC_ACT_QUICK_GELU): isc_quick_gelu in place of the run-time choice between no activation and GELU.
-template <int DBG, bool SCALED = false, bool QGELU = false>
+// FIXED_ACT (ISC_ACT_QUICK_GELU, ISC_ACT_GELU_TANH): isc_quick_gelu / isc_gelu_tanh in place of the run-time choice between
+// no activation and GELU.
+template <int DBG, bool SCALED = false, int FIXED_ACT = ISC_ACT_NONE>
 __global__ __launch_bounds__(256, 2) void k_gemm_f16_dma(const GemmParams p) {
     constexpr int STAGE = 32768;  // [weights 128 rows | activations 128 rows] x 128 B
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * STAGE];
@@ -262,9 +263,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16_dma(const GemmParams p) {
         for (int mi = 0; mi < 4; ++mi) {
             v[mi] = acc[mi][ni] + bias[mi];
             if constexpr (SCALED) v[mi] *= scale[mi];
-            if constexpr (QGELU) {
+            if constexpr (FIXED_ACT == ISC_ACT_QUICK_GELU) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[mi][q] = isc_quick_gelu(v[mi][q]);
+            } else if constexpr (FIXED_ACT == ISC_ACT_GELU_TANH) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[mi][q] = isc_gelu_tanh(v[mi][q]);
             } else if (!SCALED && p.act == ISC_ACT_GELU) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[mi][q] = gelu_fast(v[mi][q]);
@@ -1052,10 +1056,13 @@ GemmParams gemm_params(const void* a, int64_t M, int K, const void* w, int N, co
 
 }  // namespace
 
-extern "C" int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int N, const float* bias,
-                            const float* residual, int act, void* out, int out_dtype, int flags, void* stream) {
+// isc_gemm_f16 and isc_gemm_f16_act: one body; `tanh_ok` admits ISC_ACT_GELU_TANH (isc_gemm_f16 answers that code as it
+// answered the value 6 before it had a name)
+static int gemm_f16_entry(const void* a, int64_t M, int K, const void* w, int N, const float* bias, const float* residual,
+                          int act, void* out, int out_dtype, int flags, void* stream, bool tanh_ok) {
     ISC_REQUIRE(a && w && out && M > 0 && K > 0 && N > 0);
-    ISC_REQUIRE(act == ISC_ACT_NONE || act == ISC_ACT_GELU || act == ISC_ACT_QUICK_GELU);
+    ISC_REQUIRE(act == ISC_ACT_NONE || act == ISC_ACT_GELU || act == ISC_ACT_QUICK_GELU ||
+                (tanh_ok && act == ISC_ACT_GELU_TANH));
     ISC_REQUIRE(out_dtype == ISC_F16 || out_dtype == ISC_F32);
     ISC_REQUIRE((flags & ~(ISC_GEMM_A_PACKED | ISC_GEMM_W_PACKED | ISC_GEMM_OUT_PACKED | ISC_GEMM_TILE_256 |
                            ISC_GEMM_TILE_128)) == 0);
@@ -1069,7 +1076,7 @@ extern "C" int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int 
     // older kernels below explicitly.
     if ((flags & ISC_GEMM_A_PACKED) && (flags & ISC_GEMM_W_PACKED) && !(flags & (ISC_GEMM_TILE_128 | ISC_GEMM_TILE_256)) &&
         N % 256 == 0 && !(out_dtype == ISC_F32 && act != ISC_ACT_NONE) && !(out_dtype == ISC_F16 && residual)) {
-        const int epi = out_dtype == ISC_F32 ? 2 : act == ISC_ACT_GELU ? 1 : act == ISC_ACT_QUICK_GELU ? 4 : 0;
+        const int epi = out_dtype == ISC_F32 ? 2 : act == ISC_ACT_GELU ? 1 : act == ISC_ACT_QUICK_GELU ? 4 : act == ISC_ACT_GELU_TANH ? 5 : 0;
         isc_timing_begin(ISC_KERNEL_GEMM_F16, isc_stream(stream));
         const int st = isc_gemm_f16_stream_launch(a, M, K, w, N, bias, nullptr, residual, epi, out,
                                                   (flags & ISC_GEMM_OUT_PACKED) != 0, isc_stream(stream));
@@ -1104,8 +1111,11 @@ extern "C" int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int 
             hipLaunchKernelGGL(k_gemm_f16_big<0>, dim3((unsigned)grid2), dim3(256), 0, s, p);
     } else if (act == ISC_ACT_QUICK_GELU) {
         // DBG = 0 in every build: the ISC_GEMM_DEBUG bring-up variants below exist for the plain instantiation only
-        hipLaunchKernelGGL((k_gemm_f16_dma<0, false, true>), dim3((unsigned)(isc_ceil_div<long long>(tiles, 8) * 8)), dim3(256), 0,
-                           s, p);
+        hipLaunchKernelGGL((k_gemm_f16_dma<0, false, ISC_ACT_QUICK_GELU>), dim3((unsigned)(isc_ceil_div<long long>(tiles, 8) * 8)),
+                           dim3(256), 0, s, p);
+    } else if (act == ISC_ACT_GELU_TANH) {
+        hipLaunchKernelGGL((k_gemm_f16_dma<0, false, ISC_ACT_GELU_TANH>), dim3((unsigned)(isc_ceil_div<long long>(tiles, 8) * 8)),
+                           dim3(256), 0, s, p);
     } else {
         const long long grid1 = isc_ceil_div<long long>(tiles, 8) * 8;
 #ifdef ISC_ABLATION
@@ -1123,6 +1133,16 @@ extern "C" int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int 
     }
     isc_timing_end(ISC_KERNEL_GEMM_F16, s);
     return isc_launch_status();
+}
+
+extern "C" int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int N, const float* bias,
+                            const float* residual, int act, void* out, int out_dtype, int flags, void* stream) {
+    return gemm_f16_entry(a, M, K, w, N, bias, residual, act, out, out_dtype, flags, stream, false);
+}
+
+extern "C" int isc_gemm_f16_act(const void* a, int64_t M, int K, const void* w, int N, const float* bias,
+                                const float* residual, int act, void* out, int out_dtype, int flags, void* stream) {
+    return gemm_f16_entry(a, M, K, w, N, bias, residual, act, out, out_dtype, flags, stream, true);
 }
 
 extern "C" int isc_gemm_f16_scaled(const void* a, int64_t M, int K, const void* w, int N, const float* bias,

@@ -15,11 +15,12 @@ from typing import Iterable
 import torch
 from torch import Tensor
 
-from imagescry_amd import _lib, clip, efficientnet, resnet50, vit
+from imagescry_amd import _lib, clip, efficientnet, resnet50, siglip, vit
 from imagescry_amd.data import EmbeddingBatch, ImageBatch
-from imagescry_amd.transforms import normalize_per_channel, resize, resize_center_crop
+from imagescry_amd.transforms import normalize_per_channel, resize, resize_antialias, resize_center_crop
 
-__all__ = ["CLIPEmbedder", "DINOv2Embedder", "EfficientNetEmbedder", "EmbeddingModule", "ResNet50Embedder", "ViTB16Embedder", "l2_normalize_channels"]
+__all__ = ["CLIPEmbedder", "DINOv2Embedder", "EfficientNetEmbedder", "EmbeddingModule", "ResNet50Embedder", "SigLIPEmbedder", "ViTB16Embedder",
+           "l2_normalize_channels"]
 
 
 def l2_normalize_channels(x: Tensor, eps: float = 1e-12) -> Tensor:
@@ -453,7 +454,15 @@ class ViTB16Embedder(EmbeddingModule):
         # the patch-token head applies F.normalize itself when predict_step asks for it (isc_vit_tokens_out)
         self._head_normalizes = output == "patches"
         sd = state_dict if state_dict is not None else vit.make_state_dict(config, seed=seed)
-        self._net = vit.prepare(sd, config)
+        self._net = self._prepare_net(sd)
+
+    # the prepared tower and its pooled `[B, embedding_dim]` features of one pass (`SigLIPEmbedder` puts its tower and
+    # its attention-pooling head here)
+    def _prepare_net(self, sd: dict[str, Tensor]):
+        return vit.prepare(sd, self.config)
+
+    def _pooled(self, x: Tensor, grid: tuple[int, int], cap: int | None) -> Tensor:
+        return vit.forward_cls(self._net, x, grid, max_patches=cap)
 
     def _move(self, device: torch.device) -> None:
         self._net = self._net.to(device)
@@ -530,7 +539,7 @@ class ViTB16Embedder(EmbeddingModule):
         out = torch.empty((b, self.embedding_dim), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             for b0 in range(0, b, step):
-                out[b0 : b0 + step] = vit.forward_cls(self._net, x[b0 : b0 + step], grid, max_patches=cap)
+                out[b0 : b0 + step] = self._pooled(x[b0 : b0 + step], grid, cap)
         return out[:, :, None, None]
 
     def predict_step(self, batch: ImageBatch) -> EmbeddingBatch:
@@ -773,3 +782,129 @@ class CLIPEmbedder(_CheckpointPreprocess, ViTB16Embedder):
             raise ValueError(f"module is on {self.device} but ids are on {ids.device}")
         q = clip.forward_text(self._text, ids, validate=validate)
         return l2_normalize_channels(q[:, :, None, None]).reshape(q.shape) if normalize and q.shape[0] else q
+
+
+class SigLIPEmbedder(ViTB16Embedder):
+    """SigLIP / SigLIP 2: images and texts in one space, scored per pair by a sigmoid.  The vision tower is the `vit`
+    encoder on a `siglip.PRESETS` configuration ("ViT-B/16", "ViT-B/16@256" / "@384" / "@512", "ViT-L/16@256" / "@384",
+    each also as "...-siglip2": no class token, tanh GELU) followed by the attention-pooling head (`siglip.forward_image`)
+    and yields `[B, D, 1, 1]` rows for an `EmbeddingBank`; `encode_text` runs the text tower on token ids and returns
+    unit-norm float32 `[Q, D]` queries for `bank.search`.  `probability` turns the cosines a search returns into the
+    pair probabilities the checkpoint was trained to give and `score_for_probability` inverts it, so that
+    `bank.search_range(q, min_score=model.score_for_probability(0.5))` is "every image that matches".
+
+    `state_dict` holds both towers, `logit_scale` and `logit_bias` under `siglip`'s names
+    (`siglip.from_transformers_state_dict`, `siglip.make_state_dict`); without it the weights are seeded random ones.
+    `preset` may also be a `siglip.SigLIPConfig`.  The So400m checkpoints (head size 72) and the NaFlex variants are
+    refused.
+
+    `grid="fixed"` squashes to `image_size`; `grid="aspect"`, `max_patches=` resample the position table bicubically
+    (without antialiasing, as `transformers` does); above 224 tokens the streaming attention kernel and
+    `vit.images_per_pass` apply as for the other embedders.  `preprocess="squash"` (the default) is this package's
+    squash-`resize` and `normalize_per_channel` with the FIXED statistics mean = std = 0.5 (times 255).
+    `preprocess="checkpoint"` is the SigLIP processor's pipeline in one kernel (`resize_antialias`): antialiased bicubic
+    squash to the input size -- no aspect preservation, no crop --, rounding to uint8 levels, then the same statistics;
+    "faithful" as `_CheckpointPreprocess` defines it (PIL's own two-pass rounding is not emulated).
+
+    `output="patches"` is refused: a dense SigLIP map (the head's value path per token) is a follow-up, not part of this
+    embedder."""
+
+    def __init__(
+        self,
+        preset: str | siglip.SigLIPConfig = "ViT-B/16",
+        *,
+        state_dict: dict[str, Tensor] | None = None,
+        seed: int = 0,
+        max_images_per_pass: int = 1024,
+        output: str = "cls",
+        grid: str = "fixed",
+        max_patches: int | None = None,
+        preprocess: str = "squash",
+    ) -> None:
+        if isinstance(preset, siglip.SigLIPConfig):
+            cfg = preset
+        elif preset in siglip.PRESETS:
+            cfg = siglip.PRESETS[preset]
+        else:
+            raise ValueError(f"preset must be one of {sorted(siglip.PRESETS)} or a siglip.SigLIPConfig, got {preset!r}")
+        if output == "patches":
+            raise ValueError('SigLIPEmbedder has no output="patches": a dense SigLIP map (the pooling head\'s value path '
+                             "per token) is a follow-up and not part of this embedder")
+        if output != "cls":
+            raise ValueError(f'SigLIPEmbedder has no output={output!r}: "cls" (the pooled embedding) only')
+        if preprocess not in ("squash", "checkpoint"):
+            raise ValueError(f'preprocess must be "squash" or "checkpoint", got {preprocess!r}')
+        if cfg.vision.dim != cfg.text.embed_dim:
+            raise ValueError(f"the towers embed into {cfg.vision.dim} and {cfg.text.embed_dim} dimensions")
+        sd = state_dict if state_dict is not None else siglip.make_state_dict(cfg, seed=seed)
+        for key in ("logit_scale", "logit_bias"):
+            if key not in sd or sd[key].numel() != 1:
+                raise ValueError(f"the state dict needs `{key}`, one float")
+        super().__init__(config=cfg.vision, state_dict=siglip.tower(sd, "visual"), seed=seed,
+                         max_images_per_pass=max_images_per_pass, output=output, grid=grid, max_patches=max_patches)
+        self.siglip_config = cfg
+        self.logit_scale, self.logit_bias = float(sd["logit_scale"]), float(sd["logit_bias"])
+        self._text = siglip.prepare_text(siglip.tower(sd, "text"), cfg.text)
+        self.preprocess_mode = preprocess
+        self.hparams.update(embed_dim=cfg.embed_dim, preprocess=preprocess)
+        if isinstance(preset, str):
+            self.hparams.update(preset=preset)
+        self._stats: dict[torch.device, tuple[Tensor, Tensor]] = {}
+
+    def _prepare_net(self, sd: dict[str, Tensor]):
+        return siglip.prepare_vision(sd, self.config)
+
+    def _pooled(self, x: Tensor, grid: tuple[int, int], cap: int | None) -> Tensor:
+        return siglip.forward_image(self._net, x, grid, max_patches=cap)
+
+    def _move(self, device: torch.device) -> None:
+        super()._move(device)
+        self._text = self._text.to(device)
+
+    def preprocess(self, images: Tensor) -> Tensor:
+        if not isinstance(images, Tensor) or images.dtype != torch.uint8:
+            raise TypeError("images must be a uint8 tensor")
+        if images.ndim != 4 or images.shape[1] != 3:
+            raise ValueError(f"images must have shape [B, 3, H, W], got {tuple(images.shape)}")
+        if images.device not in self._stats:
+            self._stats[images.device] = tuple(
+                (torch.tensor(v, device=images.device) * 255.0).reshape(1, 3, 1, 1) for v in (siglip.IMAGE_MEAN, siglip.IMAGE_STD))
+        mean, std = self._stats[images.device]
+        if self.preprocess_mode == "checkpoint":
+            if self.grid == "aspect":
+                h, w = vit.token_grid(images.shape[-2], images.shape[-1], self._patch_cap)
+                size = (h * self.config.patch_size, w * self.config.patch_size)
+            else:
+                size = (self.config.image_size, self.config.image_size)
+            return resize_antialias(images, size, channel_means=mean, channel_stds=std, quantize=True)
+        return normalize_per_channel(self._resized(images), channel_means=mean, channel_stds=std, eps=0.0)
+
+    def encode_text(self, ids: Tensor, *, normalize: bool = True, validate: bool = True,
+                    pad_to_context: bool = True) -> Tensor:
+        """int64 / int32 `[Q, T <= context]` token ids (on the module's device, or on the CPU: copied over) -> float32
+        `[Q, D]` on the device, unit norm unless `normalize=False`.  With `pad_to_context` shorter rows are right-padded
+        with `pad_token_id` to `context` before the tower runs -- the checkpoints saw only such rows and pool position
+        `context - 1`; without it the tower runs at the given T and pools `T - 1`.  `validate`
+        (`siglip.forward_text`): ids outside the vocabulary raise ValueError after one host read; without it the call
+        makes none."""
+        text = self.siglip_config.text
+        siglip.check_ids(ids, text)
+        if self.device.type != "cuda":
+            raise _lib.HipLibraryError("the module is on the CPU; call .to() first: imagescry_amd runs on HIP devices only")
+        if ids.device.type == "cpu":
+            ids = ids.to(self.device)
+        elif ids.device != self.device:
+            raise ValueError(f"module is on {self.device} but ids are on {ids.device}")
+        if pad_to_context:
+            ids = siglip.pad_ids(ids, text)
+        q = siglip.forward_text(self._text, ids, validate=validate)
+        return l2_normalize_channels(q[:, :, None, None]).reshape(q.shape) if normalize and q.shape[0] else q
+
+    def probability(self, scores):
+        """`sigmoid(exp(logit_scale) * scores + logit_bias)` of the cosines `bank.search`, `bank.scores` or
+        `similarity_map` return (`siglip.probability`)."""
+        return siglip.probability(scores, self.logit_scale, self.logit_bias)
+
+    def score_for_probability(self, p: float) -> float:
+        """The cosine at which `probability` is `p`: a `min_score` for `bank.search_range`."""
+        return siglip.score_for_probability(p, self.logit_scale, self.logit_bias)

@@ -39,8 +39,10 @@ class ViTConfig:
     layerscale: bool = False  # per-channel scale (`ls1.gamma`, `ls2.gamma`) on the attention and the MLP branch
     pos_antialias: bool = False  # resample the position table with antialiasing (the register checkpoints)
     pre_norm: bool = False  # a LayerNorm (`norm_pre.*`) between the token assembly and the first block (CLIP)
-    act: str = "gelu"  # the MLP activation: "gelu" (erf form) or "quick_gelu" (x * sigmoid(1.702 x), OpenAI CLIP)
+    # the MLP activation: "gelu" (erf form), "quick_gelu" (x * sigmoid(1.702 x), OpenAI CLIP) or "gelu_tanh" (SigLIP)
+    act: str = "gelu"
     embed_dim: int = 0  # > 0: a bias-free projection `head.weight` [embed_dim, dim] behind the class token's norm (CLIP)
+    class_token: bool = True  # False: the sequence is the patches alone and `pos_embed` has `grid ** 2` rows (SigLIP)
 
     @property
     def grid(self) -> int:
@@ -49,11 +51,12 @@ class ViTConfig:
     @property
     def num_prefix(self) -> int:
         """Token rows in front of the patches: the class token and the registers."""
-        return 1 + self.registers
+        return int(self.class_token) + self.registers
 
     @property
     def tokens(self) -> int:
-        """Sequence length on the native grid.  (`pos_embed` has `1 + grid ** 2` rows whatever `registers` is.)"""
+        """Sequence length on the native grid.  (`pos_embed` has `1 + grid ** 2` rows whatever `registers` is; without
+        a class token, `grid ** 2`.)"""
         return self.grid * self.grid + self.num_prefix
 
     @property
@@ -115,12 +118,10 @@ def make_state_dict(cfg: ViTConfig = VIT_B16, *, seed: int = 0, randomize_affine
         return torch.rand(n, generator=g) * 0.5 + 0.75 if randomize_affine else torch.ones(n)
 
     d = cfg.dim
-    sd: dict[str, Tensor] = {
-        "cls_token": tn(1, 1, d),
-        "pos_embed": tn(1, 1 + cfg.grid**2, d),
-        "patch_embed.proj.weight": tn(d, 3, cfg.patch_size, cfg.patch_size),
-        "patch_embed.proj.bias": bias(d),
-    }
+    sd: dict[str, Tensor] = {"cls_token": tn(1, 1, d)} if cfg.class_token else {}
+    sd["pos_embed"] = tn(1, int(cfg.class_token) + cfg.grid**2, d)
+    sd["patch_embed.proj.weight"] = tn(d, 3, cfg.patch_size, cfg.patch_size)
+    sd["patch_embed.proj.bias"] = bias(d)
     for i in range(cfg.depth):
         p = f"blocks.{i}"
         sd[f"{p}.norm1.weight"], sd[f"{p}.norm1.bias"] = gamma(d), bias(d)
@@ -217,8 +218,8 @@ class Block:
 @dataclass
 class PreparedViT:
     cfg: ViTConfig
-    cls_token: Tensor  # float32 [D]
-    pos_embed: Tensor  # float32 [1 + grid ** 2, D]
+    cls_token: Tensor | None  # float32 [D]; None without a class token
+    pos_embed: Tensor  # float32 [1 + grid ** 2, D]; without a class token row 0 is a zero row nothing adds to a token
     patch: Linear  # [D, cfg.patch_kdim]: columns past 3 * P * P are zero
     blocks: list[Block] = field(default_factory=list)
     norm: Norm | None = None
@@ -230,14 +231,15 @@ class PreparedViT:
     pos_cache: dict[tuple[int, int], Tensor] = field(default_factory=dict, repr=False, compare=False)
 
     def to(self, device: torch.device) -> "PreparedViT":
-        return PreparedViT(self.cfg, self.cls_token.to(device), self.pos_embed.to(device), self.patch.to(device),
+        return PreparedViT(self.cfg, None if self.cls_token is None else self.cls_token.to(device),
+                           self.pos_embed.to(device), self.patch.to(device),
                            [b.to(device) for b in self.blocks], self.norm.to(device),
                            None if self.reg_tokens is None else self.reg_tokens.to(device),
                            None if self.norm_pre is None else self.norm_pre.to(device),
                            None if self.head is None else self.head.to(device))
 
 
-ACTIVATIONS = {"gelu": _lib.ISC_ACT_GELU, "quick_gelu": _lib.ISC_ACT_QUICK_GELU}
+ACTIVATIONS = {"gelu": _lib.ISC_ACT_GELU, "quick_gelu": _lib.ISC_ACT_QUICK_GELU, "gelu_tanh": _lib.ISC_ACT_GELU_TANH}
 
 
 def prepare_linear(sd: dict[str, Tensor], name: str, pad_to: int = 0, bias: bool = True) -> Linear:
@@ -267,7 +269,9 @@ def prepare(sd: dict[str, Tensor], cfg: ViTConfig = VIT_B16) -> PreparedViT:
     steps of 64 (`cfg.patch_kdim`: 588 -> 640 for a patch size of 14).  LayerScale stays a float32 vector for the GEMM
     epilogue: trained values go down to 1e-5, and folded into the weights they would land in fp16 subnormals.
     `register_tokens` may be spelled `reg_token` (timm); `mask_token` is ignored.  `cfg.pre_norm` asks for `norm_pre.*`,
-    `cfg.embed_dim` for a `head.weight` of shape `[embed_dim, dim]` (no bias)."""
+    `cfg.embed_dim` for a `head.weight` of shape `[embed_dim, dim]` (no bias).  Without `cfg.class_token` there is no
+    `cls_token` key and `pos_embed` is `(1, grid ** 2, dim)`; it is stored behind one zero row, the shape
+    `isc_vit_pos_resample` takes (that row is copied, never added to a token)."""
     d = cfg.dim
     if cfg.dim % 64 or cfg.mlp_dim % 64 or cfg.dim // cfg.heads != 64:
         raise ValueError("this build supports head size 64 and GEMM inner dimensions that are multiples of 64")
@@ -277,9 +281,12 @@ def prepare(sd: dict[str, Tensor], cfg: ViTConfig = VIT_B16) -> PreparedViT:
         raise ValueError(f"act must be one of {sorted(ACTIVATIONS)}, got {cfg.act!r}")
     if cfg.embed_dim < 0 or cfg.embed_dim % 4:
         raise ValueError(f"embed_dim must be a non-negative multiple of 4, got {cfg.embed_dim}")
+    if not cfg.class_token and (cfg.registers or cfg.embed_dim):
+        raise ValueError("register tokens and a projection of the class token need a class token")
     rows = 1 + cfg.grid**2
-    if tuple(sd["pos_embed"].shape) != (1, rows, d):
-        raise ValueError(f"pos_embed has shape {tuple(sd['pos_embed'].shape)}, expected (1, {rows}, {d})")
+    own = rows if cfg.class_token else rows - 1  # rows of the checkpoint's table
+    if tuple(sd["pos_embed"].shape) != (1, own, d):
+        raise ValueError(f"pos_embed has shape {tuple(sd['pos_embed'].shape)}, expected (1, {own}, {d})")
 
     def need(key: str, what: str) -> Tensor:
         if key not in sd:
@@ -289,9 +296,11 @@ def prepare(sd: dict[str, Tensor], cfg: ViTConfig = VIT_B16) -> PreparedViT:
     def scale(key: str) -> Tensor | None:
         return need(key, "LayerScale").reshape(d).float().contiguous() if cfg.layerscale else None
 
-    net = PreparedViT(cfg, sd["cls_token"].reshape(d).float().contiguous(),
-                      sd["pos_embed"].reshape(rows, d).float().contiguous(),
-                      prepare_linear(sd, "patch_embed.proj", cfg.patch_kdim))
+    pos = sd["pos_embed"].reshape(own, d).float()
+    if not cfg.class_token:
+        pos = torch.cat([torch.zeros((1, d), dtype=torch.float32, device=pos.device), pos])
+    net = PreparedViT(cfg, sd["cls_token"].reshape(d).float().contiguous() if cfg.class_token else None,
+                      pos.contiguous(), prepare_linear(sd, "patch_embed.proj", cfg.patch_kdim))
     if cfg.registers:
         key = "register_tokens" if "register_tokens" in sd or "reg_token" not in sd else "reg_token"
         reg = need(key, f"{cfg.registers} register tokens")
@@ -362,10 +371,12 @@ def _gemm(a: Tensor, m: int, lin: Linear, out: Tensor, *, act: int = _lib.ISC_AC
                                              out.data_ptr(), _lib.ISC_F16 if f16 else _lib.ISC_F32, flags, stream)
         _lib.check(st, "isc_gemm_f16_scaled")
         return out
-    st = _lib.load().isc_gemm_f16(a.data_ptr(), m, lin.in_features, lin.weight.data_ptr(), lin.out_features,
-                                  _lib.ptr(lin.bias), _lib.ptr(residual), act, out.data_ptr(),
-                                  _lib.ISC_F16 if f16 else _lib.ISC_F32, flags, stream)
-    _lib.check(st, "isc_gemm_f16")
+    # the tanh GELU goes through the entry that admits it; every other call is isc_gemm_f16, as before
+    name = "isc_gemm_f16_act" if act == _lib.ISC_ACT_GELU_TANH else "isc_gemm_f16"
+    st = getattr(_lib.load(), name)(a.data_ptr(), m, lin.in_features, lin.weight.data_ptr(), lin.out_features,
+                                    _lib.ptr(lin.bias), _lib.ptr(residual), act, out.data_ptr(),
+                                    _lib.ISC_F16 if f16 else _lib.ISC_F32, flags, stream)
+    _lib.check(st, name)
     return out
 
 
@@ -444,7 +455,10 @@ def _encode(net: PreparedViT, x: Tensor, grid: tuple[int, int], blocks: list[Blo
     del patches
     xa = torch.empty((m, d), dtype=f32, device=dev)  # residual stream (ping)
     xb = torch.empty((m, d), dtype=f32, device=dev)  # residual stream (pong)
-    if cfg.registers:
+    if not cfg.class_token:  # the table's rows behind the leading one (D floats: the alignment holds)
+        _lib.check(lib.isc_vit_assemble_plain(pe.data_ptr(), pos.data_ptr() + 4 * d, b, npatch, d, xa.data_ptr(), stream),
+                   "isc_vit_assemble_plain")
+    elif cfg.registers:
         _lib.check(lib.isc_vit_assemble_reg(pe.data_ptr(), net.cls_token.data_ptr(), net.reg_tokens.data_ptr(),
                                             pos.data_ptr(), b, t, cfg.registers, d, xa.data_ptr(), stream),
                    "isc_vit_assemble_reg")
@@ -503,12 +517,19 @@ def _check_grid(net: PreparedViT, x: Tensor, grid: tuple[int, int], max_patches:
         raise ValueError(f"x must have shape [B, 3, {h * p}, {w * p}] for a {h} x {w} grid, got {tuple(x.shape)}")
 
 
+def _need_class_token(cfg: ViTConfig, what: str) -> None:
+    if not cfg.class_token:
+        raise ValueError(f"{what} needs a tower with a class token; one without is pooled by its own head "
+                         "(siglip.forward_image)")
+
+
 def forward_cls(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = None,
                 max_patches: int | None = None) -> Tensor:
     """float32 `[B, 3, P h, P w]` (already preprocessed; `grid = (h, w)`, the native square grid by default) on a HIP
     device -> float32 `[B, D]` class-token features.  `max_patches`: the most patches `grid` may hold, the native
     grid's count by default."""
     cfg = net.cfg
+    _need_class_token(cfg, "forward_cls")
     grid = (cfg.grid, cfg.grid) if grid is None else grid
     _check_grid(net, x, grid, max_patches)
     b, d, t = x.shape[0], cfg.dim, grid[0] * grid[1] + cfg.num_prefix
@@ -538,6 +559,7 @@ def forward_tokens(net: PreparedViT, x: Tensor, grid: tuple[int, int] | None = N
     contiguous `[B, D, h, w]` tensor to write into.  `max_patches`: the most patches `grid` may hold, the native grid's
     count by default."""
     cfg = net.cfg
+    _need_class_token(cfg, "forward_tokens")
     grid = (cfg.grid, cfg.grid) if grid is None else grid
     _check_grid(net, x, grid, max_patches)
     h, w = grid
@@ -587,7 +609,7 @@ def forward_dense(net: PreparedViT, x: Tensor, mode: str, grid: tuple[int, int] 
     cfg = net.cfg
     if mode not in DENSE_MODES:
         raise ValueError(f"mode must be one of {DENSE_MODES}, got {mode!r}")
-    if net.head is None or cfg.registers or cfg.layerscale or not net.blocks:
+    if net.head is None or cfg.registers or cfg.layerscale or not net.blocks or not cfg.class_token:
         raise ValueError("a dense map needs a tower with a projection head (embed_dim), at least one block, no register "
                          "tokens and no LayerScale")
     if mode == "value" and (value is None or (value.out_features, value.in_features) != (cfg.dim, cfg.dim)):

@@ -60,6 +60,7 @@ extern "C" {
 #define ISC_ACT_SILU 3    /* x * sigmoid(x) */
 #define ISC_ACT_SIGMOID 4
 #define ISC_ACT_QUICK_GELU 5 /* x * sigmoid(1.702 x), the OpenAI CLIP checkpoints' activation (isc_gemm_f16 only) */
+#define ISC_ACT_GELU_TANH 6 /* 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))), SigLIP's `gelu_pytorch_tanh` (isc_gemm_f16_act only) */
 #define ISC_ACT_RESIDUAL_AFTER 0x100 /* OR into `act`: out = act(conv + bias) + residual (default: residual inside act) */
 
 int isc_abi_version(void);
@@ -80,7 +81,8 @@ int isc_device_info(int* num_cus, int* lds_bytes_per_cu, char* arch_name, int ar
 #define ISC_KERNEL_DOTS_FILTER 0 /* k_dots_filter: the MFMA score + threshold-filter pass of isc_cosine_topk */
 #define ISC_KERNEL_CONV 1        /* k_conv_f32 / k_conv_halo_f32: the implicit-GEMM convolutions of isc_conv2d_nhwc */
 #define ISC_KERNEL_GEMM_F16 2    /* k_gemm_f16: the fp16 GEMM of isc_gemm_f16 (transformer encoder) */
-#define ISC_KERNEL_COUNT 3
+#define ISC_KERNEL_ATTENTION_PROBE 3 /* k_attention_probe: the one-query attention of isc_attention_f16_probe */
+#define ISC_KERNEL_COUNT 4
 int isc_timing_enable(int enable);
 int isc_timing_read(int kernel_id, double* total_ms, int* launches);
 
@@ -386,10 +388,26 @@ int isc_pool_linear_l2norm(const float* x, int B, int H, int W, int C, const flo
  *                       hardware exp2, one addition, a reciprocal, one product.  For large |v| exp2 saturates to +inf
  *                       or 0 and the activation is 0 or v; no finite v gives NaN.  (The zero is -0 out of the
  *                       activation; the residual addition, which adds 0 when there is none, may make it +0.)
- * Both activations run on the streaming and on the 128 x 128-tile kernel, with fp16 and with float32 output;
+ *   ISC_ACT_GELU_TANH   (isc_gemm_f16_act only, below)  0.5 v (1 + tanh(u)), u = sqrt(2 / pi) (v + 0.044715 v^3), which
+ *                       is v * sigmoid(2 u); exactly
+ *                           w = v * fma(v * v, a, 1)      a = fl(0.044715) = 0.044714998f
+ *                           out = v * rcp(1 + exp2(w * k))  k = fl(-2 log2(e) sqrt(2 / pi)) = -2.3022082f
+ *                       -- sqrt(2 / pi) and -2 log2(e) are multiplied in exact arithmetic and rounded ONCE, into k; a
+ *                       square, one fma, two products, the hardware exp2, one addition, a reciprocal, one product.  For
+ *                       large |v| (|v| > 11) exp2 saturates to +inf or 0 and the activation is 0 (-0, as above) or v;
+ *                       v * v may overflow to +inf, which w and exp2 carry to the same two results; no finite v gives
+ *                       NaN.
+ * The activations run on the streaming and on the 128 x 128-tile kernel, with fp16 and with float32 output;
  * ISC_GEMM_TILE_256 has no activation epilogue (ISC_ERR_UNSUPPORTED).  Any other `act`: ISC_ERR_INVALID_ARG. */
 int isc_gemm_f16(const void* a, int64_t M, int K, const void* w, int N, const float* bias, const float* residual,
                  int act, void* out, int out_dtype, int flags, void* stream);
+
+/* isc_gemm_f16 with ISC_ACT_GELU_TANH admitted as well: the same operands, checks in the same order, kernels, dispatch
+ * and results for every `act` isc_gemm_f16 takes.  A separate entry because isc_gemm_f16 has always answered act == 6
+ * with ISC_ERR_INVALID_ARG and a caller that probes its activation table must see no change; it still does, and so does
+ * isc_gemm_f16_scaled. */
+int isc_gemm_f16_act(const void* a, int64_t M, int K, const void* w, int N, const float* bias, const float* residual,
+                     int act, void* out, int out_dtype, int flags, void* stream);
 
 /* LayerScale in the GEMM epilogue: out[M,N] = residual[M,N] + scale[N] * (a[M,K] . w[N,K]^T + bias[N]).  `scale`
  * float32 [N], 16-byte aligned, never NULL (ISC_ERR_INVALID_ARG); it multiplies in float32, after the bias and before
@@ -447,6 +465,29 @@ int isc_attention_stream_geometry(int* query_block, int* key_chunk);
  * else ISC_ERR_UNSUPPORTED.  No workspace, no host synchronisation, capturable. */
 int isc_attention_f16_causal(const void* qkv, int B, int T, int heads, int head_dim, void* out, int packed, void* stream);
 
+/* ONE query for a whole batch: the attention-pooling ("MAP") head of a SigLIP image tower.  Per (image b, head h)
+ *     out[b][h] = softmax_t(q[h] . k[b][t][h] / 8) v[b][t][h]          over the image's T tokens.
+ * kv fp16 [B * T, 2 * heads * 64]: the output of one Linear whose weight rows are [key; value], each head-major; q fp16
+ * [heads * 64], the probe already projected, the same for every image; out fp16 [B, heads * 64].  kv and out are both
+ * row-major (packed == 0) or both packed; all three pointers 16-byte aligned.  head_dim == 64 (else
+ * ISC_ERR_UNSUPPORTED), any T >= 1, B * T < 2^31.  No workspace, no host synchronisation, capturable, no atomics: the same
+ * bits on every call, and row b depends on B and on the other images in no way.  Every half of kv is read exactly once
+ * (a bandwidth kernel, no matrix cores: one query would fill one MFMA column in sixteen).  One workgroup of 256 threads
+ * per (image, head); thread (j, c) = (tid / 8, tid % 8) owns the 16-byte part c of the keys and values t = j (mod 32).
+ * The arithmetic, all float32:
+ *   - q is converted to float32 and multiplied by 1/8 (exact);
+ *   - s_t: the thread's eight products accumulated by fma in ascending dimension from 0, then the eight parts added
+ *     across lanes at distances 1, 2, 4;
+ *   - m = max_t s_t;  p_t = exp2((s_t - m) * fl(log2 e)) (hardware exp2), never rounded to fp16;
+ *   - l = sum_t p_t and acc[d] = sum_t p_t v_t[d]: per thread in ascending t (fma for acc), then across lanes (l: a
+ *     64-lane butterfly; acc: distances 8, 16, 32) and across the four waves as ((w0 + w1) + w2) + w3;
+ *   - out[d] = fp16(acc[d] / l), an IEEE division.
+ * The scores of up to 4096 keys are held in LDS between the two passes; a longer sequence runs in chunks of 4096 keys
+ * with a running maximum M and the per-thread partial l and acc multiplied by exp2((M_old - M_new) * fl(log2 e)) in front
+ * of every chunk (for T <= 4096 that factor multiplies zeros: the result is the plain two-pass softmax). */
+int isc_attention_f16_probe(const void* kv, const void* q, int B, int T, int heads, int head_dim, void* out, int packed,
+                            void* stream);
+
 /* The residual stream of a text tower: tokens[b * T + t] = table[ids[b * T + t]] + pos[t] -- one float32 addition per
  * element.  ids int64 [B, T]; table float32 [vocab, D]; pos float32 [>= T, D]; tokens float32 [B * T, D]; D % 4 == 0,
  * table / pos / tokens 16-byte aligned, ids 8-byte aligned.  An id outside [0, vocab) never reaches the table: its row is
@@ -486,6 +527,13 @@ int isc_vit_assemble(const float* patch_embed, const float* cls_token, const flo
  * when R == 0, which is isc_vit_assemble bit for bit).  R < 0 or T <= 1 + R: ISC_ERR_INVALID_ARG. */
 int isc_vit_assemble_reg(const float* patch_embed, const float* cls_token, const float* reg_tokens,
                          const float* pos_embed, int B, int T, int R, int D, float* tokens, void* stream);
+
+/* A tower WITHOUT a class token (SigLIP): tokens[b][j] = patch_embed[b * P + j] + pos_embed[j], one float32 addition per
+ * element; patch_embed float32 [B * P, D], pos_embed float32 [P, D], tokens float32 [B * P, D]; B, P, D > 0 (else
+ * ISC_ERR_INVALID_ARG), D % 4 == 0 (else ISC_ERR_UNSUPPORTED), all pointers 16-byte aligned.  The table of another token
+ * grid is rows 1 .. of isc_vit_pos_resample's output on the table behind one leading row of any content. */
+int isc_vit_assemble_plain(const float* patch_embed, const float* pos_embed, int B, int P, int D, float* tokens,
+                           void* stream);
 
 /* Position table of an h x w token grid from the g x g one: out[0] = pos_embed[0] (class token); the patch rows, seen
  * as [D, g, g], resampled to [D, h, w] by bicubic interpolation -- align_corners = False, no antialias, A = -0.75,
