@@ -13,6 +13,8 @@ Public surface (same names as the reference where the reference has them):
 * `EmbedSearchPipeline`                          -- encode -> search on two HIP streams (BASELINE config 5; new)
 * `EmbeddingBank`, `RangeResult`, `RowFilter`    -- cosine top-k and range search, optionally over a row filter and
   with per-query group exclusion (`row_groups=`, `exclude_group=`) (new; see search.py)
+* `class_scores`, `label_map`, `segment`,
+  `LabelMaps`                                    -- pixel label maps from dense patch scores (new; see segmentation.py)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/imagescry_hip.h;
 PyTorch is used for device memory, streams and `torch.distributed` only.
@@ -33,6 +35,7 @@ from imagescry_amd.embedding import (
     l2_normalize_channels,
 )
 from imagescry_amd.pipelines import EmbeddingPCAPipeline, EmbedSearchPipeline, SearchResult
+from imagescry_amd.segmentation import LabelMaps, class_scores, label_map, segment
 from imagescry_amd.search import EmbeddingBank, RangeResult, RowFilter, SearchHandle, shard_bounds
 from imagescry_amd.transforms import normalize_per_channel, resize, resize_antialias, resize_center_crop, to_4d
 
@@ -48,13 +51,17 @@ __all__ = [
     "SearchHandle",
     "SearchResult",
     "KMeans",
+    "LabelMaps",
     "PCA",
     "RangeResult",
     "RowFilter",
     "ResNet50Embedder",
     "SigLIPEmbedder",
     "ViTB16Embedder",
+    "class_scores",
     "clip",
+    "label_map",
+    "segment",
     "siglip",
     "l2_normalize_channels",
     "ImageBatch",

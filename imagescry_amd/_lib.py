@@ -352,6 +352,15 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
         [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int,
          c_int, c_float, c_void_p, c_void_p],
     ),
+    "isc_label_map": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p],
+    ),
+    "isc_label_map_geometry": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "isc_map_class_scores": (
+        c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p]
+    ),
 }
 
 _lib: ctypes.CDLL | None = None

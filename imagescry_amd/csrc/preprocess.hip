@@ -3,6 +3,7 @@
 // not for the matrix cores.  Reference arithmetic: src/imagescry/image/transforms.py:58-126 and
 // src/imagescry/models/embedding.py:74.
 #include "aa_filter.h"
+#include "bilinear_tap.h"
 #include "isc_common.h"
 
 namespace {
@@ -284,19 +285,7 @@ __global__ __launch_bounds__(256) void k_normalize_nhwc4(const T* __restrict__ x
     }
 }
 
-// torch upsample_bilinear2d (align_corners=False): src = scale * (dst + 0.5) - 0.5, clamped at 0;
-// i0 = min(int(src), in - 1); i1 = min(i0 + 1, in - 1); l1 = clamp(src - i0, 0, 1); l0 = 1 - l1.
-__device__ __forceinline__ void bilinear_tap(int dst, float scale, int in_size, int& i0, int& i1, float& l0, float& l1) {
-    // one rounding, written out: the two-rounding form misses torch by 0.017 at 3001 -> 1000 (an ulp of 1500 in src), and which
-    // of the two `scale * (dst + 0.5f) - 0.5f` compiles to is the contraction default's choice
-    float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
-    if (src < 0.f) src = 0.f;
-    i0 = min((int)src, in_size - 1);
-    i1 = min(i0 + 1, in_size - 1);
-    l1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
-    l0 = 1.f - l1;
-}
-
+// bilinear_tap (bilinear_tap.h): torch's align_corners=False source index with one rounding.
 template <typename T>
 __global__ __launch_bounds__(256) void k_resize_bilinear(const T* __restrict__ x, int H1, int W1, int H2, int W2,
                                                          float scale_h, float scale_w, float* __restrict__ y) {

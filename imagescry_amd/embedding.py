@@ -15,7 +15,7 @@ from typing import Iterable
 import torch
 from torch import Tensor
 
-from imagescry_amd import _lib, clip, efficientnet, resnet50, siglip, vit
+from imagescry_amd import _lib, clip, efficientnet, resnet50, segmentation, siglip, vit
 from imagescry_amd.data import EmbeddingBatch, ImageBatch
 from imagescry_amd.transforms import normalize_per_channel, resize, resize_antialias, resize_center_crop
 
@@ -782,6 +782,22 @@ class CLIPEmbedder(_CheckpointPreprocess, ViTB16Embedder):
             raise ValueError(f"module is on {self.device} but ids are on {ids.device}")
         q = clip.forward_text(self._text, ids, validate=validate)
         return l2_normalize_channels(q[:, :, None, None]).reshape(q.shape) if normalize and q.shape[0] else q
+
+    def segment(self, batch: ImageBatch, text_embeddings: Tensor, *, class_of: "Tensor | list[int] | None" = None,
+                size: tuple[int, int] | None = None, **kw: object) -> segmentation.LabelMaps:
+        """Open-vocabulary segmentation: `predict_step(batch)`, then `segmentation.segment` of its patch map against
+        `text_embeddings` (float32 `[C, E]`, `encode_text`) at `size`, by default the batch's own `(H, W)`; `class_of`,
+        `min_score`, `return_*`: `segmentation.label_map`.  `LabelMaps.indices` carries `batch.indices`.  Needs
+        `output="patches"` with a `dense` mode (only that map lives in the text tower's space), and refuses
+        `preprocess="checkpoint"`, whose map covers the centre crop and not the image."""
+        if self.output != "patches" or self.dense is None:
+            raise ValueError('segment needs the dense patch map: build the CLIPEmbedder with output="patches" and dense=')
+        if self.preprocess_mode == "checkpoint":
+            raise ValueError('segment refuses preprocess="checkpoint": its patch map covers the centre crop only, so it '
+                             "does not line up with the image's pixels; use preprocess=\"squash\"")
+        if size is None:
+            size = (int(batch.images.shape[2]), int(batch.images.shape[3]))
+        return segmentation.segment(self.predict_step(batch), text_embeddings, size, class_of=class_of, **kw)
 
 
 class SigLIPEmbedder(ViTB16Embedder):

@@ -39,7 +39,7 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
-from imagescry_amd import _lib
+from imagescry_amd import _lib, segmentation
 from imagescry_amd.data import EmbeddingBatch
 
 __all__ = ["EmbeddingBank", "RangeResult", "RowFilter", "SearchHandle", "shard_bounds"]
@@ -1737,6 +1737,19 @@ class EmbeddingBank:
                          device=self.device)
         out[:, h, w] = self.scores(q, cells + self.index_base)
         return out
+
+    def label_map(self, vectors: Tensor, image_id: int, size: tuple[int, int], **kw: object) -> segmentation.LabelMaps:
+        """Pixel labels of one stored image: `similarity_map(vectors, image_id)` upsampled to `size = (H, W)` with the arg
+        max per pixel, `segmentation.label_map(similarity_map(...)[None], size, layout="bchw", **kw)` with B = 1 (`kw`:
+        `class_of`, `min_score`, `return_*`).  A cell the bank does not hold, or has removed, scores -inf for every vector
+        and goes through the blend as it is: a pixel with such a cell among its four scores -inf (a nonzero weight) or
+        NaN (a zero weight) for every vector.  The pixels around a missing cell therefore come out `UNLABELED` under any
+        finite `min_score` (pass one, e.g. -1, to mask them); with the threshold off only the NaN ones do, and the -inf
+        ones carry the first vector's class with score -inf.  A sharded bank refuses the call, as it refuses
+        `similarity_map`."""
+        if "layout" in kw:
+            raise TypeError("label_map takes no layout: similarity_map is [Q, H, W]")
+        return segmentation.label_map(self.similarity_map(vectors, image_id)[None], size, layout="bchw", **kw)
 
     def search_rows(self, indices: "Tensor | Sequence[int]", k: int = 10, *, exclude_self: bool = True,
                     mask: "RowFilter | Tensor | None" = None,

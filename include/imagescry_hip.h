@@ -961,6 +961,61 @@ int isc_bank_project(const void* bank, int dtype, int64_t N, int D, const float*
                      const uint32_t* row_mask, float* out_rows, int64_t ldo, void* out_packed, int out_dtype, int normalize,
                      float eps, float* norm_bound, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Pixel label maps from dense patch scores
+ * ------------------------------------------------------------------------------------------- */
+
+/* Class scores per cell -> label, score and margin per PIXEL: the bilinear upsampling (align_corners=False) of every
+ * prompt's score map to H x W and the arg max over the prompts in one pass; the [B, C, H, W] tensor of
+ * `interpolate(scores, (H, W), mode="bilinear").max(1)` is never written.
+ *   scores     float [B, h, w, C]: cell-major, the prompts of one cell contiguous, leading dimension ldc >= C
+ *   class_of   int32 [C] or NULL: the class of every prompt, values in [0, 254] (NOT checked here: it would cost a
+ *              host read); several prompts may stand for one class.  NULL: class = prompt (then C <= 255 is the
+ *              caller's business too)
+ *   min_score  pixels whose best score is below it are unlabeled; -INFINITY switches the threshold off
+ *   labels     uint8 [B, H, W] or NULL, 255 = unlabeled          best     float [B, H, W] or NULL
+ *   margin     float [B, H, W] or NULL                           counts   int32 [B, 256] or NULL
+ * At least one of labels and best is required.  For the output pixel (y, x), as a fixed sequence of float32 operations:
+ *   1  (y0, y1, ly0, ly1) = tap(y, (float)h / (float)H, h) and (x0, x1, lx0, lx1) = tap(x, (float)w / (float)W, w), the
+ *      source index of isc_resize_bilinear: src = max(fmaf(scale, (float)dst + 0.5f, -0.5f), 0), i0 = min((int)src,
+ *      in - 1), i1 = min(i0 + 1, in - 1), l1 = min(max(src - (float)i0, 0), 1), l0 = 1 - l1;
+ *   2  w00 = ly0 * lx0, w01 = ly0 * lx1, w10 = ly1 * lx0, w11 = ly1 * lx1, each product rounded;
+ *   3  for every prompt c, ascending: v_c = fmaf(w11, s[y1][x1][c], fmaf(w10, s[y1][x0][c], fmaf(w01, s[y0][x1][c],
+ *      w00 * s[y0][x0][c]))); non-finite scores give what this arithmetic gives;
+ *   4  c* = the first prompt in the order of the searches: v descending, NaN last, ties to the lower c;
+ *      label = class_of[c*], best = v_c*;
+ *   5  margin = best - max{ v_c : class_of[c] != label, v_c not NaN }, one subtraction; +INFINITY when there is no such
+ *      prompt;
+ *   6  the pixel is unlabeled (labels = 255) iff best is NaN or best < min_score; best and margin are written as
+ *      computed either way;
+ *   7  counts[b][label] += 1, the unlabeled pixels at index 255.  The call zeroes counts itself (a small launch ahead
+ *      of the kernel, so a replayed graph starts from zero too); a workgroup adds its histogram with one integer atomic per
+ *      label present, and integer sums do not depend on the order: counts is deterministic.
+ * A pixel's bits depend on its own four cells only: not on B, the image's place in the batch, ldc or the tiling.
+ * Limits: 1 <= C <= 1024 (ISC_ERR_UNSUPPORTED above); h, w, H, W >= 1; h * w < 2^31 and H * W < 2^31; B <= 65535 and
+ * H <= 262140 (the grid; ISC_ERR_UNSUPPORTED); scores 16-byte aligned, best / margin / counts / class_of 4-byte
+ * (ISC_ERR_ALIGNMENT); a NaN min_score is ISC_ERR_INVALID_ARG.  Everything is checked before anything is launched.
+ * B == 0 returns ISC_OK without a launch.  No workspace, no host synchronisation, capturable. */
+int isc_label_map(const float* scores, int B, int h, int w, int C, int64_t ldc, const int32_t* class_of, int H, int W,
+                  float min_score, uint8_t* labels, float* best, float* margin, int32_t* counts, void* stream);
+
+/* The constants of isc_label_map's kernel: a workgroup owns tile_w x tile_h output pixels and walks the prompts in
+ * chunks of at most prompt_chunk -- the sizes at which its code paths change (host pointers). */
+int isc_label_map_geometry(int* tile_w, int* tile_h, int* prompt_chunk);
+
+/* The scores isc_label_map reads, straight from an embedding map (no transposed copy):
+ *   maps      float [B, E, S], the NCHW map with S = h * w        vectors   float [C, E], leading dimension ldv >= E
+ *   out       float [B, S, C], leading dimension ldc >= C
+ *   out[b][s][c] = (float)(acc / denom): acc the float64 chain acc = fma((double)maps[b][e][s], (double)vectors[c][e],
+ *   acc) over e ascending from 0, n the same chain of vectors[c][e]^2, denom = max(sqrt(n), 1e-12); square root and
+ *   division correctly rounded in float64, one rounding to float32.  A zero vector scores 0.
+ * The cell is taken as stored (a `predict_step` map is unit norm already), as the searches take the bank's rows.  These
+ * are NOT the bits of isc_cosine_scores, whose chain runs in another order.  One launch, any E >= 1 and C >= 1,
+ * B <= 65535 and C <= 2097120 (the grid; ISC_ERR_UNSUPPORTED); all pointers 4-byte aligned.  B == 0 returns ISC_OK
+ * without a launch.  No workspace, no host synchronisation, capturable. */
+int isc_map_class_scores(const float* maps, int B, int E, int S, const float* vectors, int C, int64_t ldv, float* out,
+                         int64_t ldc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
