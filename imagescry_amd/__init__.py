@@ -15,6 +15,8 @@ Public surface (same names as the reference where the reference has them):
   with per-query group exclusion (`row_groups=`, `exclude_group=`) (new; see search.py)
 * `class_scores`, `label_map`, `segment`,
   `LabelMaps`                                    -- pixel label maps from dense patch scores (new; see segmentation.py)
+* `window_grid`, `crop_windows`,
+  `label_map_windows`, `segment_windows`         -- sliding-window inference: overlapping windows averaged per pixel (new)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/imagescry_hip.h;
 PyTorch is used for device memory, streams and `torch.distributed` only.
@@ -35,7 +37,16 @@ from imagescry_amd.embedding import (
     l2_normalize_channels,
 )
 from imagescry_amd.pipelines import EmbeddingPCAPipeline, EmbedSearchPipeline, SearchResult
-from imagescry_amd.segmentation import LabelMaps, class_scores, label_map, segment
+from imagescry_amd.segmentation import (
+    LabelMaps,
+    class_scores,
+    crop_windows,
+    label_map,
+    label_map_windows,
+    segment,
+    segment_windows,
+    window_grid,
+)
 from imagescry_amd.search import EmbeddingBank, RangeResult, RowFilter, SearchHandle, shard_bounds
 from imagescry_amd.transforms import normalize_per_channel, resize, resize_antialias, resize_center_crop, to_4d
 
@@ -60,9 +71,13 @@ __all__ = [
     "ViTB16Embedder",
     "class_scores",
     "clip",
+    "crop_windows",
     "label_map",
+    "label_map_windows",
     "segment",
+    "segment_windows",
     "siglip",
+    "window_grid",
     "l2_normalize_channels",
     "ImageBatch",
     "ImageTensorDataset",

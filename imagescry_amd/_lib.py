@@ -361,6 +361,14 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "isc_map_class_scores": (
         c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p]
     ),
+    "isc_label_map_windows": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "isc_label_map_window_grid": (
+        c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]
+    ),
 }
 
 _lib: ctypes.CDLL | None = None

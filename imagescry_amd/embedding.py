@@ -784,20 +784,38 @@ class CLIPEmbedder(_CheckpointPreprocess, ViTB16Embedder):
         return l2_normalize_channels(q[:, :, None, None]).reshape(q.shape) if normalize and q.shape[0] else q
 
     def segment(self, batch: ImageBatch, text_embeddings: Tensor, *, class_of: "Tensor | list[int] | None" = None,
-                size: tuple[int, int] | None = None, **kw: object) -> segmentation.LabelMaps:
+                size: tuple[int, int] | None = None, window: "int | tuple[int, int] | None" = None,
+                stride: "int | tuple[int, int] | None" = None, **kw: object) -> segmentation.LabelMaps:
         """Open-vocabulary segmentation: `predict_step(batch)`, then `segmentation.segment` of its patch map against
         `text_embeddings` (float32 `[C, E]`, `encode_text`) at `size`, by default the batch's own `(H, W)`; `class_of`,
         `min_score`, `return_*`: `segmentation.label_map`.  `LabelMaps.indices` carries `batch.indices`.  Needs
         `output="patches"` with a `dense` mode (only that map lives in the text tower's space), and refuses
-        `preprocess="checkpoint"`, whose map covers the centre crop and not the image."""
+        `preprocess="checkpoint"`, whose map covers the centre crop and not the image.
+
+        `window=` (an int or `(win_h, win_w)`, clamped to the image) switches to sliding-window inference, the way the
+        dense CLIP methods are evaluated: `segmentation.crop_windows` of the images at `stride` (default: half the window,
+        rounded up), `predict_step` of the crops -- each squashed to what the tower takes, `max_images_per_pass` splitting
+        the larger batch -- and `segmentation.segment_windows` at the batch's own `(H, W)`, the windows that overlap on
+        a pixel averaged there.  Another `size` is refused with a window."""
         if self.output != "patches" or self.dense is None:
             raise ValueError('segment needs the dense patch map: build the CLIPEmbedder with output="patches" and dense=')
         if self.preprocess_mode == "checkpoint":
             raise ValueError('segment refuses preprocess="checkpoint": its patch map covers the centre crop only, so it '
                              "does not line up with the image's pixels; use preprocess=\"squash\"")
-        if size is None:
-            size = (int(batch.images.shape[2]), int(batch.images.shape[3]))
-        return segmentation.segment(self.predict_step(batch), text_embeddings, size, class_of=class_of, **kw)
+        own = (int(batch.images.shape[2]), int(batch.images.shape[3]))
+        if window is None:
+            if stride is not None:
+                raise ValueError("stride needs window=")
+            return segmentation.segment(self.predict_step(batch), text_embeddings, own if size is None else size,
+                                        class_of=class_of, **kw)
+        if size is not None and tuple(size) != own:
+            raise ValueError(f"segment with window= labels the batch's own {own} pixels; resizing the averaged scores to "
+                             f"size={tuple(size)} is not supported")
+        crops = segmentation.crop_windows(batch.images, window, stride)
+        crops = ImageBatch(indices=batch.indices.repeat_interleave(crops.shape[0] // max(len(batch), 1)), images=crops)
+        out = segmentation.segment_windows(self.predict_step(crops), text_embeddings, own, window, stride,
+                                           class_of=class_of, **kw)
+        return segmentation.LabelMaps(out.labels, out.scores, out.margins, out.counts, batch.indices)
 
 
 class SigLIPEmbedder(ViTB16Embedder):

@@ -7,6 +7,12 @@ the `[B, C, H, W]` tensor of `F.interpolate(scores, size).max(1)`, and `segment`
 arithmetic is fixed (include/imagescry_hip.h): the answers are deterministic, bit for bit reproducible and capturable
 into a graph.  The producers are a dense CLIP map with text embeddings (`CLIPEmbedder.segment`), a DINOv2 map with
 `KMeans` centroids, and `EmbeddingBank.similarity_map` (`EmbeddingBank.label_map`).
+
+Sliding-window inference (what MaskCLIP, SCLIP, ClearCLIP and NACLIP evaluate with): `window_grid` places windows of the
+checkpoint's own resolution over a larger image, `crop_windows` cuts them out, and `label_map_windows` upsamples every
+window's scores to its pixels, averages the windows that overlap on a pixel and takes the arg max, again in one kernel
+(`isc_label_map_windows`); `segment_windows` is `class_scores` + `label_map_windows`, `CLIPEmbedder.segment(window=)` the
+whole path.
 """
 
 from __future__ import annotations
@@ -22,7 +28,7 @@ from imagescry_amd import _lib
 from imagescry_amd.data import EmbeddingBatch
 
 __all__ = ["LabelMaps", "UNLABELED", "MAX_PROMPTS", "MAX_CLASSES", "class_scores", "label_map", "label_map_geometry",
-           "segment"]
+           "segment", "window_grid", "crop_windows", "label_map_windows", "segment_windows"]
 
 UNLABELED = 255  # the label of a pixel whose best score is NaN or below `min_score`
 MAX_PROMPTS = 1024  # isc_label_map: 1 <= C <= 1024
@@ -200,3 +206,132 @@ def segment(maps: "EmbeddingBatch | Tensor", vectors: Tensor, size: "tuple[int, 
     if isinstance(maps, EmbeddingBatch):
         return LabelMaps(out.labels, out.scores, out.margins, out.counts, maps.indices)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------ sliding windows
+def _check_pair(name: str, value: object) -> tuple[int, int]:
+    """An int or a pair of ints, all at least 1 -> (vertical, horizontal)."""
+    if isinstance(value, int) and not isinstance(value, bool):
+        value = (value, value)
+    if (not isinstance(value, (tuple, list)) or len(value) != 2
+            or not all(isinstance(v, int) and not isinstance(v, bool) for v in value)):
+        raise TypeError(f"{name} must be an int or a pair of ints, got {value!r}")
+    if value[0] < 1 or value[1] < 1:
+        raise ValueError(f"{name} must be at least 1, got {tuple(value)}")
+    return value[0], value[1]
+
+
+def _window_geometry(size: object, window: object, stride: object) -> tuple[tuple[int, int], tuple[int, int], tuple[int, int]]:
+    """The checked (size, window, stride): a window larger than the image on an axis is clamped to the image there, and
+    `stride=None` is half the (clamped) window, rounded up."""
+    big_h, big_w = _check_size(size)
+    win = _check_pair("window", window)
+    win = (min(win[0], big_h), min(win[1], big_w))
+    step = ((win[0] + 1) // 2, (win[1] + 1) // 2) if stride is None else _check_pair("stride", stride)
+    if step[0] > win[0] or step[1] > win[1]:
+        raise ValueError(f"stride {step} must not exceed the window {win} (clamped to the image): pixels between two "
+                         "windows would be covered by none")
+    return (big_h, big_w), win, step
+
+
+def _axis_starts(length: int, win: int, stride: int) -> list[int]:
+    return [min(i * stride, length - win) for i in range(max(length - win + stride - 1, 0) // stride + 1)]
+
+
+def window_grid(size: "tuple[int, int]", window: "int | tuple[int, int]",
+                stride: "int | tuple[int, int] | None" = None) -> tuple[list[int], list[int]]:
+    """The first row of every window row and the first column of every window column, `(ys, xs)`, of the sliding-window
+    grid over an image of `size = (H, W)` (mmseg's `slide_inference`; `isc_label_map_window_grid` counts the same):
+    along an axis of length L there are `max(L - win + stride - 1, 0) // stride + 1` windows, window i starting at
+    `min(i * stride, L - win)` -- the last one is shifted back to end at the border.  The starts are distinct, every
+    pixel is covered, by at most `ceil(win / stride) + 1` windows an axis.  Window `(i, j)` covers rows `ys[i] : ys[i] +
+    win_h` and columns `xs[j] : xs[j] + win_w`; an image's windows are ordered i major."""
+    (big_h, big_w), win, step = _window_geometry(size, window, stride)
+    return _axis_starts(big_h, win[0], step[0]), _axis_starts(big_w, win[1], step[1])
+
+
+def crop_windows(images: Tensor, window: "int | tuple[int, int]", stride: "int | tuple[int, int] | None" = None) -> Tensor:
+    """`[B, 3, H, W]` (any channel count, any dtype: uint8 stays uint8) -> the window crops `[B * ny * nx, 3, win_h,
+    win_w]` of `window_grid`, image-major and i major inside an image: the order `label_map_windows` reads."""
+    if not isinstance(images, Tensor):
+        raise TypeError(f"images must be a torch.Tensor, got {type(images).__name__}")
+    if images.ndim != 4:
+        raise ValueError(f"images must have shape [B, C, H, W], got {tuple(images.shape)}")
+    size, win, step = _window_geometry((int(images.shape[2]), int(images.shape[3])), window, stride)
+    ys, xs = window_grid(size, win, step)
+    crops = torch.stack([images[:, :, y:y + win[0], x:x + win[1]] for y in ys for x in xs], dim=1)
+    return crops.reshape(images.shape[0] * len(ys) * len(xs), images.shape[1], win[0], win[1])
+
+
+def label_map_windows(scores: Tensor, size: "tuple[int, int]", window: "int | tuple[int, int]",
+                      stride: "int | tuple[int, int] | None" = None, *, class_of: "Tensor | list[int] | None" = None,
+                      min_score: float | None = None, return_scores: bool = True, return_margin: bool = False,
+                      return_counts: bool = False) -> LabelMaps:
+    """Sliding-window inference in one kernel (`isc_label_map_windows`): every window's class scores are upsampled
+    bilinearly to the window's pixels, the windows that cover a pixel are averaged there and the pixel is labelled with
+    the class of the best prompt -- without writing a window's `[C, win_h, win_w]` upsampling or the `[B, C, H, W]` sum.
+
+    `scores`: float32 `[B * ny * nx, h, w, C]` (what `class_scores` returns for `crop_windows`' crops) or `[B, ny, nx, h,
+    w, C]`, the grid being `window_grid(size, window, stride)`'s.  Everything else as in `label_map`; the arithmetic is
+    fixed (include/imagescry_hip.h): with one window equal to the image the answer is `label_map`'s bit for bit."""
+    size, win, step = _window_geometry(size, window, stride)
+    scores = _check_float_tensor("scores", scores, 6 if isinstance(scores, Tensor) and scores.ndim == 6 else 4,
+                                 "[B * ny * nx, h, w, C] or [B, ny, nx, h, w, C]")
+    if min_score is not None and (isinstance(min_score, bool) or not isinstance(min_score, (int, float))):
+        raise TypeError(f"min_score must be a number or None, got {type(min_score).__name__}")
+    if min_score is not None and math.isnan(min_score):
+        raise ValueError("min_score must not be NaN")
+    ys, xs = window_grid(size, win, step)
+    ny, nx = len(ys), len(xs)
+    if scores.ndim == 6:
+        if tuple(scores.shape[1:3]) != (ny, nx):
+            raise ValueError(f"scores hold {scores.shape[1]} x {scores.shape[2]} windows an image but the grid of window "
+                             f"{win}, stride {step} over {size} has {ny} x {nx}")
+        b = scores.shape[0]
+    else:
+        if scores.shape[0] % (ny * nx):
+            raise ValueError(f"scores hold {scores.shape[0]} windows, not a multiple of the {ny} x {nx} windows of window "
+                             f"{win}, stride {step} over {size}")
+        b = scores.shape[0] // (ny * nx)
+    h, w, c = (int(v) for v in scores.shape[-3:])
+    if not 1 <= c <= MAX_PROMPTS:
+        raise ValueError(f"scores hold {c} prompts; label_map_windows takes 1 .. {MAX_PROMPTS}")
+    if h < 1 or w < 1:
+        raise ValueError(f"scores must hold at least one cell a window, got a {h} x {w} grid")
+    if h * w >= 2**31:
+        raise ValueError(f"a {h} x {w} grid has 2^31 cells or more")
+    classes = _check_class_of(class_of, c)
+    _lib.require_device(scores, "scores")
+    device = scores.device
+    if classes is not None:
+        classes = classes.to(device=device, dtype=torch.int32).contiguous()
+    scores = scores.contiguous()
+    labels = torch.empty((b, *size), dtype=torch.uint8, device=device)
+    best = torch.empty((b, *size), dtype=torch.float32, device=device) if return_scores else None
+    margins = torch.empty((b, *size), dtype=torch.float32, device=device) if return_margin else None
+    counts = torch.empty((b, 256), dtype=torch.int32, device=device) if return_counts else None
+    with torch.cuda.device(device):
+        st = _lib.load().isc_label_map_windows(scores.data_ptr(), b, h, w, c, c, _lib.ptr(classes), *size, *win, *step,
+                                               -math.inf if min_score is None else float(min_score), labels.data_ptr(),
+                                               _lib.ptr(best), _lib.ptr(margins), _lib.ptr(counts),
+                                               _lib.stream_handle(device))
+    _lib.check(st, "isc_label_map_windows")
+    return LabelMaps(labels=labels, scores=best, margins=margins, counts=counts)
+
+
+MAX_SCORED_MAPS = 65535  # isc_map_class_scores: B <= 65535 a launch
+
+
+def segment_windows(maps: "EmbeddingBatch | Tensor", vectors: Tensor, size: "tuple[int, int]",
+                    window: "int | tuple[int, int]", stride: "int | tuple[int, int] | None" = None,
+                    **kw: object) -> LabelMaps:
+    """`label_map_windows(class_scores(maps, vectors), size, window, stride, **kw)`: `maps` is the `[B * ny * nx, E, h,
+    w]` map of `crop_windows`' crops or its `EmbeddingBatch` (whose indices, one per crop, are not carried: the caller
+    knows the images').  `class_scores` runs in slices of 65 535 crops, its limit a launch."""
+    size, win, step = _window_geometry(size, window, stride)
+    m = maps.embeddings if isinstance(maps, EmbeddingBatch) else maps
+    if isinstance(m, Tensor) and m.ndim == 4 and m.shape[0] > MAX_SCORED_MAPS:
+        scores = torch.cat([class_scores(m[i:i + MAX_SCORED_MAPS], vectors) for i in range(0, m.shape[0], MAX_SCORED_MAPS)])
+    else:
+        scores = class_scores(m, vectors)
+    return label_map_windows(scores, size, win, step, **kw)

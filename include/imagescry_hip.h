@@ -1016,6 +1016,44 @@ int isc_label_map_geometry(int* tile_w, int* tile_h, int* prompt_chunk);
 int isc_map_class_scores(const float* maps, int B, int E, int S, const float* vectors, int C, int64_t ldv, float* out,
                          int64_t ldc, void* stream);
 
+/* Sliding-window inference: the image is H x W, every window win_h x win_w pixels, scored on its own h x w grid; the
+ * windows' upsampled scores are averaged per pixel and the arg max is taken, in one pass.  Neither a window's
+ * [C, win_h, win_w] upsampling nor the [B, C, H, W] sum is ever written.
+ * The window grid (mmseg's slide_inference), per axis of length L with window win and stride, 1 <= stride <= win <= L:
+ *   n = max(L - win + stride - 1, 0) / stride + 1 windows, window i starting at start_i = min(i * stride, L - win):
+ *   the last one is shifted back to end at the border, the starts are distinct, every pixel is covered, by at most
+ *   ceil(win / stride) + 1 windows.  Window (i, j) is row i, column j; an image's windows are ordered i major.
+ *   scores     float [B, ny, nx, h, w, C], leading dimension ldc >= C: what isc_map_class_scores writes for the
+ *              B * ny * nx window crops stacked image-major
+ *   class_of, min_score, labels, best, margin, counts: as for isc_label_map
+ * For the output pixel (y, x), as a fixed sequence of float32 operations:
+ *   1  the covering windows are those with start_i <= y < start_i + win_h and start_j <= x < start_j + win_w, visited
+ *      with i ascending and inside that j ascending; n is their number;
+ *   2  in a covering window the taps are tap(y - start_i, (float)h / (float)win_h, h) and tap(x - start_j, (float)w /
+ *      (float)win_w, w), the weights w00 .. w11 steps 1 - 2 of isc_label_map, and for every prompt c
+ *      u = fmaf(w11, s11, fmaf(w10, s10, fmaf(w01, s01, w00 * s00))) on that window's grid (step 3 of isc_label_map);
+ *   3  acc_c = u for the first covering window and acc_c = acc_c + u, one rounded addition, for every later one;
+ *   4  v_c = acc_c / (float)n, correctly rounded;
+ *   5  steps 4 - 7 of isc_label_map on v_c: the order of the choice, class_of, the margin, the strict threshold, the
+ *      label 255 and counts (zeroed by a launch of its own).
+ * A pixel's bits depend on the cells of its own covering windows only: not on B, ldc or the tiling.  With a single
+ * window equal to the image (win = (H, W)) the outputs are bit for bit those of isc_label_map; with stride = win every
+ * pixel has n = 1 and each window's block is isc_label_map of that window.  Non-finite scores give what the arithmetic
+ * gives: +inf in one window and -inf in another over one pixel sum to NaN.
+ * Any number of windows per pixel is served: tiles whose pixels lie in at most 4 windows stage the cells through LDS,
+ * the others (and footprints too large to stage) read them from memory with the same arithmetic.
+ * Limits and errors: those of isc_label_map (C, h * w, H * W, B, H, the alignments, a NaN min_score); win < 1,
+ * stride < 1, stride > win or win > image on either axis is ISC_ERR_INVALID_ARG.  Everything is checked before anything
+ * is launched.  B == 0 returns ISC_OK without a launch.  No workspace, no host synchronisation, capturable. */
+int isc_label_map_windows(const float* scores, int B, int h, int w, int C, int64_t ldc, const int32_t* class_of, int H, int W,
+                          int win_h, int win_w, int stride_y, int stride_x, float min_score, uint8_t* labels, float* best,
+                          float* margin, int32_t* counts, void* stream);
+
+/* The window grid of isc_label_map_windows (host only, host pointers): ny x nx windows, and max_cover = the most windows
+ * that lie on one pixel.  The same argument errors as isc_label_map_windows. */
+int isc_label_map_window_grid(int H, int W, int win_h, int win_w, int stride_y, int stride_x, int* ny, int* nx,
+                              int* max_cover);
+
 #ifdef __cplusplus
 }
 #endif
