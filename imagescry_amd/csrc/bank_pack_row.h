@@ -29,7 +29,7 @@ __device__ __forceinline__ void isc_pack_row(const TIN* __restrict__ p, int d, i
     // rows whose chunks can be fetched with 16-byte loads (a wave instruction then reads 1 KiB of the row instead of 64
     // scattered 2- or 4-byte elements)
     const bool vec_ok = IN_VECS > 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0);
-    float stored_sq = 0.f;
+    float stored_sq = 0.f, stored_max = 0.f;
     for (int c = lane; c < chunks; c += 64) {
         TOUT v[PER_CHUNK];
         float f[PER_CHUNK];
@@ -51,6 +51,7 @@ __device__ __forceinline__ void isc_pack_row(const TIN* __restrict__ p, int d, i
             v[j] = (TOUT)f[j];
             const float s = (float)v[j];
             stored_sq = fmaf(s, s, stored_sq);
+            stored_max = fmaxf(stored_max, fabsf(s));  // (a NaN is dropped here; the sum keeps it)
         }
         unsigned char* dst = packed + isc_packed_offset(row, c >> 3, ks) + (c & 7) * 16;
         *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(v);
@@ -58,7 +59,13 @@ __device__ __forceinline__ void isc_pack_row(const TIN* __restrict__ p, int d, i
     if (norm_bound) {
         stored_sq = isc_wave_sum(stored_sq);
         // float32 summation of d squares: relative error <= d * 2^-24 -- cover it (and the sqrt) with a factor
-        const float nb = sqrtf(stored_sq) * (1.f + 1e-3f);
+        float nb = sqrtf(stored_sq) * (1.f + 1e-3f);
+        // Below 2^-64 the sum is no bound any more: the squares of a float32 row of tiny scale lose bits to underflow, or
+        // vanish altogether (entries under 1e-23), and a bound of 0 for a bank of positive norms would switch the search's
+        // guard off.  ||row|| <= max|s| sqrt(Dpad) needs no square; the factor 2 covers the rounding of the square root
+        // and of the product, which in the subnormal range is absolute (2^-150 <= half of any non-zero product).  A row
+        // of zeros still publishes 0.  (wave-uniform: every lane holds the same sum)
+        if (stored_sq < 0x1p-64f) nb = 2.f * (isc_wave_max(stored_max) * sqrtf((float)(chunks * PER_CHUNK)));
         // non-negative floats order as uints; a row holding NaN makes the bound +inf: the search then trusts no filter
         // result on this bank and answers through its exhaustive pass.  The atomic goes out only when this row RAISES the
         // bound as this wave sees it (a plain read first): one atomic per row on the one word was the whole kernel --

@@ -2059,8 +2059,11 @@ __global__ __launch_bounds__(SEL_THREADS, 4) void k_final(
     // every accumulation step of the matrix core is assumed too; status[2] < 1 is what the tests assert about it).  A query
     // of denormal scale loses product bits to underflow, one of huge scale can overflow a partial sum to inf / NaN while
     // the float64 score is finite -- and such rows are dropped silently by the filter.  |partial sum| <= ||q|| max||b||, so
-    // outside [1e-30, 1e37] (and for a NaN / inf bound) no filter result is trusted: the exhaustive pass answers.
-    const bool filter_trusted = qnorm >= 1e-30 && qnorm * bmax <= 1e37;
+    // outside [1e-30, 1e37] (and for a NaN / inf bound) no filter result is trusted: the exhaustive pass answers.  A BANK of
+    // denormal scale loses the same bits: its products with a query of norm 1 round to whole units of 2^-149, an absolute
+    // error that eps, a relative bound, does not hold (tests/test_gpu_bank_pack_exact.py: rows a few units apart), so
+    // ||q|| max||b|| has the same lower end -- unless the bound is 0: every stored row is zero, and so is every score.
+    const bool filter_trusted = qnorm >= 1e-30 && (bmax == 0.0 || qnorm * bmax >= 1e-30) && qnorm * bmax <= 1e37;
     if (tid < nc) {
         const unsigned long long mykey = isc_make_key(fsc[tid], orig[tid]);
         int rank = 0;
@@ -2912,7 +2915,8 @@ __global__ __launch_bounds__(SEL_THREADS) void k_final_groups(
     if (tid == 0) kth_sh = __uint_as_float(0x7fc00000u);
     __syncthreads();
     const double eps = (double)(ks * (ISC_KSTEP_BYTES / (int)sizeof(T))) * (1.0 / 8388608.0) * qnorm * bmax;
-    const bool filter_trusted = qnorm >= 1e-30 && qnorm * bmax <= 1e37;
+    // (k_final's range, with its lower end for a bank of denormal scale)
+    const bool filter_trusted = qnorm >= 1e-30 && (bmax == 0.0 || qnorm * bmax >= 1e-30) && qnorm * bmax <= 1e37;
     if (tid < nc) {
         const unsigned long long mykey = gkey[tid];
         int rank = 0;
