@@ -17,6 +17,7 @@ Public surface (same names as the reference where the reference has them):
   `LabelMaps`                                    -- pixel label maps from dense patch scores (new; see segmentation.py)
 * `window_grid`, `crop_windows`,
   `label_map_windows`, `segment_windows`         -- sliding-window inference: overlapping windows averaged per pixel (new)
+* `label_regions`, `Regions`                     -- connected regions of a label map: ids, boxes, areas, peaks (new)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/imagescry_hip.h;
 PyTorch is used for device memory, streams and `torch.distributed` only.
@@ -39,10 +40,12 @@ from imagescry_amd.embedding import (
 from imagescry_amd.pipelines import EmbeddingPCAPipeline, EmbedSearchPipeline, SearchResult
 from imagescry_amd.segmentation import (
     LabelMaps,
+    Regions,
     class_scores,
     crop_windows,
     label_map,
     label_map_windows,
+    label_regions,
     segment,
     segment_windows,
     window_grid,
@@ -65,6 +68,7 @@ __all__ = [
     "LabelMaps",
     "PCA",
     "RangeResult",
+    "Regions",
     "RowFilter",
     "ResNet50Embedder",
     "SigLIPEmbedder",
@@ -74,6 +78,7 @@ __all__ = [
     "crop_windows",
     "label_map",
     "label_map_windows",
+    "label_regions",
     "segment",
     "segment_windows",
     "siglip",

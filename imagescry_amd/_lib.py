@@ -369,6 +369,13 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "isc_label_map_window_grid": (
         c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]
     ),
+    "isc_label_regions": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "isc_label_regions_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "isc_label_regions_geometry": (c_int, [POINTER(c_int), POINTER(c_int)]),
 }
 
 _lib: ctypes.CDLL | None = None

@@ -13,6 +13,11 @@ checkpoint's own resolution over a larger image, `crop_windows` cuts them out, a
 window's scores to its pixels, averages the windows that overlap on a pixel and takes the arg max, again in one kernel
 (`isc_label_map_windows`); `segment_windows` is `class_scores` + `label_map_windows`, `CLIPEmbedder.segment(window=)` the
 whole path.
+
+Pixels back to regions: `label_regions` (or `LabelMaps.regions`) finds the connected regions of a label map on the device
+(`isc_label_regions`: a union-find across tiles) -- ids per pixel, and per region its class, area, box, coordinate sums
+and best-scoring pixel -- and drops regions below `min_area`: what `scipy.ndimage.label` per class and image does on the
+host, without the round trip.
 """
 
 from __future__ import annotations
@@ -28,7 +33,8 @@ from imagescry_amd import _lib
 from imagescry_amd.data import EmbeddingBatch
 
 __all__ = ["LabelMaps", "UNLABELED", "MAX_PROMPTS", "MAX_CLASSES", "class_scores", "label_map", "label_map_geometry",
-           "segment", "window_grid", "crop_windows", "label_map_windows", "segment_windows"]
+           "segment", "window_grid", "crop_windows", "label_map_windows", "segment_windows", "Regions", "label_regions",
+           "label_regions_geometry"]
 
 UNLABELED = 255  # the label of a pixel whose best score is NaN or below `min_score`
 MAX_PROMPTS = 1024  # isc_label_map: 1 <= C <= 1024
@@ -65,6 +71,10 @@ class LabelMaps:
 
     def __len__(self) -> int:
         return self.labels.shape[0]
+
+    def regions(self, **kw: object) -> "Regions":
+        """`label_regions(self, **kw)`: the connected regions of these maps, `scores` scoring the peaks."""
+        return label_regions(self, **kw)
 
 
 def label_map_geometry() -> tuple[int, int, int]:
@@ -335,3 +345,150 @@ def segment_windows(maps: "EmbeddingBatch | Tensor", vectors: Tensor, size: "tup
     else:
         scores = class_scores(m, vectors)
     return label_map_windows(scores, size, win, step, **kw)
+
+
+# -------------------------------------------------------------------------------------------------- connected regions
+@dataclass(frozen=True)
+class Regions:
+    """What `label_regions` returns, R = `max_regions` rows an image; a field that was not asked for is None.
+
+    ids:         int32 `[B, H, W]`, the id of the pixel's kept region, -1 for unlabeled pixels and dropped regions
+                 (never truncated to R)
+    num:         int32 `[B]`, the true number of kept regions, also above R
+    label, area, anchor: int32 `[B, R]`, the region's class, pixels and smallest linear index `y * W + x`
+    boxes:       int32 `[B, R, 4]`, `(y0, x0, y1, x1)` with exclusive ends
+    sums:        int64 `[B, R, 2]`, `(sum of y, sum of x)` over the region's pixels
+    peak, peak_scores: int32 / float32 `[B, R]`, the region's best-scoring pixel (linear index) and its score; None
+                 without scores
+    labels:      uint8 `[B, H, W]`, the map without the dropped regions (`return_labels=True`)
+    indices:     int64 `[B]` dataset indices, carried over from a `LabelMaps`
+    Rows at and above `min(num[b], R)` read (-1, 0, -1, zeros, zeros, -1, -inf)."""
+
+    ids: Tensor
+    num: Tensor
+    label: Tensor
+    area: Tensor
+    anchor: Tensor
+    boxes: Tensor
+    sums: Tensor
+    peak: Tensor | None = None
+    peak_scores: Tensor | None = None
+    labels: Tensor | None = None
+    indices: Tensor | None = None
+
+    def to(self, device: str | torch.device) -> "Regions":
+        return Regions(*(None if t is None else t.to(device)
+                         for t in (self.ids, self.num, self.label, self.area, self.anchor, self.boxes, self.sums,
+                                   self.peak, self.peak_scores, self.labels, self.indices)))
+
+    def cpu(self) -> "Regions":
+        return self.to("cpu")
+
+    @property
+    def device(self) -> torch.device:
+        return self.ids.device
+
+    def __len__(self) -> int:
+        return self.ids.shape[0]
+
+    def centroids(self) -> Tensor:
+        """float64 `[B, R, 2]`, `(y, x) = sums / area`; NaN for empty rows."""
+        area = self.area.to(torch.float64).unsqueeze(-1)
+        return torch.where(area > 0, self.sums.to(torch.float64) / area, torch.full_like(area, math.nan))
+
+    def peak_cells(self, grid: "tuple[int, int]") -> Tensor:
+        """int64 `[B, R]`: the cell of an `h x w` grid over the image that contains the peak pixel's centre,
+        `((2y + 1) * h // (2H)) * w + (2x + 1) * w // (2W)`, -1 for empty rows.  With an image's row offset in a patch
+        bank this is the row to hand to `bank.search_rows`."""
+        if self.peak is None:
+            raise ValueError("these regions were found without scores: there are no peaks")
+        h, w = _check_size(grid)
+        big_h, big_w = self.ids.shape[1:]
+        peak = self.peak.to(torch.int64)
+        y, x = peak // big_w, peak % big_w
+        cell = ((2 * y + 1) * h // (2 * big_h)) * w + (2 * x + 1) * w // (2 * big_w)
+        return torch.where(peak >= 0, cell, torch.full_like(cell, -1))
+
+
+def label_regions_geometry() -> tuple[int, int]:
+    """(tile_w, tile_h) of `isc_label_regions`' first pass."""
+    tw, th = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().isc_label_regions_geometry(tw, th), "isc_label_regions_geometry")
+    return tw.value, th.value
+
+
+def _check_count(name: str, value: object) -> int:
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise TypeError(f"{name} must be an int, got {type(value).__name__}")
+    if value < 1:
+        raise ValueError(f"{name} must be at least 1, got {value}")
+    return value
+
+
+def label_regions(labels: "Tensor | LabelMaps", *, scores: Tensor | None = None, connectivity: int = 8, min_area: int = 1,
+                  max_regions: int = 1024, return_labels: bool = False) -> Regions:
+    """The connected regions of label maps (`isc_label_regions`, include/imagescry_hip.h has the definition): two pixels
+    of one image belong to one region if they carry the same label (not `UNLABELED`) and are linked through neighbours
+    that do -- across edges (`connectivity=4`) or edges and corners (`8`).  Regions of fewer than `min_area` pixels are
+    dropped; the others are numbered from 0 in raster order of their first pixel, per image.
+
+    `labels`: uint8 `[B, H, W]` or a `LabelMaps` (whose `scores` then score the peaks unless `scores` is given, and whose
+    `indices` are carried over).  `scores`: float32 `[B, H, W]`; without them `Regions.peak` / `.peak_scores` are None.
+    `max_regions`: rows an image in the tables; `Regions.num` holds the true count, so `num > max_regions` tells of a
+    truncated table without a host read here.  `return_labels`: also the map with the dropped regions unlabeled.
+    Integers throughout: deterministic, the same for an image wherever it stands in a batch, capturable.  Nothing
+    synchronises with the host."""
+    indices = None
+    if isinstance(labels, LabelMaps):
+        indices = labels.indices
+        if scores is None:
+            scores = labels.scores
+        labels = labels.labels
+    if not isinstance(labels, Tensor):
+        raise TypeError(f"labels must be a torch.Tensor or LabelMaps, got {type(labels).__name__}")
+    if labels.dtype != torch.uint8:
+        raise TypeError(f"labels must be uint8, got {labels.dtype}")
+    if labels.ndim != 3:
+        raise ValueError(f"labels must have shape [B, H, W], got {tuple(labels.shape)}")
+    if scores is not None:
+        scores = _check_float_tensor("scores", scores, 3, "[B, H, W]")
+        if scores.shape != labels.shape:
+            raise ValueError(f"scores {tuple(scores.shape)} must have the shape of labels {tuple(labels.shape)}")
+    if isinstance(connectivity, bool) or not isinstance(connectivity, int):
+        raise TypeError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
+    min_area = _check_count("min_area", min_area)
+    rows = _check_count("max_regions", max_regions)
+    b, big_h, big_w = (int(v) for v in labels.shape)
+    _check_size((big_h, big_w))
+    if scores is not None and min(rows, big_h * big_w) > max(1024, big_h * big_w // 8):
+        raise ValueError(f"with scores, max_regions may be at most max(1024, H * W / 8) = "
+                         f"{max(1024, big_h * big_w // 8)} for {big_h} x {big_w} images, got {rows}")
+    _lib.require_device(labels, "labels")
+    device = labels.device
+    if scores is not None and scores.device != device:
+        raise ValueError(f"labels are on {device} but scores on {scores.device}")
+    labels = labels.contiguous()
+    scores = None if scores is None else scores.contiguous()
+    lib = _lib.load()
+    need = ctypes.c_size_t()
+    _lib.check(lib.isc_label_regions_workspace_bytes(b, big_h, big_w, need), "isc_label_regions_workspace_bytes")
+
+    def table(*shape: int, dtype: torch.dtype = torch.int32) -> Tensor:
+        return torch.empty((b, rows, *shape), dtype=dtype, device=device)
+
+    ids = torch.empty((b, big_h, big_w), dtype=torch.int32, device=device)
+    num = torch.empty((b,), dtype=torch.int32, device=device)
+    kept = torch.empty_like(labels) if return_labels else None
+    label, area, anchor, boxes, sums = table(), table(), table(), table(4), table(2, dtype=torch.int64)
+    peak = None if scores is None else table()
+    peak_scores = None if scores is None else table(dtype=torch.float32)
+    workspace = torch.empty((need.value,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        st = lib.isc_label_regions(labels.data_ptr(), _lib.ptr(scores), b, big_h, big_w, connectivity, min_area, rows,
+                                   ids.data_ptr(), num.data_ptr(), _lib.ptr(kept), label.data_ptr(), area.data_ptr(),
+                                   anchor.data_ptr(), boxes.data_ptr(), sums.data_ptr(), _lib.ptr(peak),
+                                   _lib.ptr(peak_scores), workspace.data_ptr(), need.value, _lib.stream_handle(device))
+    _lib.check(st, "isc_label_regions")
+    return Regions(ids, num, label, area, anchor, boxes, sums, peak, peak_scores, kept, indices)

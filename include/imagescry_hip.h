@@ -1054,6 +1054,66 @@ int isc_label_map_windows(const float* scores, int B, int h, int w, int C, int64
 int isc_label_map_window_grid(int H, int W, int win_h, int win_w, int stride_y, int stride_x, int* ny, int* nx,
                               int* max_cover);
 
+/* Pixels back to regions: the connected regions of label maps, numbered, measured and optionally despeckled, on the
+ * device (what scipy.ndimage.label per class and image does on the host).
+ *   labels        uint8 [B, H, W], what isc_label_map writes; a pixel is foreground iff its label is not 255
+ *   best          float [B, H, W] or NULL, a score per pixel (isc_label_map's best): only the peak outputs read it
+ *   connectivity  4: two foreground pixels of one image with the same label are joined if they share an edge;
+ *                 8: an edge or a corner
+ *   min_area      >= 1; a region is KEPT iff it has at least min_area pixels (1 keeps every region)
+ *   max_regions   R >= 1, the rows an image has in the tables
+ * A region is an equivalence class of the joined relation; its ANCHOR is its smallest linear index y * W + x.  The kept
+ * regions of an image are numbered 0, 1, .. by ascending anchor -- the raster order of first encounter; for one class
+ * the numbering of scipy.ndimage.label minus one -- and the numbering starts again at 0 in every image.
+ *   region_ids    int32 [B, H, W]   the id of the pixel's kept region; -1 for unlabeled pixels and for the pixels of
+ *                                   dropped regions.  Ids are never truncated to R.
+ *   num_regions   int32 [B]         the true number of kept regions, also where it exceeds R: how a caller sees the
+ *                                   truncation of the tables without a synchronisation
+ *   labels_out    uint8 [B, H, W] or NULL   labels with the pixels of dropped regions set to 255 (the despeckled map);
+ *                                   must not overlap labels (ISC_ERR_INVALID_ARG)
+ * and the tables, each of them NULL or:
+ *   region_label  int32 [B, R]      the class of region r          region_area    int32 [B, R]   its pixels
+ *   region_anchor int32 [B, R]      its anchor
+ *   region_box    int32 [B, R, 4]   (y0, x0, y1, x1), ends exclusive: the region lies inside labels[b, y0:y1, x0:x1] and
+ *                                   touches all four sides
+ *   region_sum    int64 [B, R, 2]   (sum of y, sum of x) over the region's pixels, exact; centroid = sum / area
+ *   region_peak   int32 [B, R]      needs best: the linear index of the region's first pixel in the order of the
+ *                                   searches over best: value descending (-0.0 and +0.0 are one value), NaN last, ties to
+ *                                   the lower linear index
+ *   region_peak_score float [B, R]  needs best: best at that pixel, copied (a NaN where the whole region is NaN)
+ * Rows r < min(num_regions[b], R) are as above; every row at or above that reads (label, area, anchor, box, sum, peak,
+ * peak score) = (-1, 0, -1, 0 0 0 0, 0 0, -1, -INFINITY): every byte of every output passed is defined on every call
+ * and replay.  All outputs are integers or copies of input floats and depend on the image alone: not on B, the image's
+ * place in the batch, the tiling or the order in which atomics land (integer sums, minima and maxima only; the peak is
+ * the maximum of a 64-bit key that orders exactly as stated).  Two runs give the same bytes.
+ * How: region_ids serves as the parent array of a union-find forest in which a larger index always hangs under a
+ * smaller one.  A workgroup resolves a tile_w x tile_h tile in LDS; a second launch joins the tiles across their borders
+ * lock-free (atomic min on the parent of a root; no thread ever waits for another); later launches shorten the paths,
+ * sum the areas on the roots, rank the kept roots by an exclusive scan in raster order, and write ids, labels_out and
+ * the statistics with one set of integer atomics per tile and tile-local part of a region.  Up to nine launches.
+ * Workspace (isc_label_regions_workspace_bytes(B, H, W), 16-byte aligned): int32 [B, H, W] (the area of every region on
+ * its root, then its rank), int32 [B, ceil(H * W / 1024)] (kept roots per chunk of the raster order, then their
+ * exclusive scan) and uint64 [B, min(H * W, max(1024, H * W / 8))] (the peak keys).  The call initialises whatever it
+ * reads: a workspace full of garbage is fine.
+ * Limits: H, W >= 1, H * W < 2^31, B <= 65535, H <= 1048560 (the grid), B * R < 2^39, and with a peak output
+ * min(R, H * W) <= max(1024, H * W / 8) (the key slots) -- ISC_ERR_UNSUPPORTED beyond them.  ISC_ERR_INVALID_ARG: labels,
+ * region_ids or num_regions NULL, a connectivity other than 4 or 8, min_area < 1, max_regions < 1, a peak output
+ * without best.  ISC_ERR_WORKSPACE: workspace NULL or too small.  ISC_ERR_ALIGNMENT: workspace off 16 bytes, region_sum
+ * off 8, best or an int32 / float output off 4.  Everything is checked before anything is launched.  B == 0 returns ISC_OK
+ * without a launch.  No host synchronisation, capturable. */
+int isc_label_regions(const uint8_t* labels, const float* best, int B, int H, int W, int connectivity, int min_area,
+                      int max_regions, int32_t* region_ids, int32_t* num_regions, uint8_t* labels_out,
+                      int32_t* region_label, int32_t* region_area, int32_t* region_anchor, int32_t* region_box,
+                      int64_t* region_sum, int32_t* region_peak, float* region_peak_score, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* The workspace of isc_label_regions (host only, host pointer).  The shape errors of isc_label_regions. */
+int isc_label_regions_workspace_bytes(int B, int H, int W, size_t* bytes);
+
+/* The tile of isc_label_regions' first pass: regions are resolved inside tile_w x tile_h tiles first and joined across
+ * the tile borders afterwards -- where its code paths change (host only, host pointers). */
+int isc_label_regions_geometry(int* tile_w, int* tile_h);
+
 #ifdef __cplusplus
 }
 #endif
