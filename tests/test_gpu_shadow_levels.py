@@ -95,6 +95,8 @@ def bank64(rows64: torch.Tensor):
     # kp candidates, which no finite bank of more than kp rows produces -- only the numpy model
     # (tests/test_shadow_two_stage_model.py, carried=False) runs that branch
     (16_684, 64, 1024, [0, 2]),
+    (300_123, 160, 1024, [0, 1, 2]),  # three fp16 K steps, one and a half int8 steps: the absent half step reads as zeros
+    (140_123, 1024, 1024, [0, 2]),  # the shadow's limit in D: eight int8 K steps
 ])
 def test_chained_int8_levels(n: int, d: int, q: int, kinds: list[int], device: torch.device) -> None:
     assert _kinds(n, d, q) == kinds
