@@ -95,8 +95,12 @@ __global__ __launch_bounds__(256) void k_vit_pos_resample_aa(const float* __rest
 //            to LDS as [channel / 4][cell][4] -- a lane's four channels are one 16-byte store, rows padded by 16 bytes so
 //            that the eight lanes of a store group (528 bytes apart) fall on eight different slots; without LN
 //            (isc_tokens_to_map: rows that are final already, a projection's output) the loaded row goes to LDS as it is;
+//            a third copy of that arithmetic (vit.hip: k_layernorm, layernorm_row) -- change them together:
+//            tests/test_gpu_vit_tokens_exact.py holds the un-normalised map to the bits isc_layernorm gives on the same
+//            rows, for every NV, with and without a partly empty last lane row;
 //   phase 2  (normalize) the arithmetic of k_l2norm_spatial, bit for bit: per cell four partial sums of squares over the
-//            channels e = g, g + 4, ... in ascending order, denominator max(sqrt(r0 + r1 + r2 + r3), eps);
+//            channels e = g, g + 4, ... in ascending order, denominator max(sqrt(r0 + r1 + r2 + r3), eps) (the same test
+//            file: the bits of isc_l2norm_channels on the un-normalised map);
 //   phase 3  the transposed store: a 32-lane half of a wave reads four channels of 32 consecutive cells (one 16-byte LDS
 //            read per lane, consecutive slots) and writes, per channel, 32 consecutive floats -- 128 contiguous bytes of
 //            the channels-first map.  (A store per token would put 4-byte elements (T - 1) * 4 bytes apart.)

@@ -89,7 +89,10 @@ float32, any summation order) gives
      y^   = fl(fl(fl(d^ r^) g) + b)
    bound = SLACK |g| r ((dmu + u |d|) (1 + rho) + |d| rho) + 4 u (|g| |d| r + |b|)
    and h (|y| + bound) + 2^-25 more for an fp16 output.  A one-pass variance (E[x^2] - mu^2) loses var / mu^2 of its
-   digits instead and is what the rows with the mean at 32 standard deviations are for.
+   digits instead and is what the rows with the mean at 32 standard deviations are for.  Every other family has a
+   variance of about 1 or more, or exactly 0, where eps = 1e-6, 1e-5 or 0 move the result by a few u or not at all; the
+   rows of `small` (1e-3 * randn, variance about 1e-6) are what shows that a kernel honours its eps argument
+   (tests/test_vit_token_bounds_host.py: the restatement with another eps leaves the bound on every element).
 """
 
 from __future__ import annotations
@@ -330,7 +333,7 @@ def attention_restated(qkv: Tensor, heads: int, *, drop_largest: bool = False, e
 
 # ----------------------------------------------------------------------------------------------------- LayerNorm
 LN_EPS = 1e-6
-LN_FAMILIES = ("randn", "far-mean", "constant", "spike")
+LN_FAMILIES = ("randn", "far-mean", "constant", "spike", "small")
 
 
 def layernorm_case(rows: int, d: int, family: str, seed: int) -> dict:
@@ -345,6 +348,8 @@ def layernorm_case(rows: int, d: int, family: str, seed: int) -> dict:
     elif family == "spike":
         x = torch.randn(rows, d, generator=g)
         x[torch.arange(rows), torch.randint(0, d, (rows,), generator=g)] = 1e4
+    elif family == "small":  # the variance about equal to eps: the rows on which a wrong or ignored eps shows
+        x = torch.randn(rows, d, generator=g) * 1e-3
     else:
         raise ValueError(family)
     return {"x": x, "gamma": torch.rand(d, generator=g) + 0.5, "beta": torch.randn(d, generator=g)}
