@@ -18,6 +18,8 @@ Public surface (same names as the reference where the reference has them):
 * `window_grid`, `crop_windows`,
   `label_map_windows`, `segment_windows`         -- sliding-window inference: overlapping windows averaged per pixel (new)
 * `label_regions`, `Regions`                     -- connected regions of a label map: ids, boxes, areas, peaks (new)
+* `pool_regions`, `region_cell_weights`,
+  `RegionVectors`                                -- mask-pooled vectors per region: objects as rows of a bank (new)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/imagescry_hip.h;
 PyTorch is used for device memory, streams and `torch.distributed` only.
@@ -41,11 +43,14 @@ from imagescry_amd.pipelines import EmbeddingPCAPipeline, EmbedSearchPipeline, S
 from imagescry_amd.segmentation import (
     LabelMaps,
     Regions,
+    RegionVectors,
     class_scores,
     crop_windows,
     label_map,
     label_map_windows,
     label_regions,
+    pool_regions,
+    region_cell_weights,
     segment,
     segment_windows,
     window_grid,
@@ -69,6 +74,7 @@ __all__ = [
     "PCA",
     "RangeResult",
     "Regions",
+    "RegionVectors",
     "RowFilter",
     "ResNet50Embedder",
     "SigLIPEmbedder",
@@ -79,6 +85,8 @@ __all__ = [
     "label_map",
     "label_map_windows",
     "label_regions",
+    "pool_regions",
+    "region_cell_weights",
     "segment",
     "segment_windows",
     "siglip",

@@ -32,6 +32,7 @@ ISC_SEARCH_PASS_QUERIES = 1024  # queries per pass of isc_cosine_topk (the works
 ISC_FARTHEST_MAX_PICKS = 1 << 20  # isc_bank_farthest
 ISC_ATT_PART_QUERY = 0  # isc_attention_f16_self*: which columns of qkv play query and key
 ISC_ATT_PART_KEY = 1
+ISC_POOL_UNIT, ISC_POOL_MEAN = 0, 1  # isc_region_pool
 ISC_ABI_VERSION = 4
 ISC_BUILD_ABLATION = 1
 ISC_GEMM_A_PACKED, ISC_GEMM_W_PACKED, ISC_GEMM_OUT_PACKED, ISC_GEMM_TILE_256, ISC_GEMM_TILE_128 = 1, 2, 4, 8, 16
@@ -376,6 +377,9 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     ),
     "isc_label_regions_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "isc_label_regions_geometry": (c_int, [POINTER(c_int), POINTER(c_int)]),
+    "isc_region_cell_weights": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "isc_region_pool_geometry": (c_int, [POINTER(c_int), POINTER(c_int)]),
+    "isc_region_pool": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib: ctypes.CDLL | None = None

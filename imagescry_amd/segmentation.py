@@ -18,6 +18,11 @@ Pixels back to regions: `label_regions` (or `LabelMaps.regions`) finds the conne
 (`isc_label_regions`: a union-find across tiles) -- ids per pixel, and per region its class, area, box, coordinate sums
 and best-scoring pixel -- and drops regions below `min_area`: what `scipy.ndimage.label` per class and image does on the
 host, without the round trip.
+
+Regions back to vectors: `pool_regions` (or `Regions.embed`) pools a patch map over every region's pixels -- the mean of
+the bilinearly upsampled map over the mask, as a weighted sum over cells whose weights are exact integers
+(`isc_region_cell_weights`, `isc_region_pool`) -- so that an object is described by all of its patches and is a row of a
+bank like any other.
 """
 
 from __future__ import annotations
@@ -34,7 +39,8 @@ from imagescry_amd.data import EmbeddingBatch
 
 __all__ = ["LabelMaps", "UNLABELED", "MAX_PROMPTS", "MAX_CLASSES", "class_scores", "label_map", "label_map_geometry",
            "segment", "window_grid", "crop_windows", "label_map_windows", "segment_windows", "Regions", "label_regions",
-           "label_regions_geometry"]
+           "label_regions_geometry", "RegionVectors", "region_cell_weights", "pool_regions",
+           "region_pool_geometry"]
 
 UNLABELED = 255  # the label of a pixel whose best score is NaN or below `min_score`
 MAX_PROMPTS = 1024  # isc_label_map: 1 <= C <= 1024
@@ -409,6 +415,12 @@ class Regions:
         cell = ((2 * y + 1) * h // (2 * big_h)) * w + (2 * x + 1) * w // (2 * big_w)
         return torch.where(peak >= 0, cell, torch.full_like(cell, -1))
 
+    def embed(self, maps: "EmbeddingBatch | Tensor", **kw: object) -> "RegionVectors":
+        """`pool_regions(maps, self.ids, R, **kw)`, R the rows of these tables: a vector per region, pooled from the
+        patch map over the region's pixels, with `label`, `num` and `indices` carried over."""
+        out = pool_regions(maps, self.ids, int(self.label.shape[1]), **kw)
+        return RegionVectors(out.vectors, out.mass, out.weights, self.label, self.num, self.indices)
+
 
 def label_regions_geometry() -> tuple[int, int]:
     """(tile_w, tile_h) of `isc_label_regions`' first pass."""
@@ -492,3 +504,159 @@ def label_regions(labels: "Tensor | LabelMaps", *, scores: Tensor | None = None,
                                    _lib.ptr(peak_scores), workspace.data_ptr(), need.value, _lib.stream_handle(device))
     _lib.check(st, "isc_label_regions")
     return Regions(ids, num, label, area, anchor, boxes, sums, peak, peak_scores, kept, indices)
+
+
+# ------------------------------------------------------------------------------------------------------ region vectors
+MAX_POOL_PIXELS = 2**24  # isc_region_cell_weights: H * W <= 2^24, every weight below 2^50
+MAX_POOL_TABLE = 2**25  # ... and R * h * w <= 2^25
+MAX_POOLED_MAPS = 65535  # images a launch
+POOL_PASS_BYTES = 256 << 20  # the weights of one pass of pool_regions
+
+
+@dataclass(frozen=True)
+class RegionVectors:
+    """What `pool_regions` returns, R rows an image; a field that was not asked for or not known is None.
+
+    vectors: float32 `[B, R, E]`, the pooled map of every region: unit length (`normalize=True`) or the mean of the
+             upsampled map over the region's pixels; zeros for a region without pixels
+    mass:    int64 `[B, R]`, `4 * H * W *` the region's pixels
+    weights: int64 `[B, R, h, w]`, what `region_cell_weights` returns (`return_weights=True`)
+    label, num, indices: the regions' classes int32 `[B, R]`, their true number int32 `[B]` and the images' dataset
+             indices int64 `[B]`, carried over from a `Regions` (`Regions.embed`)"""
+
+    vectors: Tensor
+    mass: Tensor
+    weights: Tensor | None = None
+    label: Tensor | None = None
+    num: Tensor | None = None
+    indices: Tensor | None = None
+
+    def to(self, device: str | torch.device) -> "RegionVectors":
+        return RegionVectors(*(None if t is None else t.to(device)
+                               for t in (self.vectors, self.mass, self.weights, self.label, self.num, self.indices)))
+
+    def cpu(self) -> "RegionVectors":
+        return self.to("cpu")
+
+    @property
+    def device(self) -> torch.device:
+        return self.vectors.device
+
+    def __len__(self) -> int:
+        return self.vectors.shape[0]
+
+    def valid(self) -> Tensor:
+        """bool `[B, R]`: the rows of regions that have pixels (`mass > 0`)."""
+        return self.mass > 0
+
+    def flat(self) -> tuple[Tensor, Tensor, Tensor]:
+        """The valid rows as `(vectors [M, E], image int64 [M], region int64 [M])`, image major: what an
+        `EmbeddingBank(vectors, row_groups=image)` takes.  `image` is the dataset index where `indices` are known, the
+        place in the batch otherwise.  This synchronises with the host, which has to learn M."""
+        image, region = torch.nonzero(self.valid(), as_tuple=True)
+        vectors = self.vectors[image, region]
+        if self.indices is not None:
+            image = self.indices.to(device=image.device, dtype=torch.int64)[image]
+        return vectors, image, region
+
+
+def region_pool_geometry() -> tuple[int, int]:
+    """(tile_w, tile_h): the pixels a workgroup of `isc_region_cell_weights` owns."""
+    tw, th = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().isc_region_pool_geometry(tw, th), "isc_region_pool_geometry")
+    return tw.value, th.value
+
+
+def _check_region_ids(ids: object, num_regions: object, grid: tuple[int, int]) -> tuple[Tensor, int]:
+    if not isinstance(ids, Tensor):
+        raise TypeError(f"ids must be a torch.Tensor, got {type(ids).__name__}")
+    if ids.dtype != torch.int32:
+        raise TypeError(f"ids must be int32, got {ids.dtype}")
+    if ids.ndim != 3:
+        raise ValueError(f"ids must have shape [B, H, W], got {tuple(ids.shape)}")
+    rows = _check_count("num_regions", num_regions)
+    big_h, big_w = (int(v) for v in ids.shape[1:])
+    h, w = grid
+    if big_h < 1 or big_w < 1:
+        raise ValueError(f"ids must hold at least one pixel an image, got {big_h} x {big_w}")
+    if big_h * big_w > MAX_POOL_PIXELS:
+        raise ValueError(f"ids of {big_h} x {big_w} pixels exceed the 2^24 pixels the integer weights are exact for")
+    if rows * h * w > MAX_POOL_TABLE:
+        raise ValueError(f"{rows} regions x {h} x {w} cells exceed the 2^25 entries an image of the weights table")
+    return ids, rows
+
+
+def _cell_weights(ids: Tensor, rows: int, grid: tuple[int, int], out: Tensor) -> None:
+    """isc_region_cell_weights of contiguous `ids` (at most 65 535 images) into contiguous `out`."""
+    big_h, big_w = (int(v) for v in ids.shape[1:])
+    with torch.cuda.device(ids.device):
+        st = _lib.load().isc_region_cell_weights(ids.data_ptr(), ids.shape[0], big_h, big_w, *grid, rows, out.data_ptr(),
+                                                 _lib.stream_handle(ids.device))
+    _lib.check(st, "isc_region_cell_weights")
+
+
+def region_cell_weights(ids: Tensor, num_regions: int, grid: "tuple[int, int]") -> Tensor:
+    """How much every cell of an `h x w` grid counts for every region of `ids` (int32 `[B, H, W]` on the device,
+    `Regions.ids` or any raster mask; negative ids and ids at or above `num_regions` are skipped) when the grid is
+    upsampled bilinearly (`align_corners=False`) to `H x W` and summed over the region's pixels: int64 `[B, R, h, w]`,
+    exact integers (`isc_region_cell_weights`, include/imagescry_hip.h has the definition).  `weights / (4 * H * W)` is
+    the antialiased coverage of each cell by each region and sums to the region's area; `weights > 0` marks the cells a
+    region touches under the bilinear support, the device-side analogue of the reference's
+    `create_roi_mask(all_touched=True)` for masks that are rasters already.  Deterministic, capturable, nothing
+    synchronises."""
+    h, w = _check_size(grid)
+    ids, rows = _check_region_ids(ids, num_regions, (h, w))
+    _lib.require_device(ids, "ids")
+    out = torch.empty((ids.shape[0], rows, h, w), dtype=torch.int64, device=ids.device)
+    ids = ids.contiguous()
+    for i in range(0, ids.shape[0], MAX_POOLED_MAPS):  # images a launch
+        _cell_weights(ids[i:i + MAX_POOLED_MAPS], rows, (h, w), out[i:i + MAX_POOLED_MAPS])
+    return out
+
+
+def pool_regions(maps: "EmbeddingBatch | Tensor", ids: Tensor, num_regions: int, *, normalize: bool = True,
+                 return_weights: bool = False) -> RegionVectors:
+    """A vector per region: `maps` (an `EmbeddingBatch` or float32 `[B, E, h, w]`) upsampled bilinearly to the pixels of
+    `ids` (int32 `[B, H, W]`) and averaged over each region's pixels -- computed as a weighted sum over cells with the
+    exact integer weights of `region_cell_weights`, in float64 chains of a fixed order (`isc_region_pool`), so neither the
+    `[B, E, H, W]` upsampling is written nor a float summed by atomics: deterministic bit for bit and capturable.
+
+    `ids` may have any `H, W`: an upsampled `Regions.ids`, or a mask drawn on the feature grid itself (`H == h, W == w`:
+    plain masked mean pooling); downsampling is defined as well.  `normalize=True` gives rows of unit length (a bank's
+    rows, in the text tower's space for a CLIP map), `False` the mean.  Rows of regions without pixels are zeros with
+    mass 0.  `return_weights` also returns the `[B, R, h, w]` weights.  Runs in passes of images whose weights stay within
+    256 MiB; the number of launches depends on the shapes alone, and nothing synchronises with the host."""
+    if isinstance(maps, EmbeddingBatch):
+        maps = maps.embeddings
+    maps = _check_float_tensor("maps", maps, 4, "[B, E, h, w]")
+    b, e, h, w = (int(v) for v in maps.shape)
+    if e < 1 or h < 1 or w < 1:
+        raise ValueError(f"maps {tuple(maps.shape)} must not be empty")
+    if h * w >= 2**31:
+        raise ValueError(f"a {h} x {w} map has 2^31 cells or more")
+    ids, rows = _check_region_ids(ids, num_regions, (h, w))
+    if ids.shape[0] != b:
+        raise ValueError(f"maps hold {b} images but ids {ids.shape[0]}")
+    if not isinstance(normalize, bool) or not isinstance(return_weights, bool):
+        raise TypeError("normalize and return_weights must be bools")
+    _lib.require_device(maps, "maps")
+    device = maps.device
+    if ids.device != device:
+        raise ValueError(f"maps are on {device} but ids on {ids.device}")
+    maps, ids = maps.contiguous(), ids.contiguous()
+    cells = h * w
+    step = max(1, min(POOL_PASS_BYTES // (rows * cells * 8), MAX_POOLED_MAPS))  # images a pass
+    vectors = torch.empty((b, rows, e), dtype=torch.float32, device=device)
+    mass = torch.empty((b, rows), dtype=torch.int64, device=device)
+    weights = torch.empty((b if return_weights else min(b, step), rows, h, w), dtype=torch.int64, device=device)
+    mode = _lib.ISC_POOL_UNIT if normalize else _lib.ISC_POOL_MEAN
+    lib = _lib.load()
+    for i in range(0, b, step):
+        n = min(step, b - i)
+        part = weights[i:i + n] if return_weights else weights[:n]
+        _cell_weights(ids[i:i + n], rows, (h, w), part)
+        with torch.cuda.device(device):
+            st = lib.isc_region_pool(maps[i:i + n].data_ptr(), n, e, cells, part.data_ptr(), rows, mode,
+                                     vectors[i:i + n].data_ptr(), mass[i:i + n].data_ptr(), _lib.stream_handle(device))
+        _lib.check(st, "isc_region_pool")
+    return RegionVectors(vectors, mass, weights if return_weights else None)

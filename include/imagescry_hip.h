@@ -1114,6 +1114,61 @@ int isc_label_regions_workspace_bytes(int B, int H, int W, size_t* bytes);
  * the tile borders afterwards -- where its code paths change (host only, host pointers). */
 int isc_label_regions_geometry(int* tile_w, int* tile_h);
 
+/* Regions back to vectors: the patch map pooled over every region's pixels, without the [B, E, H, W] upsampling of
+ * `interpolate(maps, (H, W), mode="bilinear")` and without a float atomic.  Bilinear upsampling is linear, so the sum of
+ * the upsampled map over a region's pixels is a weighted sum over CELLS; isc_region_cell_weights computes the weights,
+ * which are exact integers, and isc_region_pool the weighted sums.
+ *   ids        int32 [B, H, W], a region per pixel (isc_label_regions' region_ids, or any raster mask)
+ *   weights    int64 [B, R, h * w]
+ * Per axis of L pixels over l cells, pixel d has two taps: n = max((2d + 1) * l - L, 0), i0 = n / (2L) (rounded down),
+ * f = n - i0 * 2L, i1 = min(i0 + 1, l - 1); the weight of i0 is 2L - f, that of i1 is f: the taps of align_corners=False
+ * as exact rationals over 2L (isc_label_map's float32 taps are their rounding).  Where i1 == i0 both weights go to that
+ * one cell.  The weight of pixel (y, x) on cell (i, j) is the product of its row weight on i and its column weight on j:
+ * an integer, and the (at most) four of a pixel sum to 4 * H * W.
+ *   weights[b][r][i * w + j] = the sum of those products over the pixels of image b with ids == r.
+ * Pixels with ids < 0 (unlabeled, dropped) and ids >= R (regions beyond a truncated table) are skipped.  So the sum of
+ * row r is 4 * H * W * (the pixels of region r), weights / (4 * H * W) is the region's antialiased coverage of every
+ * cell, and weights > 0 marks the cells the region touches under the bilinear support.
+ * The call zeroes weights itself (a launch ahead of the kernel: garbage on entry is fine and a replayed graph
+ * starts from zero).  Only integer atomics are used -- a workgroup owns a tile_w x tile_h tile of pixels
+ * (isc_region_pool_geometry), sums equal (region, cell) keys along a wave's row and in an LDS table, and adds every key
+ * of the tile to memory once; keys that find no slot in the table are added directly -- so the result does not depend on
+ * the order in which they land: two runs give the same bytes, whatever B and the image's place in the batch.
+ * Limits: H, W, h, w, R >= 1 (ISC_ERR_INVALID_ARG); H * W <= 2^24 (every weight is then below 4 (HW)^2 = 2^50: exact in
+ * int64 and in a double), h * w < 2^31, R * h * w <= 2^25, B <= 65535 (ISC_ERR_UNSUPPORTED); ids 4-byte aligned, weights
+ * 8-byte (ISC_ERR_ALIGNMENT); ids or weights NULL is ISC_ERR_INVALID_ARG.  Everything is checked before anything is
+ * launched.  B == 0 returns ISC_OK without a launch.  No workspace, no host synchronisation, capturable. */
+int isc_region_cell_weights(const int32_t* ids, int B, int H, int W, int h, int w, int R, int64_t* weights, void* stream);
+
+/* The pixels a workgroup of isc_region_cell_weights owns -- where its code paths change (host only, host pointers). */
+int isc_region_pool_geometry(int* tile_w, int* tile_h);
+
+#define ISC_POOL_UNIT 0 /* rows of unit length */
+#define ISC_POOL_MEAN 1 /* the mean of the upsampled map over the region's pixels */
+
+/* A vector per (image, region): the map's cells weighted by one row of weights each.
+ *   maps       float [B, E, S], the NCHW map with S = h * w         weights  int64 [B, R, S] (isc_region_cell_weights)
+ *   out        float [B, R, E]                                      mass     int64 [B, R] or NULL
+ * For every (b, r):
+ *   mass = the sum of weights[b][r][c] over c, exact (4 * H * W * area for weights of isc_region_cell_weights);
+ *   s[e] = the float64 chain acc = fma((double)weights[b][r][c], (double)maps[b][e][c], acc) over c ascending from 0,
+ *          in which cells with weight 0 are SKIPPED, not multiplied: a NaN or inf cell outside the region's support does
+ *          not reach it;
+ *   ISC_POOL_MEAN: out[b][r][e] = (float)(s[e] / (double)mass);
+ *   ISC_POOL_UNIT: n = the chain n = fma(s[e], s[e], n) over e ascending from 0, out[b][r][e] = (float)(s[e] / sqrt(n)),
+ *          and a row of zeros if n == 0;
+ *   square root and division correctly rounded in float64, one rounding to float32.  A row with mass == 0 is all zeros
+ *   in both modes.  Non-finite cells inside the support give what this arithmetic gives.
+ * A row's bits depend on its own weights and its image's map only: not on B, the image's place in the batch or R.
+ * How: a workgroup per (b, r) scans its weight row, compacts the non-zero (cell, weight) pairs into LDS in ascending
+ * cell order, stages the gathered cells through LDS (loaded along c, read along e) and runs the chains with a lane per
+ * e.  One launch, any E >= 1 (ISC_ERR_INVALID_ARG below); a mode other than the two above is ISC_ERR_INVALID_ARG.
+ * Limits: S, R >= 1; S < 2^31, R * S <= 2^25, B <= 65535 (ISC_ERR_UNSUPPORTED); maps and out 4-byte aligned, weights and
+ * mass 8-byte (ISC_ERR_ALIGNMENT); maps, weights or out NULL is ISC_ERR_INVALID_ARG.  Everything is checked before
+ * anything is launched.  B == 0 returns ISC_OK without a launch.  No workspace, no host synchronisation, capturable. */
+int isc_region_pool(const float* maps, int B, int E, int S, const int64_t* weights, int R, int mode, float* out,
+                    int64_t* mass, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
