@@ -20,6 +20,9 @@ Public surface (same names as the reference where the reference has them):
 * `label_regions`, `Regions`                     -- connected regions of a label map: ids, boxes, areas, peaks (new)
 * `pool_regions`, `region_cell_weights`,
   `RegionVectors`                                -- mask-pooled vectors per region: objects as rows of a bank (new)
+* `create_roi_mask`                              -- reference src/imagescry/geometry.py, rasterised on the device
+* `rasterize_polygons`, `pack_polygons`,
+  `pool_polygons`, `PackedPolygons`              -- drawn polygons to region ids and to query vectors (new)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/imagescry_hip.h;
 PyTorch is used for device memory, streams and `torch.distributed` only.
@@ -42,14 +45,19 @@ from imagescry_amd.embedding import (
 from imagescry_amd.pipelines import EmbeddingPCAPipeline, EmbedSearchPipeline, SearchResult
 from imagescry_amd.segmentation import (
     LabelMaps,
+    PackedPolygons,
     Regions,
     RegionVectors,
     class_scores,
+    create_roi_mask,
     crop_windows,
     label_map,
     label_map_windows,
     label_regions,
+    pack_polygons,
+    pool_polygons,
     pool_regions,
+    rasterize_polygons,
     region_cell_weights,
     segment,
     segment_windows,
@@ -72,6 +80,7 @@ __all__ = [
     "KMeans",
     "LabelMaps",
     "PCA",
+    "PackedPolygons",
     "RangeResult",
     "Regions",
     "RegionVectors",
@@ -81,11 +90,15 @@ __all__ = [
     "ViTB16Embedder",
     "class_scores",
     "clip",
+    "create_roi_mask",
     "crop_windows",
     "label_map",
     "label_map_windows",
     "label_regions",
+    "pack_polygons",
+    "pool_polygons",
     "pool_regions",
+    "rasterize_polygons",
     "region_cell_weights",
     "segment",
     "segment_windows",

@@ -33,6 +33,8 @@ ISC_FARTHEST_MAX_PICKS = 1 << 20  # isc_bank_farthest
 ISC_ATT_PART_QUERY = 0  # isc_attention_f16_self*: which columns of qkv play query and key
 ISC_ATT_PART_KEY = 1
 ISC_POOL_UNIT, ISC_POOL_MEAN = 0, 1  # isc_region_pool
+ISC_FILL_EVENODD, ISC_FILL_NONZERO = 0, 1  # isc_rasterize_polygons
+ISC_RASTER_MAX_COORD = 1 << 23  # |q| of a vertex coordinate, in 1/256ths of a pixel
 ISC_ABI_VERSION = 4
 ISC_BUILD_ABLATION = 1
 ISC_GEMM_A_PACKED, ISC_GEMM_W_PACKED, ISC_GEMM_OUT_PACKED, ISC_GEMM_TILE_256, ISC_GEMM_TILE_128 = 1, 2, 4, 8, 16
@@ -380,6 +382,13 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     "isc_region_cell_weights": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "isc_region_pool_geometry": (c_int, [POINTER(c_int), POINTER(c_int)]),
     "isc_region_pool": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "isc_rasterize_polygons": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+         c_size_t, c_void_p],
+    ),
+    "isc_rasterize_polygons_workspace_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
+    "isc_rasterize_polygons_geometry": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
 }
 
 _lib: ctypes.CDLL | None = None

@@ -23,6 +23,11 @@ Regions back to vectors: `pool_regions` (or `Regions.embed`) pools a patch map o
 the bilinearly upsampled map over the mask, as a weighted sum over cells whose weights are exact integers
 (`isc_region_cell_weights`, `isc_region_pool`) -- so that an object is described by all of its patches and is a row of a
 bank like any other.
+
+Drawn regions: `rasterize_polygons` burns ROI polygons -- what an annotator drew -- onto a pixel grid as region ids on the
+device (`isc_rasterize_polygons`: an exact integer definition of rasterio's `rasterize`, with or without `all_touched`),
+`pack_polygons` snaps and flattens them on the host, `create_roi_mask` is the reference's `geometry.create_roi_mask`, and
+`pool_polygons` turns every drawn shape into a query vector.
 """
 
 from __future__ import annotations
@@ -31,6 +36,7 @@ import ctypes
 import math
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -40,7 +46,8 @@ from imagescry_amd.data import EmbeddingBatch
 __all__ = ["LabelMaps", "UNLABELED", "MAX_PROMPTS", "MAX_CLASSES", "class_scores", "label_map", "label_map_geometry",
            "segment", "window_grid", "crop_windows", "label_map_windows", "segment_windows", "Regions", "label_regions",
            "label_regions_geometry", "RegionVectors", "region_cell_weights", "pool_regions",
-           "region_pool_geometry"]
+           "region_pool_geometry", "PackedPolygons", "pack_polygons", "rasterize_polygons", "rasterize_geometry",
+           "create_roi_mask", "pool_polygons"]
 
 UNLABELED = 255  # the label of a pixel whose best score is NaN or below `min_score`
 MAX_PROMPTS = 1024  # isc_label_map: 1 <= C <= 1024
@@ -660,3 +667,270 @@ def pool_regions(maps: "EmbeddingBatch | Tensor", ids: Tensor, num_regions: int,
                                      vectors[i:i + n].data_ptr(), mass[i:i + n].data_ptr(), _lib.stream_handle(device))
         _lib.check(st, "isc_region_pool")
     return RegionVectors(vectors, mass, weights if return_weights else None)
+
+
+# ------------------------------------------------------------------------------------------------------ drawn regions
+RASTER_FRACTION = 256  # vertices are fixed point: q = 256 * coordinate
+MAX_RASTER_SIDE = 32768  # isc_rasterize_polygons: H, W <= 32768
+MAX_RASTER_IMAGES = 65535  # images a launch
+FILL_RULES = {"evenodd": _lib.ISC_FILL_EVENODD, "nonzero": _lib.ISC_FILL_NONZERO}
+
+
+@dataclass(frozen=True)
+class PackedPolygons:
+    """Polygons of B images, snapped to 1/256 pixel and flattened: what `isc_rasterize_polygons` reads.
+
+    vertices:    int32 `[V, 2]`, `(256 x, 256 y)`
+    ring_start:  int32 `[N + 1]`, ring n is `vertices[ring_start[n]:ring_start[n + 1]]`, closed
+    ring_region: int32 `[N]`, the region of the ring's shape; consecutive rings of one image with one value are one shape
+    image_start: int32 `[B + 1]`, image b owns rings `image_start[b]:image_start[b + 1]`
+    num_regions: the most shapes any image has, at least 1: the R of the tables downstream
+
+    The tensors may be refilled in place (same sizes) between the replays of a captured graph."""
+
+    vertices: Tensor
+    ring_start: Tensor
+    ring_region: Tensor
+    image_start: Tensor
+    num_regions: int
+
+    def to(self, device: str | torch.device) -> "PackedPolygons":
+        return PackedPolygons(self.vertices.to(device), self.ring_start.to(device), self.ring_region.to(device),
+                              self.image_start.to(device), self.num_regions)
+
+    def cpu(self) -> "PackedPolygons":
+        return self.to("cpu")
+
+    @property
+    def device(self) -> torch.device:
+        return self.vertices.device
+
+    def __len__(self) -> int:
+        return self.image_start.shape[0] - 1
+
+
+def rasterize_geometry() -> tuple[int, int, int]:
+    """(tile_w, tile_h, edge_chunk) of `isc_rasterize_polygons`."""
+    tw, th, ec = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().isc_rasterize_polygons_geometry(tw, th, ec), "isc_rasterize_polygons_geometry")
+    return tw.value, th.value, ec.value
+
+
+def _check_raster_size(name: str, size: object) -> tuple[int, int]:
+    try:
+        h, w = _check_size(size)
+    except (TypeError, ValueError) as exc:
+        raise type(exc)(str(exc).replace("size", name, 1)) from None
+    return h, w
+
+
+def _is_number(v: object) -> bool:
+    if isinstance(v, Tensor):
+        return v.ndim == 0
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+
+
+def _ring_array(ring: object) -> np.ndarray:
+    """One ring as float64 `[V, 2]`."""
+    if isinstance(ring, Tensor):
+        a = ring.detach().cpu().to(torch.float64).numpy()
+    else:
+        try:
+            a = np.asarray(ring if isinstance(ring, np.ndarray) else [tuple(float(c) for c in v) for v in ring],
+                           dtype=np.float64)
+        except (TypeError, ValueError) as exc:
+            raise TypeError(f"a ring must be a [V, 2] array-like of (x, y), got {type(ring).__name__}") from exc
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"a ring must have shape [V, 2], got {tuple(a.shape)}")
+    if a.shape[0] < 3:
+        raise ValueError(f"a ring needs at least 3 vertices, got {a.shape[0]}")
+    if not np.isfinite(a).all():
+        raise ValueError("a ring holds a coordinate that is not finite")
+    return a
+
+
+def _shape_rings(shape: object) -> list[np.ndarray]:
+    """The rings of one shape: a ring, a list of rings, a polygon-like (`.exterior.coords`, `.interiors`) or a
+    multipolygon-like (`.geoms`)."""
+    if hasattr(shape, "geoms"):
+        return [ring for part in shape.geoms for ring in _shape_rings(part)]
+    if hasattr(shape, "exterior"):
+        return [_ring_array(shape.exterior.coords), *(_ring_array(hole.coords) for hole in shape.interiors)]
+    if isinstance(shape, (Tensor, np.ndarray)):
+        return [_ring_array(ring) for ring in shape] if shape.ndim == 3 else [_ring_array(shape)]
+    if isinstance(shape, (list, tuple)):
+        if len(shape) == 0:
+            raise ValueError("a shape must hold at least one ring")
+        first = shape[0]
+        if isinstance(first, (list, tuple)) and len(first) == 2 and all(_is_number(v) for v in first):
+            return [_ring_array(shape)]
+        if isinstance(first, (Tensor, np.ndarray)) and first.ndim == 1:
+            return [_ring_array(np.stack([np.asarray(v, dtype=np.float64) for v in shape]))]
+        return [_ring_array(ring) for ring in shape]
+    raise TypeError(f"a shape must be a [V, 2] ring, a list of rings, or an object with .exterior / .geoms, "
+                    f"got {type(shape).__name__}")
+
+
+def pack_polygons(polygons: object, *, size: "tuple[int, int] | None" = None,
+                  extent: "tuple[int, int] | None" = None) -> PackedPolygons:
+    """Snap and flatten polygons on the host.  `polygons`: a list with one entry per image, each a list of shapes; the
+    region id of a shape is its place in that list.  A shape is a `[V, 2]` array-like or tensor of `(x, y)` (one ring), a
+    list of rings (an exterior and its holes, or the parts of a multipolygon), any object with `.exterior.coords` and
+    `.interiors`, or any object with `.geoms` holding such objects -- shapely's `Polygon` and `MultiPolygon` fit without
+    shapely being imported.  x runs right, y down, pixel `(y, x)` covers `[x, x + 1) x [y, y + 1)`.
+
+    With `size=(H, W)` and `extent=(H0, W0)` the polygons are given on an `H0 x W0` image and scaled onto `H x W`:
+    `sx = W / W0`, `sy = H / H0`; otherwise both are 1.  Snapping is `q = rint(x * sx * 256.0)`, left to right in
+    float64, halves to even.  `ValueError`: a ring of fewer than 3 vertices, a coordinate that is not finite, or
+    `|q| > 2^23` (32768 pixels)."""
+    sx = sy = 1.0
+    if size is not None:
+        out_h, out_w = _check_raster_size("size", size)
+    if extent is not None:
+        ext_h, ext_w = _check_raster_size("extent", extent)
+        if size is None:
+            raise ValueError("extent needs size: the grid the polygons are scaled onto")
+        sx, sy = out_w / ext_w, out_h / ext_h
+    if not isinstance(polygons, (list, tuple)):
+        raise TypeError(f"polygons must be a list with one list of shapes per image, got {type(polygons).__name__}")
+    verts: list[np.ndarray] = []
+    ring_start, ring_region, image_start = [0], [], [0]
+    most = 1
+    for shapes in polygons:
+        if not isinstance(shapes, (list, tuple)):
+            raise TypeError(f"every image's entry must be a list of shapes, got {type(shapes).__name__}")
+        most = max(most, len(shapes))
+        for region, shape in enumerate(shapes):
+            for ring in _shape_rings(shape):
+                q = np.stack([np.rint(ring[:, 0] * sx * 256.0), np.rint(ring[:, 1] * sy * 256.0)], axis=1)
+                if np.abs(q).max() > _lib.ISC_RASTER_MAX_COORD:
+                    raise ValueError(f"a vertex lies beyond {MAX_RASTER_SIDE} pixels from the origin after scaling")
+                verts.append(q.astype(np.int32))
+                ring_start.append(ring_start[-1] + q.shape[0])
+                ring_region.append(region)
+        image_start.append(len(ring_region))
+    if ring_start[-1] >= 2**31:
+        raise ValueError("2^31 vertices or more")
+    vertices = np.concatenate(verts, axis=0) if verts else np.zeros((0, 2), dtype=np.int32)
+    return PackedPolygons(torch.from_numpy(vertices), torch.tensor(ring_start, dtype=torch.int32),
+                          torch.tensor(ring_region, dtype=torch.int32), torch.tensor(image_start, dtype=torch.int32), most)
+
+
+def _check_packed(pack: PackedPolygons) -> None:
+    fields = (("vertices", pack.vertices), ("ring_start", pack.ring_start), ("ring_region", pack.ring_region),
+              ("image_start", pack.image_start))
+    for name, t in fields:
+        if not isinstance(t, Tensor) or t.dtype != torch.int32:
+            raise TypeError(f"PackedPolygons.{name} must be an int32 tensor")
+        if t.device != pack.vertices.device:
+            raise ValueError(f"PackedPolygons.{name} is on {t.device} but vertices on {pack.vertices.device}")
+    if pack.vertices.ndim != 2 or pack.vertices.shape[1] != 2:
+        raise ValueError(f"PackedPolygons.vertices must have shape [V, 2], got {tuple(pack.vertices.shape)}")
+    if pack.ring_region.ndim != 1 or pack.ring_start.shape != (pack.ring_region.shape[0] + 1,):
+        raise ValueError("PackedPolygons.ring_start must have one entry more than ring_region")
+    if pack.image_start.ndim != 1 or pack.image_start.shape[0] < 1:
+        raise ValueError("PackedPolygons.image_start must have shape [B + 1]")
+
+
+def _some(t: Tensor) -> Tensor:
+    """`t`, or one element where it is empty: the kernels take no NULL."""
+    return t.contiguous() if t.numel() else torch.zeros((2,), dtype=t.dtype, device=t.device)
+
+
+def rasterize_polygons(polygons: object, size: "tuple[int, int]", *, extent: "tuple[int, int] | None" = None,
+                       fill_rule: str = "evenodd", all_touched: bool = False, num_regions: int | None = None,
+                       return_counts: bool = False,
+                       device: "str | torch.device | None" = None) -> "Tensor | tuple[Tensor, Tensor]":
+    """Polygons to region ids on the device (`isc_rasterize_polygons`, include/imagescry_hip.h has the definition): int32
+    `[B, H, W]`, every pixel the region of the LAST shape of its image that covers it (rasterio's order for a list of
+    shapes), -1 where none does; with `return_counts` also int32 `[B, R]`, the pixels of every region.
+
+    `polygons`: what `pack_polygons` takes (packed here with `size` and `extent`) or a `PackedPolygons`, which is moved to
+    `device` if it lives on the CPU; `device=None` is where the pack lives, else the current GPU.  A shape covers a pixel
+    whose centre lies inside it -- by the parity of crossings (`fill_rule="evenodd"`: holes are holes whatever their
+    orientation) or by the winding number (`"nonzero"`) -- under the top-left rule, so shapes that share an edge partition
+    the pixels; with `all_touched=True` also every pixel whose interior an edge of the shape passes through (rasterio's
+    `all_touched`, GDAL's ALL_TOUCHED).  `extent=(H0, W0)`: the polygons are given on an `H0 x W0` image.  `num_regions`:
+    R, by default the pack's; shapes at or beyond it are skipped.  Integers throughout: deterministic, the same for an
+    image wherever it stands in a batch, capturable; nothing synchronises with the host."""
+    big_h, big_w = _check_raster_size("size", size)
+    if big_h > MAX_RASTER_SIDE or big_w > MAX_RASTER_SIDE:
+        raise ValueError(f"size {big_h} x {big_w} exceeds {MAX_RASTER_SIDE} pixels a side")
+    if not isinstance(fill_rule, str) or fill_rule not in FILL_RULES:
+        raise ValueError(f"fill_rule must be one of {sorted(FILL_RULES)}, got {fill_rule!r}")
+    if not isinstance(all_touched, bool) or not isinstance(return_counts, bool):
+        raise TypeError("all_touched and return_counts must be bools")
+    if isinstance(polygons, PackedPolygons):
+        if extent is not None:
+            raise ValueError("a PackedPolygons is scaled already: give extent to pack_polygons")
+        pack = polygons
+    else:
+        pack = pack_polygons(polygons, size=(big_h, big_w), extent=extent)
+    _check_packed(pack)
+    rows = pack.num_regions if num_regions is None else num_regions
+    rows = _check_count("num_regions", rows)
+    if device is not None:
+        device = torch.device(device)
+    if pack.device.type == "cpu":
+        pack = pack.to(torch.device("cuda", torch.cuda.current_device()) if device is None else device)
+    elif device is not None and device != pack.device and (device.index is not None or device.type != pack.device.type):
+        raise ValueError(f"the polygons are on {pack.device} but device is {device}")
+    _lib.require_device(pack.vertices, "polygons")
+    device = pack.device
+    b, rings = len(pack), int(pack.ring_region.shape[0])
+    ids = torch.empty((b, big_h, big_w), dtype=torch.int32, device=device)
+    counts = torch.empty((b, rows), dtype=torch.int32, device=device) if return_counts else None
+    lib = _lib.load()
+    need = ctypes.c_size_t()
+    _lib.check(lib.isc_rasterize_polygons_workspace_bytes(rings, need), "isc_rasterize_polygons_workspace_bytes")
+    workspace = torch.empty((need.value,), dtype=torch.uint8, device=device)
+    vertices, ring_start, ring_region = _some(pack.vertices), pack.ring_start.contiguous(), _some(pack.ring_region)
+    image_start = pack.image_start.contiguous()
+    for i in range(0, b, MAX_RASTER_IMAGES):  # images a launch; image_start holds offsets into all the rings
+        n = min(MAX_RASTER_IMAGES, b - i)
+        with torch.cuda.device(device):
+            st = lib.isc_rasterize_polygons(vertices.data_ptr(), ring_start.data_ptr(), ring_region.data_ptr(),
+                                            image_start[i:].data_ptr(), n, big_h, big_w, rows, FILL_RULES[fill_rule],
+                                            int(all_touched), ids[i:i + n].data_ptr(),
+                                            None if counts is None else counts[i:i + n].data_ptr(), workspace.data_ptr(),
+                                            need.value, _lib.stream_handle(device))
+        _lib.check(st, "isc_rasterize_polygons")
+    return (ids, counts) if return_counts else ids
+
+
+def create_roi_mask(roi: object, original_image_shape: "tuple[int, int]", feature_map_shape: "tuple[int, int]",
+                    class_index: int = 1, *, device: "str | torch.device | None" = None) -> Tensor:
+    """The reference's `geometry.create_roi_mask`, on the device: `roi` -- one shape or a list of shapes (what
+    `pack_polygons` takes for one image), drawn on an image of `original_image_shape = (h, w)` -- burnt onto the
+    `feature_map_shape = (hf, wf)` grid with `all_touched=True`: int64 `[hf, wf]` holding `class_index` where any shape
+    covers or touches the cell and 0 elsewhere."""
+    if isinstance(class_index, bool) or not isinstance(class_index, int):
+        raise TypeError(f"class_index must be an int, got {type(class_index).__name__}")
+    extent = tuple(int(v) for v in original_image_shape)
+    grid = tuple(int(v) for v in feature_map_shape)
+    single = not isinstance(roi, (list, tuple)) or (
+        len(roi) > 0 and isinstance(roi[0], (list, tuple)) and len(roi[0]) == 2 and all(_is_number(v) for v in roi[0]))
+    shapes = [roi] if single else list(roi)
+    ids = rasterize_polygons([shapes], grid, extent=extent, all_touched=True, device=device)
+    return (ids[0] >= 0).to(torch.int64) * class_index
+
+
+def pool_polygons(maps: "EmbeddingBatch | Tensor", polygons: object, size: "tuple[int, int]", *,
+                  extent: "tuple[int, int] | None" = None, fill_rule: str = "evenodd", all_touched: bool = False,
+                  **pool_kw: object) -> RegionVectors:
+    """A vector per drawn shape: `pool_regions(maps, rasterize_polygons(polygons, size, ...), R, **pool_kw)` with R the
+    most shapes an image has -- `maps` upsampled to `size` and averaged over every shape's pixels, rows of unit length by
+    default: what `bank.search` takes for "more like what I outlined"."""
+    tensor = maps.embeddings if isinstance(maps, EmbeddingBatch) else maps
+    if not isinstance(tensor, Tensor):
+        raise TypeError(f"maps must be an EmbeddingBatch or a torch.Tensor, got {type(maps).__name__}")
+    _lib.require_device(tensor, "maps")
+    pack = polygons if isinstance(polygons, PackedPolygons) else pack_polygons(polygons, size=_check_raster_size("size", size),
+                                                                              extent=extent)
+    if isinstance(polygons, PackedPolygons) and extent is not None:
+        raise ValueError("a PackedPolygons is scaled already: give extent to pack_polygons")
+    if len(pack) != tensor.shape[0]:
+        raise ValueError(f"maps hold {tensor.shape[0]} images but the polygons {len(pack)}")
+    ids = rasterize_polygons(pack, size, fill_rule=fill_rule, all_touched=all_touched,
+                             device=tensor.device if pack.device.type == "cpu" else None)
+    return pool_regions(tensor, ids, pack.num_regions, **pool_kw)

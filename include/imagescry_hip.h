@@ -1169,6 +1169,69 @@ int isc_region_pool_geometry(int* tile_w, int* tile_h);
 int isc_region_pool(const float* maps, int B, int E, int S, const int64_t* weights, int R, int mode, float* out,
                     int64_t* mass, void* stream);
 
+#define ISC_FILL_EVENODD 0 /* a shape covers a centre that an odd number of its edges cross */
+#define ISC_FILL_NONZERO 1 /* ... whose winding sum over its edges is not zero */
+#define ISC_RASTER_MAX_COORD (1 << 23) /* |q| of a vertex coordinate: 32768 pixels in 1/256ths */
+
+/* Drawn regions: ROI polygons burnt onto a pixel grid as region ids -- the raster isc_region_cell_weights takes, from
+ * outlines a person drew instead of a mask a model produced.  What rasterio's `rasterize(shapes, all_touched=...)` does on
+ * the host, defined exactly and in integers, so that the answer does not depend on rounding, on the order of the edges
+ * or on where the work is split.
+ *
+ * Coordinates.  x runs right, y down; pixel (y, x) covers [x, x + 1) x [y, y + 1).  A vertex is (qx, qy), int32 fixed
+ * point with 8 fractional bits: q = 256 * coordinate.  The centre of pixel (y, x) is (256 x + 128, 256 y + 128).  Every
+ * coordinate is CLAMPED to [-ISC_RASTER_MAX_COORD, ISC_RASTER_MAX_COORD] as it is loaded, so any int32 is defined.  With
+ * H, W <= 32768 every difference then fits 2^25 and every product 2^50: int64 holds all of the below.
+ *   vertices     int32 [V, 2], (qx, qy)
+ *   ring_start   int32 [N + 1], ring n is vertices[ring_start[n] .. ring_start[n + 1]); closed: the last vertex joins the
+ *                first.  Edges of zero length are ignored (a repeated closing vertex is harmless).
+ *   ring_region  int32 [N]
+ *   image_start  int32 [B + 1], image b owns rings [image_start[b], image_start[b + 1])
+ * The offsets are trusted: non-decreasing and inside their arrays.
+ * Shapes.  A maximal run of consecutive rings of one image with EQUAL ring_region values is one shape (an exterior and
+ * its holes, or a multipolygon); its region is that value, and a run whose value is < 0 or >= R is skipped as a whole
+ * (and still separates the runs before and after it).
+ * Centre rule.  For a centre C and an edge A -> B: the edge is UPWARD if Ay <= Cy < By, DOWNWARD if By <= Cy < Ay, and
+ * does not count otherwise (horizontal edges never do).  With d = (Bx - Ax)(Cy - Ay) - (By - Ay)(Cx - Ax), an upward
+ * edge crosses if d > 0 and adds +1 to the winding, a downward edge crosses if d < 0 and adds -1.  A shape COVERS the
+ * pixel if the crossings of all its rings are odd in number (ISC_FILL_EVENODD) or if its winding sum is not zero
+ * (ISC_FILL_NONZERO).  This is the top-left rule: a centre on a left or top edge is in, one on a right or bottom edge
+ * is out, so shapes that share an edge partition the pixels.
+ * Touch rule (all_touched != 0).  A shape also covers a pixel if one of its edges of non-zero length meets the pixel's
+ * OPEN square (x0, x1) x (y0, y1) = (256 x, 256 x + 256) x (256 y, 256 y + 256): min(Ax, Bx) < x1 and max(Ax, Bx) > x0;
+ * min(Ay, By) < y1 and max(Ay, By) > y0; and over the four corners P of the square, e(P) = (Bx - Ax)(Py - Ay) -
+ * (By - Ay)(Px - Ax) is strictly negative at one and strictly positive at another.  An edge along a pixel border, or
+ * through a corner only, does not touch.  With the centre rule this marks the pixels the shape overlaps with positive
+ * area or whose interior its boundary crosses.
+ * Painter's order.  ids[b][y][x] = the region of the LAST shape of image b, in ring order, that covers the pixel; -1 if
+ * none does.  counts[b][r] (or NULL) = the pixels of image b with id r.
+ *
+ * How: a launch writes the clamped bounding box of every ring into the workspace.  Then a workgroup owns a tile_w x
+ * tile_h tile of pixels (isc_rasterize_polygons_geometry), walks the image's rings in order, skips the rings whose box
+ * misses the tile -- exact: a closed ring adds no crossing parity and no winding to a centre outside its box -- and stages
+ * the others' edges through LDS edge_chunk at a time, dropping the edges that cannot count for the tile's rows (and,
+ * without all_touched, those not right of its first centre).  Crossing parity, winding and the touched flag of the open
+ * shape live in registers across chunks and rings.  counts is zeroed by a launch of its own, combined per tile in LDS
+ * and added with integer atomics.  Two launches, three with counts; the same bytes on every run and wherever an image
+ * stands in the batch.  No host synchronisation, capturable; the polygon arrays may be refilled in place between replays.
+ * Workspace: isc_rasterize_polygons_workspace_bytes(N), 16 bytes a ring, 16-byte aligned, garbage on entry is fine.  N is
+ * not an argument: rings beyond the workspace's capacity are rasterised without the box test, with the same result.
+ * Limits: 1 <= H, W <= 32768, H * W < 2^31, B <= 65535 (ISC_ERR_UNSUPPORTED); H, W, R < 1, B < 0, a fill rule other than
+ * the two above, or vertices, ring_start, ring_region, image_start or ids NULL: ISC_ERR_INVALID_ARG.  ISC_ERR_WORKSPACE:
+ * workspace NULL or below 16 bytes.  ISC_ERR_ALIGNMENT: vertices off 8 bytes, workspace off 16, any other pointer off 4.
+ * Everything is checked before anything is launched.  B == 0 returns ISC_OK without a launch. */
+int isc_rasterize_polygons(const int32_t* vertices, const int32_t* ring_start, const int32_t* ring_region,
+                           const int32_t* image_start, int B, int H, int W, int R, int fill_rule, int all_touched,
+                           int32_t* ids, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The workspace of isc_rasterize_polygons for N rings in all (host only, host pointer).  N < 0 is
+ * ISC_ERR_INVALID_ARG, N >= 2^31 ISC_ERR_UNSUPPORTED. */
+int isc_rasterize_polygons_workspace_bytes(int64_t num_rings, size_t* bytes);
+
+/* The tile of pixels a workgroup of isc_rasterize_polygons owns and the edges it stages at a time -- where its code
+ * paths change (host only, host pointers). */
+int isc_rasterize_polygons_geometry(int* tile_w, int* tile_h, int* edge_chunk);
+
 #ifdef __cplusplus
 }
 #endif
