@@ -23,6 +23,7 @@ Public surface (same names as the reference where the reference has them):
 * `create_roi_mask`                              -- reference src/imagescry/geometry.py, rasterised on the device
 * `rasterize_polygons`, `pack_polygons`,
   `pool_polygons`, `PackedPolygons`              -- drawn polygons to region ids and to query vectors (new)
+* `trace_regions`, `RegionOutlines`              -- region ids back to polygon rings: outlines, holes, areas (new)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/imagescry_hip.h;
 PyTorch is used for device memory, streams and `torch.distributed` only.
@@ -46,6 +47,7 @@ from imagescry_amd.pipelines import EmbeddingPCAPipeline, EmbedSearchPipeline, S
 from imagescry_amd.segmentation import (
     LabelMaps,
     PackedPolygons,
+    RegionOutlines,
     Regions,
     RegionVectors,
     class_scores,
@@ -61,6 +63,7 @@ from imagescry_amd.segmentation import (
     region_cell_weights,
     segment,
     segment_windows,
+    trace_regions,
     window_grid,
 )
 from imagescry_amd.search import EmbeddingBank, RangeResult, RowFilter, SearchHandle, shard_bounds
@@ -82,6 +85,7 @@ __all__ = [
     "PCA",
     "PackedPolygons",
     "RangeResult",
+    "RegionOutlines",
     "Regions",
     "RegionVectors",
     "RowFilter",
@@ -103,6 +107,7 @@ __all__ = [
     "segment",
     "segment_windows",
     "siglip",
+    "trace_regions",
     "window_grid",
     "l2_normalize_channels",
     "ImageBatch",

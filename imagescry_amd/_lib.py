@@ -389,6 +389,13 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     ),
     "isc_rasterize_polygons_workspace_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
     "isc_rasterize_polygons_geometry": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "isc_trace_regions": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "isc_trace_regions_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "isc_trace_regions_geometry": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
 }
 
 _lib: ctypes.CDLL | None = None

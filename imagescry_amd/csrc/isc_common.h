@@ -85,3 +85,26 @@ __device__ __forceinline__ float isc_wave_max(float v) {
     for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
     return v;
 }
+
+// ---- workgroup-level scan (256 threads) ---------------------------------------------------------
+// -> the sum of v over the threads before this one (256 threads); `total` = over all.  wave_sums: 4 ints of LDS.
+__device__ __forceinline__ int isc_block_exclusive_scan(int v, int* wave_sums, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += up;
+    }
+    __syncthreads();  // an earlier scan's sums are consumed
+    if (lane == 63) wave_sums[wave] = incl;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (w < wave) before += wave_sums[w];
+        total += wave_sums[w];
+    }
+    return before + incl - v;
+}

@@ -240,28 +240,6 @@ __device__ __forceinline__ bool kept_root(const int32_t* par, const int32_t* are
     return p < hw && par[p] == p && area[p] >= min_area;
 }
 
-// -> the sum of v over the threads before this one (256 threads); `total` = over all.  wave_sums: 4 ints of LDS.
-__device__ __forceinline__ int block_exclusive_scan(int v, int* wave_sums, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    __syncthreads();  // an earlier scan's sums are consumed
-    if (lane == 63) wave_sums[wave] = incl;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        if (w < wave) before += wave_sums[w];
-        total += wave_sums[w];
-    }
-    return before + incl - v;
-}
-
 __global__ __launch_bounds__(kRegionThreads) void k_regions_count(const int32_t* __restrict__ parent,
                                                                   const int32_t* __restrict__ area, int hw, int min_area,
                                                                   int nchunks, int32_t* __restrict__ chunk_count) {
@@ -273,7 +251,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_regions_count(const int32_t*
     for (int k = 0; k < kRegionRounds; ++k)
         mine += kept_root(parent + base, area + base, hw, p0 + k * kRegionThreads, min_area) ? 1 : 0;
     int total;
-    block_exclusive_scan(mine, wave_sums, total);
+    isc_block_exclusive_scan(mine, wave_sums, total);
     if (threadIdx.x == 0) chunk_count[(size_t)blockIdx.y * nchunks + blockIdx.x] = total;
 }
 
@@ -287,7 +265,7 @@ __global__ __launch_bounds__(256) void k_regions_offsets(int32_t* __restrict__ c
         const int i = i0 + threadIdx.x;
         const int v = i < nchunks ? c[i] : 0;
         int total;
-        const int before = block_exclusive_scan(v, wave_sums, total);
+        const int before = isc_block_exclusive_scan(v, wave_sums, total);
         if (i < nchunks) c[i] = running + before;
         running += total;
     }
@@ -312,7 +290,7 @@ __global__ __launch_bounds__(kRegionThreads) void k_regions_number(
         const int a = root ? area[base + p] : 0;
         const bool kept = root && a >= min_area;
         int total;
-        const int r = at + block_exclusive_scan(kept ? 1 : 0, wave_sums, total);
+        const int r = at + isc_block_exclusive_scan(kept ? 1 : 0, wave_sums, total);
         at += total;
         if (!root) continue;
         area[base + p] = kept ? r : -1;

@@ -28,6 +28,10 @@ Drawn regions: `rasterize_polygons` burns ROI polygons -- what an annotator drew
 device (`isc_rasterize_polygons`: an exact integer definition of rasterio's `rasterize`, with or without `all_touched`),
 `pack_polygons` snaps and flattens them on the host, `create_roi_mask` is the reference's `geometry.create_roi_mask`, and
 `pool_polygons` turns every drawn shape into a query vector.
+
+Outlines: `trace_regions` (or `Regions.outlines`) turns region ids back into polygon rings on the device
+(`isc_trace_regions`: rasterio's `shapes`, defined exactly) -- corners only, holes as rings of negative area, laid out as
+a `PackedPolygons` that `rasterize_polygons` takes as it is -- and `RegionOutlines.shapes()` brings them to the host.
 """
 
 from __future__ import annotations
@@ -47,7 +51,7 @@ __all__ = ["LabelMaps", "UNLABELED", "MAX_PROMPTS", "MAX_CLASSES", "class_scores
            "segment", "window_grid", "crop_windows", "label_map_windows", "segment_windows", "Regions", "label_regions",
            "label_regions_geometry", "RegionVectors", "region_cell_weights", "pool_regions",
            "region_pool_geometry", "PackedPolygons", "pack_polygons", "rasterize_polygons", "rasterize_geometry",
-           "create_roi_mask", "pool_polygons"]
+           "create_roi_mask", "pool_polygons", "RegionOutlines", "trace_regions", "trace_geometry"]
 
 UNLABELED = 255  # the label of a pixel whose best score is NaN or below `min_score`
 MAX_PROMPTS = 1024  # isc_label_map: 1 <= C <= 1024
@@ -427,6 +431,13 @@ class Regions:
         patch map over the region's pixels, with `label`, `num` and `indices` carried over."""
         out = pool_regions(maps, self.ids, int(self.label.shape[1]), **kw)
         return RegionVectors(out.vectors, out.mass, out.weights, self.label, self.num, self.indices)
+
+    def outlines(self, **kw: object) -> "RegionOutlines":
+        """`trace_regions(self.ids, R, **kw)`, R the rows of these tables: the outline of every region as polygon rings,
+        with `label`, `num` and `indices` carried over.  Pass the `connectivity` the regions were found with."""
+        out = trace_regions(self.ids, int(self.label.shape[1]), **kw)
+        return RegionOutlines(out.packed, out.ring_area2, out.num_rings, out.num_vertices, out.size, out.max_rings,
+                              out.max_vertices, self.label, self.num, self.indices)
 
 
 def label_regions_geometry() -> tuple[int, int]:
@@ -934,3 +945,156 @@ def pool_polygons(maps: "EmbeddingBatch | Tensor", polygons: object, size: "tupl
     ids = rasterize_polygons(pack, size, fill_rule=fill_rule, all_touched=all_touched,
                              device=tensor.device if pack.device.type == "cpu" else None)
     return pool_regions(tensor, ids, pack.num_regions, **pool_kw)
+
+
+# ----------------------------------------------------------------------------------------------------- region outlines
+MAX_TRACE_PIXELS = 2**29  # isc_trace_regions: H * W < 2^29, the 4 H W possible vertices are counted in an int32
+
+
+@dataclass(frozen=True)
+class RegionOutlines:
+    """What `trace_regions` returns: the outlines of the regions of B id maps as closed rings on the pixel lattice, N =
+    `max_rings` rows and V = `max_vertices` vertices an image.
+
+    packed:       a `PackedPolygons` over the call's four arrays (a view, nothing copied): vertices `[B * V, 2]`,
+                  ring_start `[B * (N + 1) + 1]`, ring_region `[B * (N + 1)]`, image_start `[B + 1]`.  Image b owns rings
+                  `b * (N + 1) + j`; unused rows have region -1 and no vertices.  `rasterize_polygons(packed, size,
+                  num_regions=R)` gives back the ids under either fill rule.
+    ring_area2:   int64 `[B, N]`, twice the signed area: positive for a ring with its region inside, negative for a hole,
+                  0 for unused rows
+    num_rings, num_vertices: int32 `[B]`, the TRUE counts, also above N and V.  An image that does not fit is written as
+                  empty; `complete()` tells, and the counts are the capacities to retry with.
+    size:         `(H, W)`;  max_rings, max_vertices: N and V
+    label, num, indices: carried over by `Regions.outlines`, else None."""
+
+    packed: PackedPolygons
+    ring_area2: Tensor
+    num_rings: Tensor
+    num_vertices: Tensor
+    size: tuple[int, int]
+    max_rings: int
+    max_vertices: int
+    label: Tensor | None = None
+    num: Tensor | None = None
+    indices: Tensor | None = None
+
+    def to(self, device: str | torch.device) -> "RegionOutlines":
+        return RegionOutlines(self.packed.to(device), self.ring_area2.to(device), self.num_rings.to(device),
+                              self.num_vertices.to(device), self.size, self.max_rings, self.max_vertices,
+                              *(None if t is None else t.to(device) for t in (self.label, self.num, self.indices)))
+
+    def cpu(self) -> "RegionOutlines":
+        return self.to("cpu")
+
+    @property
+    def device(self) -> torch.device:
+        return self.ring_area2.device
+
+    def __len__(self) -> int:
+        return self.ring_area2.shape[0]
+
+    def complete(self) -> Tensor:
+        """bool `[B]`: the image's rings and vertices fit `max_rings` and `max_vertices`."""
+        return (self.num_rings <= self.max_rings) & (self.num_vertices <= self.max_vertices)
+
+    def holes(self) -> Tensor:
+        """bool `[B, N]`: the ring is a hole (`ring_area2 < 0`)."""
+        return self.ring_area2 < 0
+
+    def shapes(self, *, strict: bool = True) -> "list[list[list[np.ndarray]]]":
+        """The outlines on the host -- the one call here that synchronises.  Per image a list of length R (the
+        `num_regions` of the call); entry r is the list of that region's rings as float64 `[n, 2]` arrays of `(x, y)` in
+        pixels, ordered by start vertex.  A non-empty entry is what `pack_polygons` takes for a shape.  For a connected
+        region it is the exterior followed by its holes: the arguments of `shapely.Polygon(shell, holes)`.  A region of
+        several components is a list of rings for even-odd fill, not a list of polygons: holes are not assigned to
+        exteriors.  An incomplete image (`complete()`) raises `ValueError` unless `strict=False`, with which it is
+        empty."""
+        if not isinstance(strict, bool):
+            raise TypeError("strict must be a bool")
+        n = self.max_rings
+        host = self.cpu()
+        fits = host.complete().tolist()
+        if strict and not all(fits):
+            b = fits.index(False)
+            raise ValueError(f"image {b} has {int(host.num_rings[b])} rings and {int(host.num_vertices[b])} vertices: "
+                             f"beyond max_rings = {n} or max_vertices = {self.max_vertices}; trace it again with those")
+        vertices = host.packed.vertices.to(torch.float64).numpy() / RASTER_FRACTION
+        start = host.packed.ring_start.numpy()
+        region = host.packed.ring_region.numpy()
+        out = []
+        for b in range(len(host)):
+            per_region: list[list[np.ndarray]] = [[] for _ in range(host.packed.num_regions)]
+            for j in range(min(int(host.num_rings[b]), n) if fits[b] else 0):
+                k = b * (n + 1) + j
+                per_region[int(region[k])].append(vertices[start[k]:start[k + 1]].copy())
+            out.append(per_region)
+        return out
+
+
+def trace_geometry() -> tuple[int, int, int, int]:
+    """(pixel_chunk, node_chunk, ring_tile, node_pass) of `isc_trace_regions`."""
+    pc, nc, rt, np_ = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().isc_trace_regions_geometry(pc, nc, rt, np_), "isc_trace_regions_geometry")
+    return pc.value, nc.value, rt.value, np_.value
+
+
+def trace_regions(ids: Tensor, num_regions: int, *, connectivity: int = 8, max_rings: int | None = None,
+                  max_vertices: int | None = None) -> RegionOutlines:
+    """Region ids back to outlines on the device (`isc_trace_regions`, include/imagescry_hip.h has the definition): the
+    boundary of every region r in `[0, num_regions)` of int32 `[B, H, W]` `ids` as closed rings of lattice vertices --
+    corners only, the region on the right of the direction of travel, holes as rings of negative area -- ordered by
+    (region, start vertex).  The inverse of `rasterize_polygons`, rasterio's `shapes`.
+
+    `connectivity`: where two pixels of a region meet at a corner only, 8 runs one ring through the corner and 4 keeps
+    the rings apart; use what `label_regions` used.  `max_rings` (N) and `max_vertices` (V): the rows an image has; the
+    defaults `2 * num_regions` and `max(4096, H * W // 4)` are heuristics, not bounds -- the worst case is `H * W` rings
+    and `4 * H * W` vertices -- and `RegionOutlines.num_rings` / `.num_vertices` hold the true counts: an image beyond
+    either comes out empty, `complete()` says so without a host read here, and the counts are what to call again with.
+    Integers throughout: deterministic, the same for an image wherever it stands in a batch, capturable.  Nothing
+    synchronises with the host."""
+    if not isinstance(ids, Tensor):
+        raise TypeError(f"ids must be a torch.Tensor, got {type(ids).__name__}")
+    if ids.dtype != torch.int32:
+        raise TypeError(f"ids must be int32, got {ids.dtype}")
+    if ids.ndim != 3:
+        raise ValueError(f"ids must have shape [B, H, W], got {tuple(ids.shape)}")
+    rows = _check_count("num_regions", num_regions)
+    if isinstance(connectivity, bool) or not isinstance(connectivity, int):
+        raise TypeError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
+    b, big_h, big_w = (int(v) for v in ids.shape)
+    _check_size((big_h, big_w))
+    if big_h > MAX_RASTER_SIDE or big_w > MAX_RASTER_SIDE or big_h * big_w >= MAX_TRACE_PIXELS:
+        raise ValueError(f"ids of {big_h} x {big_w} exceed {MAX_RASTER_SIDE} pixels a side or 2^29 pixels")
+    if b > MAX_RASTER_IMAGES:
+        raise ValueError(f"at most {MAX_RASTER_IMAGES} images a call, got {b}")
+    n = _check_count("max_rings", 2 * rows if max_rings is None else max_rings)
+    v = _check_count("max_vertices", max(4096, big_h * big_w // 4) if max_vertices is None else max_vertices)
+    if max(b, 1) * (n + 1) >= 2**31 or max(b, 1) * v >= 2**31:
+        raise ValueError(f"B * (max_rings + 1) and B * max_vertices must stay below 2^31, got B = {b}, {n} and {v}")
+    _lib.require_device(ids, "ids")
+    device = ids.device
+    ids = ids.contiguous()
+    lib = _lib.load()
+    need = ctypes.c_size_t()
+    _lib.check(lib.isc_trace_regions_workspace_bytes(b, big_h, big_w, need), "isc_trace_regions_workspace_bytes")
+
+    def empty(*shape: int, dtype: torch.dtype = torch.int32) -> Tensor:
+        return torch.empty(shape, dtype=dtype, device=device)
+
+    vertices, ring_start, ring_region = empty(b * v, 2), empty(b * (n + 1) + 1), empty(b * (n + 1))
+    image_start, area2 = empty(b + 1), empty(b, n, dtype=torch.int64)
+    num_rings, num_vertices = empty(b), empty(b)
+    if b == 0:
+        ring_start.zero_()
+        image_start.zero_()
+    workspace = torch.empty((need.value,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        st = lib.isc_trace_regions(ids.data_ptr(), b, big_h, big_w, rows, connectivity, n, v, vertices.data_ptr(),
+                                   ring_start.data_ptr(), ring_region.data_ptr(), image_start.data_ptr(),
+                                   area2.data_ptr(), num_rings.data_ptr(), num_vertices.data_ptr(), workspace.data_ptr(),
+                                   need.value, _lib.stream_handle(device))
+    _lib.check(st, "isc_trace_regions")
+    return RegionOutlines(PackedPolygons(vertices, ring_start, ring_region, image_start, rows), area2, num_rings,
+                          num_vertices, (big_h, big_w), n, v)

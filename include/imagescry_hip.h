@@ -1232,6 +1232,73 @@ int isc_rasterize_polygons_workspace_bytes(int64_t num_rings, size_t* bytes);
  * paths change (host only, host pointers). */
 int isc_rasterize_polygons_geometry(int* tile_w, int* tile_h, int* edge_chunk);
 
+/* Region outlines: a raster of region ids back to polygon rings -- the inverse of isc_rasterize_polygons, what rasterio
+ * calls `shapes`, defined exactly and in integers.
+ *   ids   int32 [B, H, W].  A pixel belongs to region r if ids == r and 0 <= r < R; every other value is "no region".
+ * Lattice vertices are (x, y) with 0 <= x <= W and 0 <= y <= H; x runs right, y down; pixel (y, x) covers
+ * [x, x + 1) x [y, y + 1).
+ * Edges.  Pixel (y, x) of region r has up to four directed boundary edges; side s is present if the neighbour across it
+ * is outside the image or not of region r:
+ *   side 0 (top)     (x, y)         -> (x + 1, y)       east         side 1 (right)  (x + 1, y)  -> (x + 1, y + 1)  south
+ *   side 2 (bottom)  (x + 1, y + 1) -> (x, y + 1)       west         side 3 (left)   (x, y + 1)  -> (x, y)          north
+ * The region is always on the right of the direction of travel.  The KEY of an edge is 4 * (y * W + x) + s.
+ * Successor.  The successor of an edge is the edge of the same region that starts where it ends.  There is one such
+ * edge, except at a SADDLE: a vertex whose two diagonal pixels are of r and whose other two are not.  There, with
+ * connectivity 4 the successor is the edge of the same pixel (a right turn: the two pixels stay apart), with
+ * connectivity 8 that of the other pixel (a left turn: the ring passes through the vertex twice).  The successor map is a
+ * permutation of the edges; its cycles are the RINGS.
+ * Vertices.  The vertices of a ring are the start vertices of those of its edges whose predecessor runs in another
+ * direction -- the corners only, so a ring has at least 4 -- in ring order, starting from the vertex that is smallest in
+ * (y, x).
+ * Area.  area2 = the sum of x_i * y_(i+1) - x_(i+1) * y_i over the ring, twice the signed area: positive for a ring with
+ * its region inside (clockwise on screen), negative for a hole.
+ * Order.  The rings of an image are ordered by (region, y of the start vertex, x of the start vertex); two rings of one
+ * region never share a start vertex.
+ * Outputs, with N the ring capacity and V the vertex capacity of an image, laid out so that (vertices, ring_start,
+ * ring_region, image_start) ARE valid input to isc_rasterize_polygons for B images, nothing copied and no host read:
+ *   vertices     int32 [B, V, 2], (256 x, 256 y): the fixed point of isc_rasterize_polygons
+ *   ring_start   int32 [B * (N + 1) + 1]: entry b * (N + 1) + j is b * V + the vertices of the image's rings before ring
+ *                j; for j at or past the rings held it is the end of the last ring; the final entry is B * V
+ *   ring_region  int32 [B, N + 1]: the region of ring j, -1 for unused rows; column N is always -1, so the "ring" between
+ *                two images' blocks is a skipped run
+ *   image_start  int32 [B + 1], b * (N + 1)
+ *   ring_area2   int64 [B, N] or NULL, 0 for unused rows
+ *   num_rings, num_vertices  int32 [B]: the TRUE counts, also above N and V
+ * An image that does not fit (num_rings > N or num_vertices > V) is written as EMPTY: its regions all -1, its ring_start
+ * entries all b * V, its area2 zeros, its vertices untouched; its counts say why, and a caller retries with the
+ * capacities they name (the pattern of isc_search_range).  rasterize(trace(ids)) gives back ids (values outside [0, R)
+ * as -1) under either fill rule: every vertex lies on the lattice and every pixel centre off it.
+ * The worst case is H * W rings and 4 * H * W vertices an image (a checkerboard of two regions).
+ *
+ * How: corner edges are counted per pixel_chunk pixels in raster order and scanned per image (num_vertices); every
+ * corner edge becomes a node, numbered in key order, and a thread per node walks its straight run to the next corner.
+ * ceil(log2(4 H W)) rounds of pointer jumping -- a number that depends on the shape alone -- give every node the smallest
+ * node of its ring, the ring's LEADER, and its distance behind it.  A leader on side 0 starts at the ring's start vertex
+ * (area2 > 0); one on side 2 ends its run there (a hole).  Leaders are counted per node_chunk nodes and scanned
+ * (num_rings); the rings of an image that fits are placed by counting the smaller (region, start vertex) keys, ring_tile
+ * keys at a time through LDS -- N * N / 2 comparisons an image at worst; the lengths are scanned in that order; a thread
+ * per node writes its vertex and adds its term of area2 with a 64-bit integer atomic.  11 + ceil(log2(4 H W)) launches;
+ * the same bytes on every run and wherever an image stands in the batch.  No thread waits for another; no host
+ * synchronisation, capturable; ids may be refilled in place between replays.
+ * Workspace: isc_trace_regions_workspace_bytes(B, H, W), about 168 bytes a pixel (two 16-byte jumping states for each of
+ * the 4 H W possible nodes), 16-byte aligned.  The call initialises whatever it reads: garbage on entry is fine.
+ * Limits: 1 <= H, W <= 32768, H * W < 2^29 (the count of 4 H W corner edges is an int32; the sides alone allow 2^30),
+ * B <= 65535, B * (N + 1) < 2^31, B * V < 2^31 (ISC_ERR_UNSUPPORTED); H, W, R, N, V < 1, B < 0, a connectivity other
+ * than 4 or 8, or ids or an output other than ring_area2 NULL: ISC_ERR_INVALID_ARG.  ISC_ERR_WORKSPACE: workspace NULL or
+ * too small.  ISC_ERR_ALIGNMENT: workspace off 16 bytes, vertices or ring_area2 off 8, any other pointer off 4.
+ * Everything is checked before anything is launched.  B == 0 returns ISC_OK without a launch. */
+int isc_trace_regions(const int32_t* ids, int B, int H, int W, int R, int connectivity, int N, int V, int32_t* vertices,
+                      int32_t* ring_start, int32_t* ring_region, int32_t* image_start, int64_t* ring_area2,
+                      int32_t* num_rings, int32_t* num_vertices, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The workspace of isc_trace_regions (host only, host pointer).  The shape errors of isc_trace_regions. */
+int isc_trace_regions_workspace_bytes(int B, int H, int W, size_t* bytes);
+
+/* The chunks of isc_trace_regions' scans over pixels and over nodes, the ring keys it stages at a time and the nodes of
+ * an image that its per-node launches cover in one pass (a thread strides over the rest) -- where its code paths change
+ * (host only, host pointers). */
+int isc_trace_regions_geometry(int* pixel_chunk, int* node_chunk, int* ring_tile, int* node_pass);
+
 #ifdef __cplusplus
 }
 #endif
