@@ -24,6 +24,9 @@ Public surface (same names as the reference where the reference has them):
 * `rasterize_polygons`, `pack_polygons`,
   `pool_polygons`, `PackedPolygons`              -- drawn polygons to region ids and to query vectors (new)
 * `trace_regions`, `RegionOutlines`              -- region ids back to polygon rings: outlines, holes, areas (new)
+* `overlap_table`, `confusion_matrix`,
+  `SegmentationScores`, `match_regions`,
+  `RegionMatches`                                -- two rasters compared: confusion matrices, mIoU, region IoU matching (new)
 
 All arithmetic runs in hand-written HIP kernels behind the C ABI of include/imagescry_hip.h;
 PyTorch is used for device memory, streams and `torch.distributed` only.
@@ -47,15 +50,20 @@ from imagescry_amd.pipelines import EmbeddingPCAPipeline, EmbedSearchPipeline, S
 from imagescry_amd.segmentation import (
     LabelMaps,
     PackedPolygons,
+    RegionMatches,
     RegionOutlines,
     Regions,
     RegionVectors,
+    SegmentationScores,
     class_scores,
+    confusion_matrix,
     create_roi_mask,
     crop_windows,
     label_map,
     label_map_windows,
     label_regions,
+    match_regions,
+    overlap_table,
     pack_polygons,
     pool_polygons,
     pool_regions,
@@ -85,20 +93,25 @@ __all__ = [
     "PCA",
     "PackedPolygons",
     "RangeResult",
+    "RegionMatches",
     "RegionOutlines",
     "Regions",
     "RegionVectors",
     "RowFilter",
     "ResNet50Embedder",
+    "SegmentationScores",
     "SigLIPEmbedder",
     "ViTB16Embedder",
     "class_scores",
     "clip",
+    "confusion_matrix",
     "create_roi_mask",
     "crop_windows",
     "label_map",
     "label_map_windows",
     "label_regions",
+    "match_regions",
+    "overlap_table",
     "pack_polygons",
     "pool_polygons",
     "pool_regions",

@@ -22,6 +22,7 @@ LIB_NAME = "libimagescry_hip.so"
 LIB_PATH = Path(os.environ.get("ISC_LIB") or Path(__file__).resolve().parent / LIB_NAME)
 
 ISC_U8, ISC_F16, ISC_F32 = 0, 1, 2
+ISC_I32 = 3  # isc_overlap_table
 ISC_ACT_NONE, ISC_ACT_RELU, ISC_ACT_GELU, ISC_ACT_SILU, ISC_ACT_SIGMOID, ISC_ACT_QUICK_GELU = 0, 1, 2, 3, 4, 5
 ISC_ACT_GELU_TANH = 6
 ISC_ACT_RESIDUAL_AFTER = 0x100
@@ -396,6 +397,13 @@ SIGNATURES: dict[str, tuple[object, list[object]]] = {
     ),
     "isc_trace_regions_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "isc_trace_regions_geometry": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "isc_overlap_table": (
+        c_int,
+        [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    ),
+    "isc_overlap_geometry": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "isc_overlap_best": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "isc_overlap_best_geometry": (c_int, [POINTER(c_int)]),
 }
 
 _lib: ctypes.CDLL | None = None

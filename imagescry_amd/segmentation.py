@@ -32,6 +32,12 @@ device (`isc_rasterize_polygons`: an exact integer definition of rasterio's `ras
 Outlines: `trace_regions` (or `Regions.outlines`) turns region ids back into polygon rings on the device
 (`isc_trace_regions`: rasterio's `shapes`, defined exactly) -- corners only, holes as rings of negative area, laid out as
 a `PackedPolygons` that `rasterize_polygons` takes as it is -- and `RegionOutlines.shapes()` brings them to the host.
+
+Two rasters compared: `overlap_table` counts the pixels of every pair of values in two aligned rasters on the device
+(`isc_overlap_table`: integer atomics, the same bytes on every run) -- `confusion_matrix` (or `LabelMaps.confusion`) is
+the batch-summed class table and `SegmentationScores` the mIoU, mAcc and aAcc of mmseg's `IoUMetric` from it;
+`match_regions` (or `Regions.match`) finds for every region of one id raster the region of the other it fits best by
+IoU, compared exactly (`isc_overlap_best`).
 """
 
 from __future__ import annotations
@@ -51,7 +57,9 @@ __all__ = ["LabelMaps", "UNLABELED", "MAX_PROMPTS", "MAX_CLASSES", "class_scores
            "segment", "window_grid", "crop_windows", "label_map_windows", "segment_windows", "Regions", "label_regions",
            "label_regions_geometry", "RegionVectors", "region_cell_weights", "pool_regions",
            "region_pool_geometry", "PackedPolygons", "pack_polygons", "rasterize_polygons", "rasterize_geometry",
-           "create_roi_mask", "pool_polygons", "RegionOutlines", "trace_regions", "trace_geometry"]
+           "create_roi_mask", "pool_polygons", "RegionOutlines", "trace_regions", "trace_geometry", "overlap_table",
+           "overlap_geometry", "overlap_best_geometry", "confusion_matrix", "SegmentationScores", "RegionMatches",
+           "match_regions"]
 
 UNLABELED = 255  # the label of a pixel whose best score is NaN or below `min_score`
 MAX_PROMPTS = 1024  # isc_label_map: 1 <= C <= 1024
@@ -92,6 +100,10 @@ class LabelMaps:
     def regions(self, **kw: object) -> "Regions":
         """`label_regions(self, **kw)`: the connected regions of these maps, `scores` scoring the peaks."""
         return label_regions(self, **kw)
+
+    def confusion(self, target: Tensor, num_classes: int, out: Tensor | None = None) -> Tensor:
+        """`confusion_matrix(self, target, num_classes, out=out)`: these maps as the prediction against `target`."""
+        return confusion_matrix(self, target, num_classes, out=out)
 
 
 def label_map_geometry() -> tuple[int, int, int]:
@@ -438,6 +450,13 @@ class Regions:
         out = trace_regions(self.ids, int(self.label.shape[1]), **kw)
         return RegionOutlines(out.packed, out.ring_area2, out.num_rings, out.num_vertices, out.size, out.max_rings,
                               out.max_vertices, self.label, self.num, self.indices)
+
+    def match(self, other: "Regions", **kw: object) -> "RegionMatches":
+        """`match_regions(self, other, R, R', **kw)`, R and R' the rows of the two tables: the region of `other` every
+        region here fits best."""
+        if not isinstance(other, Regions):
+            raise TypeError(f"other must be a Regions (match_regions takes rasters), got {type(other).__name__}")
+        return match_regions(self, other, int(self.label.shape[1]), int(other.label.shape[1]), **kw)
 
 
 def label_regions_geometry() -> tuple[int, int]:
@@ -1098,3 +1117,287 @@ def trace_regions(ids: Tensor, num_regions: int, *, connectivity: int = 8, max_r
     _lib.check(st, "isc_trace_regions")
     return RegionOutlines(PackedPolygons(vertices, ring_start, ring_region, image_start, rows), area2, num_rings,
                           num_vertices, (big_h, big_w), n, v)
+
+
+# ------------------------------------------------------------------------------------------------------ overlap tables
+MAX_OVERLAP_PIXELS = 2**31 - 1  # isc_overlap_table: H * W < 2^31
+MAX_OVERLAP_TABLE = 2**25  # ... and (Ra + 1) * (Rb + 1) <= 2^25: a pair's key is a non-negative int32
+MAX_OVERLAP_MAPS = 65535  # images a launch
+OVERLAP_PASS_BYTES = POOL_PASS_BYTES  # the tables of one pass of match_regions: the rule of pool_regions
+
+
+def overlap_geometry() -> tuple[int, int, int]:
+    """(tile_w, tile_h, slots): the pixels a workgroup of `isc_overlap_table` owns and the pairs its LDS table holds."""
+    tw, th, slots = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().isc_overlap_geometry(tw, th, slots), "isc_overlap_geometry")
+    return tw.value, th.value, slots.value
+
+
+def overlap_best_geometry() -> int:
+    """The columns `isc_overlap_best` reduces at a time."""
+    columns = ctypes.c_int()
+    _lib.check(_lib.load().isc_overlap_best_geometry(columns), "isc_overlap_best_geometry")
+    return columns.value
+
+
+def _overlap_raster(name: str, t: object) -> Tensor:
+    if isinstance(t, LabelMaps):
+        t = t.labels
+    elif isinstance(t, Regions):
+        t = t.ids
+    if not isinstance(t, Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, LabelMaps or Regions, got {type(t).__name__}")
+    if t.dtype not in (torch.uint8, torch.int32):
+        raise TypeError(f"{name} must be uint8 or int32, got {t.dtype}")
+    if t.ndim != 3:
+        raise ValueError(f"{name} must have shape [B, H, W], got {tuple(t.shape)}")
+    return t
+
+
+def _check_overlap_pair(a: object, b: object, num_a: object, num_b: object) -> tuple[Tensor, Tensor, int, int]:
+    a, b = _overlap_raster("a", a), _overlap_raster("b", b)
+    ra, rb = _check_count("num_a", num_a), _check_count("num_b", num_b)
+    if a.shape != b.shape:
+        raise ValueError(f"a {tuple(a.shape)} and b {tuple(b.shape)} must have one shape")
+    big_h, big_w = (int(v) for v in a.shape[1:])
+    if big_h < 1 or big_w < 1:
+        raise ValueError(f"the rasters must hold at least one pixel an image, got {big_h} x {big_w}")
+    if big_h * big_w > MAX_OVERLAP_PIXELS:
+        raise ValueError(f"rasters of {big_h} x {big_w} pixels have 2^31 pixels or more")
+    if (ra + 1) * (rb + 1) > MAX_OVERLAP_TABLE:
+        raise ValueError(f"a table of {ra + 1} x {rb + 1} entries exceeds the 2^25 entries of an overlap table")
+    _lib.require_device(a, "a")
+    if b.device != a.device:
+        raise ValueError(f"a is on {a.device} but b on {b.device}")
+    return a.contiguous(), b.contiguous(), ra, rb
+
+
+def _overlap_dtype(t: Tensor) -> int:
+    return _lib.ISC_U8 if t.dtype == torch.uint8 else _lib.ISC_I32
+
+
+def _overlap_into(a: Tensor, b: Tensor, ra: int, rb: int, per_image: bool, accumulate: bool, table: Tensor) -> None:
+    """isc_overlap_table of contiguous `a` and `b` into contiguous `table`, in launches of at most 65 535 images."""
+    lib = _lib.load()
+    big_h, big_w = (int(v) for v in a.shape[1:])
+    for i in range(0, a.shape[0], MAX_OVERLAP_MAPS):
+        n = min(MAX_OVERLAP_MAPS, a.shape[0] - i)
+        part = table[i:i + n] if per_image else table
+        with torch.cuda.device(a.device):
+            st = lib.isc_overlap_table(a[i:i + n].data_ptr(), _overlap_dtype(a), b[i:i + n].data_ptr(), _overlap_dtype(b), n,
+                                       big_h, big_w, ra, rb, int(per_image), int(accumulate or (i > 0 and not per_image)),
+                                       part.data_ptr(), _lib.stream_handle(a.device))
+        _lib.check(st, "isc_overlap_table")
+
+
+def overlap_table(a: "Tensor | LabelMaps | Regions", b: "Tensor | LabelMaps | Regions", num_a: int, num_b: int, *,
+                  per_image: bool = True, out: Tensor | None = None) -> Tensor:
+    """How many pixels carry every pair of values in two aligned rasters (`isc_overlap_table`, include/imagescry_hip.h
+    has the definition): int64 `[B, num_a + 1, num_b + 1]`, or `[num_a + 1, num_b + 1]` summed over the batch with
+    `per_image=False`.  `a` and `b` are uint8 or int32 `[B, H, W]` of one shape on one device, each with its own dtype; a
+    `LabelMaps` stands for its `labels`, a `Regions` for its `ids`.  Entry `[.., i, j]` counts the pixels whose value is
+    `i` in `a` and `j` in `b`; a value outside `[0, num_a)` -- a negative id, an id beyond a truncated table,
+    `UNLABELED`, an ignore index -- counts at the "none" index `num_a`, and likewise `num_b` for `b`.  Every pixel is
+    counted once: a per-image table sums to `H * W`.
+
+    `out=`: an int64 table of that shape on the device, to which the counts are ADDED -- the running total over a
+    dataset (and a captured call with `out=` adds again on every replay).  Integer atomics throughout: the same bytes
+    on every run, for an image wherever it stands in a batch; capturable; nothing synchronises with the host."""
+    a, b, ra, rb = _check_overlap_pair(a, b, num_a, num_b)
+    if not isinstance(per_image, bool):
+        raise TypeError("per_image must be a bool")
+    shape = (a.shape[0], ra + 1, rb + 1) if per_image else (ra + 1, rb + 1)
+    if out is None:
+        # an empty batch launches nothing, so nothing zeroes its table
+        table = (torch.empty if a.shape[0] else torch.zeros)(shape, dtype=torch.int64, device=a.device)
+    else:
+        if not isinstance(out, Tensor):
+            raise TypeError(f"out must be a torch.Tensor, got {type(out).__name__}")
+        if out.dtype != torch.int64:
+            raise TypeError(f"out must be int64, got {out.dtype}")
+        if tuple(out.shape) != shape:
+            raise ValueError(f"out must have shape {shape}, got {tuple(out.shape)}")
+        if out.device != a.device:
+            raise ValueError(f"a is on {a.device} but out on {out.device}")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous: the counts are added to it in place")
+        table = out
+    _overlap_into(a, b, ra, rb, per_image, out is not None, table)
+    return table
+
+
+def confusion_matrix(pred: "Tensor | LabelMaps", target: Tensor, num_classes: int, *, out: Tensor | None = None) -> Tensor:
+    """The class confusion matrix of a batch, int64 `[C + 1, C + 1]` with C = `num_classes`: entry `[i, j]` counts the
+    pixels predicted as class `i` whose target is class `j` -- rows are the prediction, columns the target -- and row and
+    column C hold the pixels without a class: `UNLABELED` predictions, an `ignore_index` (255, -100, ...) in the target.
+    `overlap_table(pred, target, C, C, per_image=False, out=out)`; an int64 target (torch's usual dtype for label
+    maps) is narrowed to int32 first, which keeps every value a label map holds.  `out=` adds to a running matrix: one
+    per dataset, `SegmentationScores.from_confusion` at the end."""
+    if isinstance(target, Tensor) and target.dtype == torch.int64:
+        target = target.to(torch.int32)
+    rows = _check_count("num_classes", num_classes)
+    return overlap_table(pred, target, rows, rows, per_image=False, out=out)
+
+
+def _ratio(num: Tensor, den: Tensor) -> Tensor:
+    return num.to(torch.float64) / den.to(torch.float64)  # 0 / 0 is NaN
+
+
+def _nan_mean(values: Tensor) -> Tensor:
+    """The mean of the non-NaN entries of a float64 vector, NaN without any, in a FIXED order of additions: NaN reads
+    as 0, the vector is padded with zeros to a power of two, and neighbours `v[2k] + v[2k + 1]` are added until one value
+    is left, which is divided by the count.  A library reduction picks its order by device and size; this one gives the
+    same bits everywhere."""
+    valid = ~torch.isnan(values)
+    v = torch.where(valid, values, torch.zeros_like(values))
+    size = 1 << max(0, v.numel() - 1).bit_length()
+    v = torch.cat([v, v.new_zeros(size - v.numel())])
+    while v.numel() > 1:
+        v = v[0::2] + v[1::2]
+    return v[0] / valid.sum().to(torch.float64)
+
+
+@dataclass(frozen=True)
+class SegmentationScores:
+    """The per-class counts of mmseg's `IoUMetric` from a confusion matrix T (rows the prediction, columns the target,
+    index C "none"), int64 `[C]` each.  Pixels whose target is "none" are ignored entirely; an unlabeled prediction on a
+    labeled pixel counts against the target's class.
+
+    intersect:   `T[c, c]`
+    pred_area:   the sum of `T[c, j]` over `j < C`
+    target_area: the sum of `T[i, c]` over `i <= C`
+    union:       `pred_area + target_area - intersect`"""
+
+    intersect: Tensor
+    pred_area: Tensor
+    target_area: Tensor
+    union: Tensor
+
+    @classmethod
+    def from_confusion(cls, table: Tensor) -> "SegmentationScores":
+        """From an int64 `[C + 1, C + 1]` table of `confusion_matrix`, on the table's device, without a host read."""
+        if not isinstance(table, Tensor):
+            raise TypeError(f"table must be a torch.Tensor, got {type(table).__name__}")
+        if table.dtype != torch.int64:
+            raise TypeError(f"table must be int64, got {table.dtype}")
+        if table.ndim != 2 or table.shape[0] != table.shape[1] or table.shape[0] < 2:
+            raise ValueError(f"table must have shape [C + 1, C + 1] with C >= 1, got {tuple(table.shape)}")
+        c = table.shape[0] - 1
+        intersect = torch.diagonal(table)[:c].contiguous()
+        pred_area = table[:c, :c].sum(dim=1)
+        target_area = table[:, :c].sum(dim=0)
+        return cls(intersect, pred_area, target_area, pred_area + target_area - intersect)
+
+    def to(self, device: str | torch.device) -> "SegmentationScores":
+        return SegmentationScores(*(t.to(device) for t in (self.intersect, self.pred_area, self.target_area, self.union)))
+
+    def cpu(self) -> "SegmentationScores":
+        return self.to("cpu")
+
+    @property
+    def device(self) -> torch.device:
+        return self.intersect.device
+
+    def __len__(self) -> int:
+        return self.intersect.shape[0]
+
+    def iou(self) -> Tensor:
+        """float64 `[C]`, `intersect / union`; NaN for a class in neither prediction nor target."""
+        return _ratio(self.intersect, self.union)
+
+    def accuracy(self) -> Tensor:
+        """float64 `[C]`, `intersect / target_area`; NaN for a class absent from the target."""
+        return _ratio(self.intersect, self.target_area)
+
+    def dice(self) -> Tensor:
+        """float64 `[C]`, `2 * intersect / (pred_area + target_area)`; NaN where both are empty."""
+        return _ratio(2 * self.intersect, self.pred_area + self.target_area)
+
+    def miou(self) -> Tensor:
+        """0-dim float64: the mean of `iou()` over the classes where it is not NaN (a fixed order of additions: the same
+        bits on every device)."""
+        return _nan_mean(self.iou())
+
+    def macc(self) -> Tensor:
+        """0-dim float64: the mean of `accuracy()` over the classes where it is not NaN."""
+        return _nan_mean(self.accuracy())
+
+    def aacc(self) -> Tensor:
+        """0-dim float64: `intersect.sum() / target_area.sum()`, the share of labeled pixels predicted right."""
+        return _ratio(self.intersect.sum(), self.target_area.sum())
+
+
+@dataclass(frozen=True)
+class RegionMatches:
+    """What `match_regions` returns: for every region of `a` its best partner in `b` by IoU.
+
+    best:  int32 `[B, num_a]`, the region of `b`, -1 for a region that overlaps none (or has no pixels)
+    inter: int64 `[B, num_a]`, the pixels the two share
+    union: int64 `[B, num_a]`, the pixels of either; the region's own area where `best` is -1
+    best_b, inter_b, union_b: the same for every region of `b` against `a`, `[B, num_b]` (`both=True`), else None"""
+
+    best: Tensor
+    inter: Tensor
+    union: Tensor
+    best_b: Tensor | None = None
+    inter_b: Tensor | None = None
+    union_b: Tensor | None = None
+
+    def to(self, device: str | torch.device) -> "RegionMatches":
+        return RegionMatches(*(None if t is None else t.to(device)
+                               for t in (self.best, self.inter, self.union, self.best_b, self.inter_b, self.union_b)))
+
+    def cpu(self) -> "RegionMatches":
+        return self.to("cpu")
+
+    @property
+    def device(self) -> torch.device:
+        return self.best.device
+
+    def __len__(self) -> int:
+        return self.best.shape[0]
+
+    def iou(self) -> Tensor:
+        """float64 `[B, num_a]`, `inter / union`; NaN for a region without pixels.  Above 1/2 the match is mutual."""
+        return _ratio(self.inter, self.union)
+
+    def iou_b(self) -> Tensor:
+        """float64 `[B, num_b]`, `inter_b / union_b` (`both=True`)."""
+        if self.inter_b is None:
+            raise ValueError("these matches were computed without both=True")
+        return _ratio(self.inter_b, self.union_b)
+
+
+def match_regions(a: "Tensor | LabelMaps | Regions", b: "Tensor | LabelMaps | Regions", num_a: int, num_b: int, *,
+                  exclude_none: bool = False, both: bool = False) -> RegionMatches:
+    """For every region of `a` the region of `b` it fits best: the largest IoU among the regions it shares a pixel with,
+    compared exactly in integers, ties to the lower id (`isc_overlap_table` + `isc_overlap_best`, include/imagescry_hip.h
+    has the definition).  `a`, `b`, `num_a`, `num_b` as in `overlap_table`, per image.  A region's area counts all of
+    its pixels; with `exclude_none=True` only those that lie on some region of the other raster (pixels that are "none"
+    on the other side are left out of both areas).  `both=True` also answers for every region of `b`.  Two regions with
+    IoU above 1/2 are each other's unique best.  Runs in passes of images whose tables stay within 256 MiB; the number of
+    launches depends on the shapes alone, and nothing synchronises with the host."""
+    a, b, ra, rb = _check_overlap_pair(a, b, num_a, num_b)
+    if not isinstance(exclude_none, bool) or not isinstance(both, bool):
+        raise TypeError("exclude_none and both must be bools")
+    device = a.device
+    n_img = a.shape[0]
+    step = max(1, min(OVERLAP_PASS_BYTES // ((ra + 1) * (rb + 1) * 8), MAX_OVERLAP_MAPS))  # images a pass
+    tables = torch.empty((min(n_img, step), ra + 1, rb + 1), dtype=torch.int64, device=device)
+
+    def outputs(rows: int) -> tuple[Tensor, Tensor, Tensor]:
+        return (torch.empty((n_img, rows), dtype=torch.int32, device=device),
+                torch.empty((n_img, rows), dtype=torch.int64, device=device),
+                torch.empty((n_img, rows), dtype=torch.int64, device=device))
+
+    found = [outputs(ra)] + ([outputs(rb)] if both else [])
+    lib = _lib.load()
+    for i in range(0, n_img, step):
+        n = min(step, n_img - i)
+        _overlap_into(a[i:i + n], b[i:i + n], ra, rb, True, False, tables[:n])
+        for axis, (best, inter, union) in enumerate(found):
+            with torch.cuda.device(device):
+                st = lib.isc_overlap_best(tables.data_ptr(), n, ra, rb, axis, int(exclude_none), best[i:i + n].data_ptr(),
+                                          inter[i:i + n].data_ptr(), union[i:i + n].data_ptr(), _lib.stream_handle(device))
+            _lib.check(st, "isc_overlap_best")
+    return RegionMatches(*found[0], *(found[1] if both else (None, None, None)))

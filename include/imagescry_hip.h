@@ -43,6 +43,7 @@ extern "C" {
 #define ISC_U8 0
 #define ISC_F16 1
 #define ISC_F32 2
+#define ISC_I32 3 /* rasters of ids: isc_overlap_table */
 
 /* status codes */
 #define ISC_OK 0
@@ -1298,6 +1299,63 @@ int isc_trace_regions_workspace_bytes(int B, int H, int W, size_t* bytes);
  * an image that its per-node launches cover in one pass (a thread strides over the rest) -- where its code paths change
  * (host only, host pointers). */
 int isc_trace_regions_geometry(int* pixel_chunk, int* node_chunk, int* ring_tile, int* node_pass);
+
+/* Two rasters compared: the 2-D histogram of value pairs over the pixels of two aligned rasters -- a class confusion
+ * matrix (mIoU), or the overlap of every pair of regions of two id rasters (region matching, duplicates, coverage).
+ *   a, b     [B, H, W] of a_dtype / b_dtype, ISC_U8 or ISC_I32 each on its own
+ *   table    int64 [B, Ra + 1, Rb + 1] with per_image != 0, else [Ra + 1, Rb + 1], summed over the batch
+ * The a-index of a pixel is its value v in `a` if 0 <= v < Ra, else Ra: the "none" slot, which takes negative ids, ids
+ * beyond a truncated table, the unlabeled 255 of a label map when Ra <= 255, and an ignore index.  The b-index likewise
+ * with Rb.  table[..][i][j] = the number of pixels with a-index i and b-index j: every pixel is counted exactly once, so
+ * a per-image table sums to H * W.
+ * accumulate == 0: the call zeroes the table itself (a launch ahead of the kernel: garbage on entry is fine and a
+ * replayed graph starts from zero).  accumulate != 0: the counts are ADDED to what the table holds -- the running total
+ * over a dataset; a replayed graph adds again on every replay.
+ * Only integer atomics are used -- a workgroup owns a tile_w x tile_h tile of pixels (isc_overlap_geometry), sums equal
+ * pairs along a wave's row and in an LDS table of `slots` keys, and adds every pair of the tile to memory once; pairs
+ * that find no slot are added directly -- so the result does not depend on the order in which they land: the same bytes
+ * on every run, whatever B is and wherever an image stands in the batch.
+ * Limits: H, W, Ra, Rb >= 1, B >= 0, both dtypes ISC_U8 or ISC_I32 (ISC_ERR_INVALID_ARG); H * W < 2^31, B <= 65535,
+ * (Ra + 1) * (Rb + 1) <= 2^25 (a pair's key is a non-negative int32) (ISC_ERR_UNSUPPORTED); a, b or table NULL is
+ * ISC_ERR_INVALID_ARG; a and b aligned to their element size, table to 8 bytes (ISC_ERR_ALIGNMENT).  Everything is
+ * checked before anything is launched.  B == 0 is checked like any other shape and then returns ISC_OK without a launch
+ * and without a look at the pointers: it zeroes nothing, also with accumulate == 0.  No workspace, no host
+ * synchronisation, capturable; a and b may be refilled in place between replays. */
+int isc_overlap_table(const void* a, int a_dtype, const void* b, int b_dtype, int B, int H, int W, int Ra, int Rb,
+                      int per_image, int accumulate, int64_t* table, void* stream);
+
+/* The pixels a workgroup of isc_overlap_table owns and the pairs its LDS table holds -- where its code paths change
+ * (host only, host pointers). */
+int isc_overlap_geometry(int* tile_w, int* tile_h, int* slots);
+
+/* The best partner by IoU of every region, from per-image tables [B, Ra + 1, Rb + 1] of isc_overlap_table.
+ * axis == 0: for every row i < Ra the best column j < Rb; best int32, inter and uni int64, each [B, Ra].  With
+ *   I = table[i][j],
+ *   area_a[i] = the sum of row i over j <= Rb (over j < Rb with exclude_none != 0: pixels that are "none" in b do not
+ *               count towards a's areas),
+ *   area_b[j] = the sum of column j over i <= Ra (over i < Ra with exclude_none != 0),
+ *   U = area_a[i] + area_b[j] - I,
+ * the best j is, among those with I > 0, the one with the largest I / U -- compared exactly, I * U' against I' * U in
+ * unsigned 64-bit arithmetic; ties go to the lower j.  best = j, inter = I, uni = U; a row that overlaps no region gets
+ * (-1, 0, area_a[i]).  axis == 1 asks the same of the transposed table: for every column j < Rb the best row i < Ra,
+ * outputs [B, Rb].  Any other axis is ISC_ERR_INVALID_ARG.
+ * Precondition: every row sum and every column sum of a table is below 2^31, so that I < 2^31, U < 2^32 and the
+ * products stay below 2^63.  A per-image table of ONE isc_overlap_table call satisfies it (H * W < 2^31); a table
+ * accumulated over many calls may not, and the answer is then unspecified (nothing is read or written out of bounds).
+ * Two regions with IoU > 1/2 are each other's unique best: if I / U > 1/2 then I is more than half of both areas, so
+ * any other partner of either shares less than half of that region's area and has IoU < 1/2.  Matching by
+ * "best with IoU > 1/2" is therefore one-to-one with either axis (the matching of panoptic quality).
+ * A workgroup per image: the row sums first, then per chunk of `columns` columns (isc_overlap_best_geometry) the
+ * column sums through LDS and every row's best in the chunk, a wave per row; the running best of a row is kept in
+ * the outputs themselves.  No workspace, one launch, no host synchronisation, capturable, the same bytes on every run.
+ * Limits: Ra, Rb >= 1, B >= 0 (ISC_ERR_INVALID_ARG); B <= 65535, (Ra + 1) * (Rb + 1) <= 2^25 (ISC_ERR_UNSUPPORTED);
+ * table, best, inter or uni NULL is ISC_ERR_INVALID_ARG; best 4-byte aligned, the others 8-byte (ISC_ERR_ALIGNMENT).
+ * B == 0 as isc_overlap_table. */
+int isc_overlap_best(const int64_t* table, int B, int Ra, int Rb, int axis, int exclude_none, int32_t* best,
+                     int64_t* inter, int64_t* uni, void* stream);
+
+/* The columns isc_overlap_best reduces at a time (host only, host pointer). */
+int isc_overlap_best_geometry(int* columns);
 
 #ifdef __cplusplus
 }
